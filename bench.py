@@ -8,6 +8,10 @@ and nodes are HBM-resident before the timed region.  value = P x N / time (every
 semantics evaluates), summed over the whole job.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4] [--mode batched|exact]
+                  [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what takes time of
+its own: the CPU baselines, the prefix check against the CPU oracle, and (stream pipeline) the per-kernel
+timing pass.  --dump-outputs DIR writes the last timed step's results as DIR/<name>.npy.
   N > 1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 """
 import argparse
@@ -73,10 +77,14 @@ def parse():
     ap.add_argument("--topk", type=int, default=16)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--cpu-baseline-s", type=float, default=12.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-check", action="store_true",
-                    help="skip the (untimed) prefix check of the timed run's results against the CPU oracle")
+                    help="--full without the (untimed) prefix check of the timed run's results against the CPU oracle")
     ap.add_argument("--check-pods", type=int, default=5000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baselines, the oracle prefix check and the per-kernel timing pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--no-xchg", action="store_true", help="N > 1: RCCL stream pipeline instead of the device-side exchange")
     return ap.parse_args()
 
@@ -136,8 +144,31 @@ def cpu_baseline(cl, budget_s):
                        f"({t:.1f} s; Go reference unbuildable here: no Go toolchain)"), mt
 
 
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: all files together, headers included, stay under 64 MB
+DUMP_SEED = 20240607
+
+
+def dump_outputs(path, res):
+    """The arrays a caller of the timed path receives (Engine.results(): node index, score, feasible
+    count per pod) as float64 .npy files; int32 values are exact in float64.  An output too large for
+    DUMP_MAX_BYTES is sampled at fixed, seeded pod indices (the same for every array, written too)."""
+    os.makedirs(path, exist_ok=True)
+    names = ("node_index", "score", "feasible_count")
+    p = res[0].shape[0]
+    cap = DUMP_MAX_BYTES // 8 // (len(names) + 1)
+    sel = None
+    if p > cap:
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(p, size=cap, replace=False))
+        np.save(os.path.join(path, "sample_pod_index.npy"), sel.astype(np.float64))
+    for name, a in zip(names, res):
+        a = a if sel is None else a[sel]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
+    if args.steps < 1:
+        sys.exit("--steps must be at least 1")
     from ksched import MODE_BATCHED, MODE_EXACT, cluster
     from ksched.dist import env_rank, make_sharded_engine
     rank, world, local = env_rank()
@@ -219,14 +250,18 @@ def main():
     pairs = cl.n_pods * cl.n_nodes
     value = pairs * args.steps / elapsed
     st = step_stats[-1] if step_stats else eng.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     if persistent and step_stats:
         eng.set_timing(False)
         kstats = step_stats
-    else:
+    elif args.full:
         eng.set_timing(True, 8)
         step()
         kstats = [eng.stats()]
         eng.set_timing(False)
+    else:
+        kstats = []  # the stream pipeline's per-kernel figures take a pass of their own (--full)
     names = (["k_exact"] if mode == MODE_EXACT else ["k_pipe" if persistent else "k_score_topk"]) + \
         ["k_merge", "k_commit", "rccl_allgather+merge"]
     fam_ms = [sum(s["kernel_ms"][f] for s in kstats) for f in range(4)]
@@ -306,15 +341,16 @@ def main():
         "batches_per_step": int(st["batches"]),
         "truncated_batches_per_step": int(st["truncations"]),
         "rescued_lists_per_step": int(st.get("rescues", 0)),
-        "kernel_avg_ms": fam_share,
-        "roofline": roof,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if kstats:
+        out["kernel_avg_ms"] = fam_share
+        out["roofline"] = roof
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         base, mt = cpu_baseline(cl, args.cpu_baseline_s)
         out["cpu_baseline"] = base
         if mt:
             out["cpu_baseline_mt"] = mt
-    if not args.no_check and rank == 0:
+    if args.full and not args.no_check and rank == 0:
         # the timed run's own results, prefix against the CPU oracle (pods resolve in order, so the
         # first k results of the full run are the results of a k-pod run); outside the timed region
         sys.path.insert(0, os.path.join(ROOT, "oracle"))

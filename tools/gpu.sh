@@ -32,7 +32,7 @@ trace() {  # trace <name> [bench args]: the c4 phase trace, raw per-batch stamps
 }
 bench() {  # bench <name> [bench args]
   local name=$1; shift
-  step "$name" 300 python -u bench.py --steps 5 --warmup 1 --no-cpu-baseline "$@" &&
+  step "$name" 300 python -u bench.py --full --steps 5 --warmup 1 --no-cpu-baseline "$@" &&
   grep -o '"value": [0-9.e+]*\|"truncated_batches_per_step": [0-9]*\|"rescued_lists_per_step": [0-9]*\|"check_ok": [a-z]*' \
     "gpurun_out/$name.log" | tr '\n' ' '; echo
 }

@@ -26,7 +26,7 @@ pass() {  # pass <name> <counters...>
 }
 stats() {
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o run \
-    -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 > "$out/stats_bench.json" 2> "$out/stats.err"
+    -- python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > "$out/stats_bench.json" 2> "$out/stats.err"
   local rc=$?
   rm -f "$out"/stats/run_kernel_trace.csv  # one row per launch: large, summarised by run_kernel_stats.csv
   echo "stats rc=$rc"
