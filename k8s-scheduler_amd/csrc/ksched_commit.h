@@ -217,7 +217,7 @@ __device__ __forceinline__ bool rescue_rank_fold(const PersistArgs &X, unsigned 
         for (int i = 0; i < kXchgRescueWords; ++i) rw[i] = 0;
     }
     if (__ballot(!ok)) {
-        if (lane == 0) atomicCAS(err, 0, 12);
+        if (lane == 0) atomicCAS(err, 0, kErrWaitRescue);
         return false;
     }
     Rec rr;
@@ -266,7 +266,7 @@ __device__ __forceinline__ bool commit_rescue(const CommitArgs &A, int f, int64_
         ok = poll_ge(&A.ctl->rescue_done.v, q * (unsigned long long)A.rescue_n, A.timeout_ticks, &A.ctl->polls_rmw,
                      &seen) ? 1 : 0;
         if (A.trace_row) A.trace_row[17] += wall_clock64() - t0;  // time the rescues kept the commit waiting
-        if (!ok) atomicCAS(A.err, 0, 12);
+        if (!ok) atomicCAS(A.err, 0, kErrWaitRescue);
     }
     ok = __builtin_amdgcn_readfirstlane(ok);
     if (!ok) return false;
@@ -1249,7 +1249,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             const int l = (int)__builtin_ctzll(bm);
             const int src = __builtin_amdgcn_readlane(my_src, l);
             const int val = __builtin_amdgcn_readlane(my_idx, l);
-            if (lane == 0 && atomicCAS(A.err, 0, 14) == 0 && A.xp && A.xp->prog) {  // the words the host reports
+            if (lane == 0 && atomicCAS(A.err, 0, kErrBadIndex) == 0 && A.xp && A.xp->prog) {  // the words the host reports
                 A.xp->prog[kProgWords * (A.xp->G + A.xp->B) + 3] =
                     (uint64_t)A.batch << 40 | (uint64_t)l << 32 | (uint64_t)(uint32_t)src;
                 A.xp->prog[kProgWords * (A.xp->G + A.xp->B) + 4] = (uint64_t)(uint32_t)val;

@@ -1,0 +1,300 @@
+// ksched_data.hip -- libksched: the calls that move data in and out of a context.  Node rows (load, delta, read,
+// save / restore), pending pods, per-pod results, and the FailedScheduling explanations.
+#include <cmath>
+#include <cstring>
+
+#include "ksched_ctx.h"
+
+using namespace ksched;
+
+static uint64_t uabs(int64_t v) { return v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v; }
+
+extern "C" {
+
+int ksched_load_nodes(ksched_ctx *c, int64_t n, const int64_t *ac, const int64_t *am, const int64_t *ap,
+                      const uint64_t *labels, const float *price) {
+    if (!c) return KSCHED_E_INVALID;
+    if (n < 0 || (n > 0 && (!ac || !am || !ap))) return fail(c, KSCHED_E_INVALID, "load_nodes: bad arguments");
+    if (c->o.use_labels && n > 0 && !labels) return fail(c, KSCHED_E_INVALID, "load_nodes: use_labels needs labels");
+    if (c->o.priority == KSCHED_PRIORITY_BEST_PRICE && n > 0 && !price)
+        return fail(c, KSCHED_E_INVALID, "load_nodes: best-price priority needs prices");
+    // node indices are int32 on the device and kNoIdx (INT32_MAX) marks "no candidate": every global
+    // index this rank produces (node_offset + local) must stay below it
+    if (c->o.node_offset < 0 || n > 0x7ffffff0LL || c->o.node_offset + n > 0x7ffffff0LL)
+        return fail(c, KSCHED_E_INVALID, "load_nodes: node_offset + n must stay below 2^31 - 16");
+    std::vector<NodeRec> h((size_t)std::max<int64_t>(n, 0));
+    uint64_t mx = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        NodeRec &r = h[(size_t)i];
+        r.a[0] = ac[i]; r.a[1] = am[i]; r.a[2] = ap[i];
+        r.af[0] = r.af[1] = r.af[2] = 0.0;  // derived on the device (k_prep_nodes) with the reciprocals
+        r.y[0] = r.y[1] = r.y[2] = 0.0;
+        r.labels = labels ? labels[i] : 0;
+        r.price = (price && price[i] != 0.f) ? price[i] : 0.f;  // "-0" == "0": canonical +0 (price_key)
+        r.ys[0] = r.ys[1] = r.ys[2] = 0.f;
+        mx = std::max(mx, std::max(uabs(ac[i]), std::max(uabs(am[i]), uabs(ap[i]))));
+        if (price && !std::isfinite(price[i])) return fail(c, KSCHED_E_INVALID, "load_nodes: non-finite price");
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->perm_n = -1;  // first: whatever happens below, d->perm no longer describes the loaded nodes
+    HIPCHK(c, c->d->nodes.reserve((size_t)n * sizeof(NodeRec)));
+    c->d->snap.release();
+    // in the stream of the kernels that read it (a legacy hipMemcpy from pageable memory may return before its DMA
+    // lands, and nothing orders it with this non-blocking stream: k_prep_nodes read the memory's earlier contents --
+    // the round-4 exchange failure)
+    if (n > 0) HIPCHK(c, hipMemcpyAsync(c->d->nodes, h.data(), (size_t)n * sizeof(NodeRec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_prep_nodes(c->d->nodes, n, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->max_abs_alloc = mx;
+    c->n_local = n;
+    c->explain_valid = false;
+    c->n_global = c->o.nranks > 1 ? c->o.nodes_global : (c->o.nodes_global > 0 ? c->o.nodes_global : n);
+    if (c->n_global < c->o.node_offset + n) return fail(c, KSCHED_E_INVALID, "load_nodes: nodes_global too small");
+    if (price && n > 0 && n <= (int64_t)kExact1Block * 16) {
+        // exact mode on one workgroup (k_exact1): the nodes in the best-price argmax's order -- price ascending,
+        // node index ascending on ties (prices are finite, -0 canonical: the order of price_key descending)
+        std::vector<int32_t> perm((size_t)n);
+        for (int64_t i = 0; i < n; ++i) perm[(size_t)i] = (int32_t)i;
+        std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) { return h[(size_t)x].price < h[(size_t)y].price; });
+        HIPCHK(c, c->d->perm.reserve((size_t)n * sizeof(int32_t)));
+        HIPCHK(c, hipMemcpyAsync(c->d->perm, perm.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->perm_n = n;
+    } else {
+        c->d->perm.release();
+    }
+    return KSCHED_OK;
+}
+
+int ksched_apply_delta(ksched_ctx *c, int64_t k, const int32_t *idx, const int64_t *dc, const int64_t *dm,
+                       const int64_t *dp) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "apply_delta before load_nodes");
+    if (k < 0 || (k > 0 && (!idx || !dc || !dm || !dp))) return fail(c, KSCHED_E_INVALID, "apply_delta: bad arguments");
+    if (k == 0) return KSCHED_OK;
+    for (int64_t i = 0; i < k; ++i) {
+        if (idx[i] < 0 || idx[i] >= c->n_local) return fail(c, KSCHED_E_INVALID, "apply_delta: node index out of range");
+        c->max_abs_alloc = sat_add(c->max_abs_alloc, sat_add(uabs(dc[i]), sat_add(uabs(dm[i]), uabs(dp[i]))));
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    std::vector<int64_t> d((size_t)(3 * k));
+    std::memcpy(d.data(), dc, (size_t)k * 8);
+    std::memcpy(d.data() + k, dm, (size_t)k * 8);
+    std::memcpy(d.data() + 2 * k, dp, (size_t)k * 8);
+    int32_t *d_idx = nullptr;
+    int64_t *d_d = nullptr;
+    HIPCHK(c, hipMalloc(&d_idx, (size_t)k * 4));
+    if (hipMalloc(&d_d, (size_t)k * 24) != hipSuccess) { hipFree(d_idx); return fail(c, KSCHED_E_DEVICE, "apply_delta: alloc"); }
+    hipError_t e = hipMemcpyAsync(d_idx, idx, (size_t)k * 4, hipMemcpyHostToDevice, c->stream);  // the kernel's stream
+    if (e == hipSuccess) e = hipMemcpyAsync(d_d, d.data(), (size_t)k * 24, hipMemcpyHostToDevice, c->stream);
+    c->explain_valid = false;
+    if (e == hipSuccess) e = launch_apply_delta(c->d->nodes, c->n_local, k, d_idx, d_d, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    hipFree(d_idx);
+    hipFree(d_d);
+    if (e != hipSuccess) return fail(c, KSCHED_E_DEVICE, std::string("apply_delta: ") + hipGetErrorString(e));
+    return KSCHED_OK;
+}
+
+int ksched_explain(ksched_ctx *c, int64_t rc, int64_t rm, int64_t rp, uint64_t sel, int64_t out_counts[KSCHED_NUM_REASONS],
+                   uint8_t *out_reason) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "explain before load_nodes");
+    if (!out_counts) return fail(c, KSCHED_E_INVALID, "explain: out_counts is NULL");
+    static_assert(KSCHED_NUM_REASONS == kNumReasons, "reason codes");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t n = c->n_local;
+    unsigned long long *d_cnt = nullptr;
+    HIPCHK(c, hipMalloc(&d_cnt, KSCHED_NUM_REASONS * sizeof(unsigned long long) + (size_t)(out_reason ? n : 0)));
+    uint8_t *d_reason = out_reason ? (uint8_t *)(d_cnt + KSCHED_NUM_REASONS) : nullptr;
+    unsigned long long h[KSCHED_NUM_REASONS] = {};
+    hipError_t e = hipMemsetAsync(d_cnt, 0, KSCHED_NUM_REASONS * sizeof(unsigned long long), c->stream);
+    if (e == hipSuccess)
+        e = launch_explain(c->d->nodes, n, rc, rm, rp, sel, c->o.use_labels != 0, d_reason, d_cnt, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_reason && n > 0) e = hipMemcpy(out_reason, d_reason, (size_t)n, hipMemcpyDeviceToHost);
+    hipFree(d_cnt);
+    if (e != hipSuccess) return fail(c, KSCHED_E_DEVICE, std::string("explain: ") + hipGetErrorString(e));
+    for (int k = 0; k < KSCHED_NUM_REASONS; ++k) out_counts[k] = (int64_t)h[k];
+    return KSCHED_OK;
+}
+
+static ExplainArgs explain_args(ksched_ctx *c) {
+    ExplainArgs a{};
+    a.idx = c->d->oidx; a.p = c->p;
+    a.rc = c->d->rc; a.rm = c->d->rm; a.rp = c->d->rp; a.sel = c->d->sel;
+    a.nodes = c->d->nodes; a.n_local = c->n_local; a.node_lo = c->o.node_offset;
+    a.use_labels = c->o.use_labels != 0;
+    return a;
+}
+
+int ksched_explain_batch(ksched_ctx *c, int64_t p, int64_t *out_counts, int64_t *out_nofit) {
+    if (!c) return KSCHED_E_INVALID;
+    if (!out_counts && p > 0) return fail(c, KSCHED_E_INVALID, "explain_batch: out_counts is NULL");
+    if (p != c->p) return fail(c, KSCHED_E_INVALID, "explain_batch: p differs from the last schedule call");
+    if (!c->explain_valid) return fail(c, KSCHED_E_STATE, "explain_batch: the node state changed since the last schedule call");
+    if (p >= 0x7fffffff) return fail(c, KSCHED_E_INVALID, "explain_batch: too many pods");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::memset(out_counts, 0, (size_t)p * KSCHED_NUM_REASONS * sizeof(int64_t));
+    if (out_nofit) *out_nofit = 0;
+    if (p == 0 || c->n_local == 0) return KSCHED_OK;
+    const size_t cnt_bytes = (size_t)p * kNumReasons * sizeof(unsigned long long);
+    HIPCHK(c, c->d->xbuf.reserve(std::max<size_t>(256, cnt_bytes + (size_t)p * sizeof(int32_t))));
+    unsigned long long *d_cnt = static_cast<unsigned long long *>(c->d->xbuf.p);
+    int32_t *d_fpod = reinterpret_cast<int32_t *>(static_cast<char *>(c->d->xbuf.p) + cnt_bytes);
+    HIPCHK(c, hipMemsetAsync(d_cnt, 0, cnt_bytes, c->stream));
+    ExplainArgs a = explain_args(c);
+    int64_t nf = 0;
+    a.fpod_out = d_fpod;
+    a.n_nofit = &nf;
+    HIPCHK(c, explain_batch(a, &c->d->xws.p, &c->d->xws.bytes, d_cnt, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (nf == 0) return KSCHED_OK;
+    std::vector<unsigned long long> h((size_t)nf * kNumReasons);
+    std::vector<int32_t> fp((size_t)nf);
+    HIPCHK(c, hipMemcpy(h.data(), d_cnt, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(fp.data(), d_fpod, fp.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t f = 0; f < nf; ++f)
+        for (int r = 0; r < kNumReasons; ++r)
+            out_counts[(size_t)fp[(size_t)f] * kNumReasons + r] = (int64_t)h[(size_t)f * kNumReasons + r];
+    if (out_nofit) *out_nofit = nf;
+    return KSCHED_OK;
+}
+
+int ksched_explain_pod(ksched_ctx *c, int64_t pod, int64_t out_counts[KSCHED_NUM_REASONS], uint8_t *out_reason) {
+    if (!c) return KSCHED_E_INVALID;
+    if (!out_counts) return fail(c, KSCHED_E_INVALID, "explain_pod: out_counts is NULL");
+    if (pod < 0 || pod >= c->p) return fail(c, KSCHED_E_INVALID, "explain_pod: pod out of range");
+    if (!c->explain_valid) return fail(c, KSCHED_E_STATE, "explain_pod: the node state changed since the last schedule call");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t n = c->n_local;
+    ExplainArgs a = explain_args(c);
+    HIPCHK(c, hipMemcpy(&a.q_rc, c->d->rc + pod, 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&a.q_rm, c->d->rm + pod, 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&a.q_rp, c->d->rp + pod, 8, hipMemcpyDeviceToHost));
+    if (c->o.use_labels) HIPCHK(c, hipMemcpy(&a.q_sel, c->d->sel + pod, 8, hipMemcpyDeviceToHost));
+    const size_t st_bytes = (size_t)3 * std::max<int64_t>(n, 1) * sizeof(int64_t);
+    HIPCHK(c, c->d->xbuf.reserve(std::max<size_t>(256, st_bytes + 64 + (size_t)std::max<int64_t>(n, 1))));
+    int64_t *d_state = static_cast<int64_t *>(c->d->xbuf.p);
+    unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(static_cast<char *>(c->d->xbuf.p) + st_bytes);
+    uint8_t *d_reason = reinterpret_cast<uint8_t *>(d_cnt + 8);
+    HIPCHK(c, hipMemsetAsync(d_cnt, 0, kNumReasons * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, explain_pod_at(a, pod, d_state, out_reason ? d_reason : nullptr, d_cnt, c->stream));
+    unsigned long long h[kNumReasons] = {};
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost));
+    if (out_reason && n > 0) HIPCHK(c, hipMemcpy(out_reason, d_reason, (size_t)n, hipMemcpyDeviceToHost));
+    for (int r = 0; r < kNumReasons; ++r) out_counts[r] = (int64_t)h[r];
+    return KSCHED_OK;
+}
+
+int ksched_read_nodes(ksched_ctx *c, int64_t n, int64_t *ac, int64_t *am, int64_t *ap) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "read_nodes before load_nodes");
+    if (n != c->n_local) return fail(c, KSCHED_E_INVALID, "read_nodes: size mismatch");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<NodeRec> h((size_t)n);
+    if (n > 0) HIPCHK(c, hipMemcpy(h.data(), c->d->nodes, (size_t)n * sizeof(NodeRec), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) {
+        if (ac) ac[i] = h[(size_t)i].a[0];
+        if (am) am[i] = h[(size_t)i].a[1];
+        if (ap) ap[i] = h[(size_t)i].a[2];
+    }
+    return KSCHED_OK;
+}
+
+int ksched_save_state(ksched_ctx *c) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "save_state before load_nodes");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, c->d->snap.reserve((size_t)c->n_local * sizeof(NodeRec)));  // (released by every load_nodes)
+    if (c->n_local > 0)
+        HIPCHK(c, hipMemcpyAsync(c->d->snap, c->d->nodes, (size_t)c->n_local * sizeof(NodeRec), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->snap_max_abs_alloc = c->max_abs_alloc;
+    return KSCHED_OK;
+}
+
+int ksched_restore_state(ksched_ctx *c) {
+    if (!c) return KSCHED_E_INVALID;
+    if (!c->d->snap) return fail(c, KSCHED_E_STATE, "restore_state without save_state");
+    HIPCHK(c, hipSetDevice(c->dev));
+    if (c->n_local > 0)
+        HIPCHK(c, hipMemcpyAsync(c->d->nodes, c->d->snap, (size_t)c->n_local * sizeof(NodeRec), hipMemcpyDeviceToDevice, c->stream));
+    c->max_abs_alloc = c->snap_max_abs_alloc;
+    c->explain_valid = false;
+    return KSCHED_OK;
+}
+
+int ksched_upload_pods(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                       const uint64_t *sel) {
+    if (!c) return KSCHED_E_INVALID;
+    if (p < 0 || (p > 0 && (!rc || !rm || !rp))) return fail(c, KSCHED_E_INVALID, "upload_pods: bad arguments");
+    if (c->o.use_labels && p > 0 && !sel) return fail(c, KSCHED_E_INVALID, "upload_pods: use_labels needs selectors");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t q = (size_t)p;
+    HIPCHK(c, c->d->rc.reserve(q * 8)); HIPCHK(c, c->d->rm.reserve(q * 8));
+    HIPCHK(c, c->d->rp.reserve(q * 8)); HIPCHK(c, c->d->sel.reserve(q * 8));
+    HIPCHK(c, c->d->oidx.reserve(q * 4)); HIPCHK(c, c->d->osc.reserve(q * 8));
+    HIPCHK(c, c->d->ofeas.reserve(q * 4));
+    if (p > 0) {
+        // in the stream of the kernels that read them, finished before the caller's buffers may change (see
+        // ksched_load_nodes)
+        HIPCHK(c, hipMemcpyAsync(c->d->rc, rc, (size_t)p * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d->rm, rm, (size_t)p * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d->rp, rp, (size_t)p * 8, hipMemcpyHostToDevice, c->stream));
+        if (sel) HIPCHK(c, hipMemcpyAsync(c->d->sel, sel, (size_t)p * 8, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(c, hipMemsetAsync(c->d->sel, 0, (size_t)p * 8, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    uint64_t sum = 0;
+    for (int64_t i = 0; i < p; ++i) sum = sat_add(sum, sat_add(uabs(rc[i]), sat_add(uabs(rm[i]), uabs(rp[i]) + 1)));
+    c->sum_abs_req = sum;
+    c->p = p;
+    c->explain_valid = false;
+    return KSCHED_OK;
+}
+
+int ksched_selftest_fastdiv(ksched_ctx *c, int64_t n, const double *a, const double *b, double *out_native,
+                            double *out_fast) {
+    if (!c || n < 0 || (n > 0 && (!a || !b || !out_native || !out_fast))) return KSCHED_E_INVALID;
+    if (n == 0) return KSCHED_OK;
+    HIPCHK(c, hipSetDevice(c->dev));
+    double *d = nullptr;
+    HIPCHK(c, hipMalloc(&d, (size_t)n * 32));
+    hipError_t e = hipMemcpyAsync(d, a, (size_t)n * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + n, b, (size_t)n * 8, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_selftest_div(n, d, d + n, d + 2 * n, d + 3 * n, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(out_native, d + 2 * n, (size_t)n * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_fast, d + 3 * n, (size_t)n * 8, hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (e != hipSuccess) return fail(c, KSCHED_E_DEVICE, std::string("selftest_fastdiv: ") + hipGetErrorString(e));
+    return KSCHED_OK;
+}
+
+int ksched_download_results(ksched_ctx *c, int64_t p, int32_t *oi, double *os, int32_t *of) {
+    if (!c) return KSCHED_E_INVALID;
+    if (p != c->p) return fail(c, KSCHED_E_INVALID, "download_results: size mismatch");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (p == 0) return KSCHED_OK;
+    if (oi) HIPCHK(c, hipMemcpy(oi, c->d->oidx, (size_t)p * 4, hipMemcpyDeviceToHost));
+    if (os) HIPCHK(c, hipMemcpy(os, c->d->osc, (size_t)p * 8, hipMemcpyDeviceToHost));
+    if (of) HIPCHK(c, hipMemcpy(of, c->d->ofeas, (size_t)p * 4, hipMemcpyDeviceToHost));
+    if (oi && c->st.placed == 0) {
+        int64_t placed = 0;
+        for (int64_t i = 0; i < p; ++i) placed += oi[i] >= 0;
+        c->st.placed = placed;
+    }
+    return KSCHED_OK;
+}
+
+}  // extern "C"

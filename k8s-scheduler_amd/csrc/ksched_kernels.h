@@ -4,7 +4,7 @@
 //                              arg-best per pod through tagged 8-byte granules (no host round trip).
 // Batched mode: k_score_topk   pod-per-lane fused predicate + score + per-lane top-K over a node
 //                              chunk (node rows are wave-uniform -> scalar loads);
-//               k_merge        sorted-list merge, one wave per (pod, <=64 lists), DPP/shuffle arg-best;
+//               k_merge        sorted-list merge of the ranks' lists, one wave per pod, DPP/shuffle arg-best;
 //               k_commit       one wave replays the batch in pod order: re-scores the nodes already
 //                              committed in the batch, takes the first untouched candidate, commits,
 //                              stops at the first candidate-list overflow.
@@ -192,7 +192,7 @@ struct ExactArgs {
     PodArgs pods;
     OutArgs out;
     uint64_t *slots;  // [2][G][4] granules {epoch:32 | value:32}; zeroed before every launch
-    int32_t *err;     // device error word (1 = exchange timeout)
+    int32_t *err;     // device error word (kErrExactExchange)
     int64_t timeout_ticks;
     const int32_t *perm;  // k_exact1: slot -> node (best-price: nodes by price asc, index asc); null: slot = node
 };
@@ -212,14 +212,14 @@ struct ScoreArgs {
     // device-side wait for commit(b-2): poll *wait_committed >= wait_target (null: the stream waits)
     const unsigned long long *wait_committed;
     unsigned long long wait_target;
-    int32_t *err;                    // device error word (4 = the wait timed out)
+    int32_t *err;                    // device error word (kErrStreamScoreWait)
 };
 
 struct MergeArgs {
-    const void *in;         // Cand [B][C_in][K]  or, INPUT_REC, C_in rank blocks of rank_stride bytes,
+    const void *in;         // Cand [B][C_in][K]  or, for the rank merge, C_in rank blocks of rank_stride bytes,
                             // each {Rec [B][K]; int64 fc[B]} (the RCCL all-gather layout)
     const int64_t *in_cnt;  // [B][C_in] (Cand input only)
-    int64_t rank_stride;    // bytes per rank block (INPUT_REC)
+    int64_t rank_stride;    // bytes per rank block (rank merge)
     int32_t C_in;
     int32_t C_out;          // ceil(C_in / 64)
     int32_t chunk_input;    // 1: inputs are score-kernel chunk lists (cut when full)
@@ -228,7 +228,7 @@ struct MergeArgs {
     int64_t *out_cnt;       // [B][C_out]
     Rec *out_rec;           // [B][K]  (final)
     int64_t *out_fc;        // [B]
-    const NodeRec *nodes;   // final + !INPUT_REC: gather node snapshot state
+    const NodeRec *nodes;   // Cand input: gather node snapshot state
     int64_t node_offset;
     const int64_t *cursor;
     int64_t P;
@@ -288,7 +288,7 @@ struct CommitArgs {
     int32_t touch_screen;   // persistent commit: the touched-node screen on (KSCHED_NO_TOUCH_SCREEN=1 turns it off)
     const char *inh;        // persistent commit: the mergers' keys of the older export (inherit_x2_keys), else null
     int64_t timeout_ticks;  // bound of the rescue wait
-    int32_t *err;           // device error word (12 = the rescue wait timed out)
+    int32_t *err;           // device error word (kErrWaitRescue)
     uint64_t *trace_row;    // KSCHED_PERSIST_TRACE: this batch's trace row (else null)
     const PersistArgs *xp;  // persistent pipeline: its arguments (R > 1: the rescue's rank fold through the rings)
     int64_t dbg_act;        // diagnostics (KSCHED_XCHG_DUMP): this batch's active-batch index
@@ -418,7 +418,8 @@ hipError_t launch_score_topk(int KC, int prio, int dom, bool lab, bool fast53, c
                              hipStream_t s);
 // one workgroup per pod: the score kernel's workgroup lists -> the pod's K-entry Rec list (C_in <= 256)
 hipError_t launch_merge_pod(int KC, int K, const MergeArgs &a, hipStream_t s);
-hipError_t launch_merge(int KIN, int K, bool input_rec, bool final_stage, const MergeArgs &a, hipStream_t s);
+// one wave per pod: the ranks' K-entry Rec lists (the all-gather layout) -> the pod's global K-entry Rec list
+hipError_t launch_rank_merge(int K, const MergeArgs &a, hipStream_t s);
 hipError_t launch_commit(int K, int prio, int dom, bool lab, bool fast53, const CommitArgs &a, size_t lds_bytes,
                          hipStream_t s);
 constexpr int kSpcThreads = 512;  // speculative commit: wave 0 guesses and checks, 8 waves evaluate
@@ -456,7 +457,7 @@ struct PersistArgs {
     char *xring;            // 4 XBufs + the permanently empty one (slot 4)
     int64_t xbuf_bytes;
     OutArgs out;
-    int32_t *err;           // device error word (5..9 = a persistent wait timed out)
+    int32_t *err;           // device error word (kErrWait* .. kErrLdsCanary)
     int64_t timeout_ticks;
     int32_t no_screen;      // diagnostics (KSCHED_NO_SCREEN): the exact scan in every batch
     int32_t no_pairs;       // diagnostics (KSCHED_NO_PAIRS): the screened scan's exact phase by rows, never by pairs
@@ -509,6 +510,13 @@ constexpr int kProgWords = 6;  // 0 phase, 1 where/seen, 2 heartbeat, 3 busy, 4 
 enum : int { kProgWaitCommit = 1, kProgScan = 2, kProgArrived = 3, kProgWaitArrive = 4, kProgMerged = 5,
              kProgWaitMerged = 6, kProgCommitted = 7, kProgIdle = 8, kProgRescue = 9, kProgWaitRescue = 10,
              kProgTimedOut = 0x80 };
+// the device error word (ExactArgs / ScoreArgs / MergeArgs / CommitArgs / PersistArgs ::err): a call's first error,
+// decoded by the host at sync (decode_device_error, ksched_diag.hip, has each code's meaning)
+enum : int32_t { kErrExactExchange = 1, kErrStreamMergeWait = 2, kErrStreamScoreWait = 4,
+                 // the persistent pipeline's waits
+                 kErrWaitMerged = 5, kErrWaitCommit = 6, kErrWaitArrive = 7, kErrScorePlan = 8, kErrCommitPlan = 9,
+                 kErrWaitPeerLists = 10, kErrRankBarrier = 11, kErrWaitRescue = 12,
+                 kErrBadIndex = 14, kErrLdsCanary = 15 };
 __device__ __forceinline__ uint32_t hw_where() {
     uint32_t xcc, hw;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));

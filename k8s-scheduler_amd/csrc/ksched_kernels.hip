@@ -153,7 +153,7 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                     }
                     if (__all(ok)) break;
                     if (wall_clock64() - t0 > A.timeout_ticks) {
-                        if (lane == 0) { atomicExch(A.err, 1); s_abort = 1; }
+                        if (lane == 0) { atomicExch(A.err, kErrExactExchange); s_abort = 1; }
                         break;
                     }
                     __builtin_amdgcn_s_sleep(1);
@@ -373,7 +373,7 @@ __device__ __forceinline__ void score_topk_body(const ScoreArgs &A) {
             while (__hip_atomic_load(A.wait_committed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < A.wait_target) {
                 __builtin_amdgcn_s_sleep(1);
                 if (wall_clock64() - t0 > 200000000ull) {  // 2 s: report instead of spinning forever
-                    __hip_atomic_store(A.err, 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(A.err, kErrStreamScoreWait, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     s_late = 1;
                     break;
                 }
@@ -524,19 +524,18 @@ __global__ __launch_bounds__(kScoreThreads, 8) void k_score_topk(ScoreArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Merge: one wave per (pod, group of <= 64 sorted lists of KIN entries).  Each lane stages one list in
-// LDS; K rounds of wave arg-best over the lanes' heads (the winning lane advances).  Final stage writes
-// Rec entries carrying the node snapshot state; INPUT_REC merges the ranks' Rec lists.
+// Rank merge: one wave per pod over the ranks' sorted Rec lists of K entries.  Each lane stages one rank's list in
+// LDS; K rounds of wave arg-best over the lanes' heads (the winning lane advances); the winners' Rec rows are copied.
 // Exact prefix ("cut") rule: a cut input list has unlisted candidates, all ranking below its last
 // entry.  The output keeps only entries ranking at or above the best such cutoff (anything below it
 // could be preceded by an unlisted candidate) and is itself cut when any input was, or when entries
-// were left over after K rounds.  The flag travels in entry 0's pad (Cand) / pad (Rec).
+// were left over after K rounds.  The flag travels in entry 0's pad.
 // ------------------------------------------------------------------------------------------------
-template <int KIN, int K, bool INPUT_REC, bool FINAL>
+template <int K>
 __global__ __launch_bounds__(64) void k_merge(MergeArgs A) {
     __builtin_amdgcn_s_setprio(3);  // latency-critical: win issue arbitration over co-resident score waves
-    __shared__ double s_key[64 * KIN];
-    __shared__ int32_t s_idx[64 * KIN];
+    __shared__ double s_key[64 * K];
+    __shared__ int32_t s_idx[64 * K];
     const int lane = threadIdx.x;
     const int grp = blockIdx.x;
     const int b = blockIdx.y;
@@ -548,35 +547,22 @@ __global__ __launch_bounds__(64) void k_merge(MergeArgs A) {
     int n = 0;          // valid entries of this lane's list
     bool cut = false;   // this lane's list is cut
     if (has) {
-        if (INPUT_REC) {
-            const char *blk = static_cast<const char *>(A.in) + (size_t)list * A.rank_stride;
-            const Rec *src = reinterpret_cast<const Rec *>(blk) + (size_t)b * KIN;
+        const char *blk = static_cast<const char *>(A.in) + (size_t)list * A.rank_stride;
+        const Rec *src = reinterpret_cast<const Rec *>(blk) + (size_t)b * K;
 #pragma unroll
-            for (int q = 0; q < KIN; ++q) {
-                const bool v = src[q].valid != 0;
-                s_key[lane * KIN + q] = v ? src[q].key : -__builtin_inf();
-                s_idx[lane * KIN + q] = v ? src[q].idx : kNoIdx;
-                n += v;
-            }
-            cut = src[0].pad != 0;
-            cnt = reinterpret_cast<const int64_t *>(blk + (size_t)A.B * KIN * sizeof(Rec))[b];
-        } else {
-            const Cand *src = static_cast<const Cand *>(A.in) + ((size_t)b * A.C_in + list) * KIN;
-#pragma unroll
-            for (int q = 0; q < KIN; ++q) {
-                s_key[lane * KIN + q] = src[q].key;
-                s_idx[lane * KIN + q] = src[q].idx;
-                n += src[q].idx != kNoIdx;
-            }
-            // chunk lists (first stage): cut when full; merged lists carry the flag
-            cut = A.chunk_input ? (n == KIN) : (src[0].pad != 0);
-            cnt = A.in_cnt[(size_t)b * A.C_in + list];
+        for (int q = 0; q < K; ++q) {
+            const bool v = src[q].valid != 0;
+            s_key[lane * K + q] = v ? src[q].key : -__builtin_inf();
+            s_idx[lane * K + q] = v ? src[q].idx : kNoIdx;
+            n += v;
         }
+        cut = src[0].pad != 0;
+        cnt = reinterpret_cast<const int64_t *>(blk + (size_t)A.B * K * sizeof(Rec))[b];
     }
     cnt = wave_sum_i64(cnt);
     // best cutoff over the cut lists (their last valid entry)
-    double ck = (cut && n > 0) ? s_key[lane * KIN + n - 1] : -__builtin_inf();
-    int32_t ci = (cut && n > 0) ? s_idx[lane * KIN + n - 1] : kNoIdx;
+    double ck = (cut && n > 0) ? s_key[lane * K + n - 1] : -__builtin_inf();
+    int32_t ci = (cut && n > 0) ? s_idx[lane * K + n - 1] : kNoIdx;
     const bool anycut = __ballot(cut) != 0;
     {
         int32_t aux = 0;
@@ -587,46 +573,31 @@ __global__ __launch_bounds__(64) void k_merge(MergeArgs A) {
     double mk = -__builtin_inf();
     int32_t mi = kNoIdx, msrc = -1;
     for (int r = 0; r < K; ++r) {
-        double k = (h < n) ? s_key[lane * KIN + h] : -__builtin_inf();
-        int32_t ix = (h < n) ? s_idx[lane * KIN + h] : kNoIdx;
-        int32_t src = lane * KIN + h;
+        double k = (h < n) ? s_key[lane * K + h] : -__builtin_inf();
+        int32_t ix = (h < n) ? s_idx[lane * K + h] : kNoIdx;
+        int32_t src = lane * K + h;
         wave_argbest(k, ix, src);
         if (ix == kNoIdx) break;  // wave-uniform
-        if (src == lane * KIN + h) ++h;
+        if (src == lane * K + h) ++h;
         if (lane == r) { mk = k; mi = ix; msrc = src; }
     }
     const bool left = __ballot(h < n) != 0;  // candidates beyond the K output entries
     // entries ranking below the best cutoff are not exact
     if (anycut && mi != kNoIdx && better(ck, ci, mk, mi)) { mk = -__builtin_inf(); mi = kNoIdx; }
     const int32_t cut_out = (anycut || left) ? 1 : 0;
-    if (!FINAL) {
-        if (lane < K) {
-            Cand *dst = A.out + ((size_t)b * A.C_out + grp) * K + lane;
-            dst->key = mk; dst->idx = mi; dst->pad = lane == 0 ? cut_out : 0;
+    if (lane < K) {
+        Rec r{};
+        if (mi != kNoIdx) {
+            const int srcl = msrc / K, srcq = msrc % K;
+            const char *blk = static_cast<const char *>(A.in) + (size_t)(grp * 64 + srcl) * A.rank_stride;
+            r = reinterpret_cast<const Rec *>(blk)[(size_t)b * K + srcq];
+        } else {
+            r.key = -__builtin_inf(); r.idx = kNoIdx; r.valid = 0;
         }
-        if (lane == 0) A.out_cnt[(size_t)b * A.C_out + grp] = cnt;
-    } else {
-        if (lane < K) {
-            Rec r{};
-            if (mi != kNoIdx) {
-                if (INPUT_REC) {
-                    const int srcl = msrc / KIN, srcq = msrc % KIN;
-                    const char *blk = static_cast<const char *>(A.in) + (size_t)(grp * 64 + srcl) * A.rank_stride;
-                    r = reinterpret_cast<const Rec *>(blk)[(size_t)b * KIN + srcq];
-                } else {
-                    const NodeRec &nd = A.nodes[mi - A.node_offset];
-                    r.key = mk; r.idx = mi; r.valid = 1;
-                    r.a[0] = nd.a[0]; r.a[1] = nd.a[1]; r.a[2] = nd.a[2];
-                    r.labels = nd.labels; r.price = nd.price;
-                }
-            } else {
-                r.key = -__builtin_inf(); r.idx = kNoIdx; r.valid = 0;
-            }
-            r.pad = lane == 0 ? cut_out : 0;
-            A.out_rec[(size_t)b * K + lane] = r;
-        }
-        if (lane == 0) A.out_fc[b] = cnt;
+        r.pad = lane == 0 ? cut_out : 0;
+        A.out_rec[(size_t)b * K + lane] = r;
     }
+    if (lane == 0) A.out_fc[b] = cnt;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1141,30 +1112,10 @@ hipError_t score_k(int KC, const ScoreArgs &a, int pg, hipStream_t s) {
     }
 }
 
-template <int KIN, int K>
-hipError_t merge_kk(bool rec, bool fin, const MergeArgs &a, hipStream_t s) {
-    dim3 grid(a.C_out, a.B);
-    if (rec) {
-        if (!fin) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_merge<KIN, K, true, true>), grid, dim3(64), 0, s, a);
-    } else if (fin) {
-        hipLaunchKernelGGL((k_merge<KIN, K, false, true>), grid, dim3(64), 0, s, a);
-    } else {
-        hipLaunchKernelGGL((k_merge<KIN, K, false, false>), grid, dim3(64), 0, s, a);
-    }
-    return hipGetLastError();
-}
-
 template <int K>
-hipError_t merge_k(int KIN, bool rec, bool fin, const MergeArgs &a, hipStream_t s) {
-    if (KIN == K) return merge_kk<K, K>(rec, fin, a, s);
-    if (rec) return hipErrorInvalidValue;  // rank lists always hold K entries
-    switch (KIN) {
-        case 2: return merge_kk<2, K>(false, fin, a, s);
-        case 4: return K > 4 ? merge_kk<(K > 4 ? 4 : K), K>(false, fin, a, s) : hipErrorInvalidValue;
-        case 8: return K > 8 ? merge_kk<(K > 8 ? 8 : K), K>(false, fin, a, s) : hipErrorInvalidValue;
-        default: return hipErrorInvalidValue;
-    }
+hipError_t rank_merge_k(const MergeArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL((k_merge<K>), dim3(a.C_out, a.B), dim3(64), 0, s, a);
+    return hipGetLastError();
 }
 
 template <int K, int PRIO, int DOM, bool LAB, bool F53>
@@ -1264,11 +1215,11 @@ hipError_t launch_score_topk(int KC, int prio, int dom, bool lab, bool f53, cons
     KSCHED_DISPATCH(prio, dom, lab, f53, (score_k<P_, D_, L_, F_>(KC, a, pod_groups, s)));
 }
 
-hipError_t launch_merge(int KIN, int K, bool input_rec, bool final_stage, const MergeArgs &a, hipStream_t s) {
+hipError_t launch_rank_merge(int K, const MergeArgs &a, hipStream_t s) {
     switch (K) {
-        case 4: return merge_k<4>(KIN, input_rec, final_stage, a, s);
-        case 8: return merge_k<8>(KIN, input_rec, final_stage, a, s);
-        case 16: return merge_k<16>(KIN, input_rec, final_stage, a, s);
+        case 4: return rank_merge_k<4>(a, s);
+        case 8: return rank_merge_k<8>(a, s);
+        case 16: return rank_merge_k<16>(a, s);
         default: return hipErrorInvalidValue;
     }
 }

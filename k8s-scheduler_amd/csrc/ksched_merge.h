@@ -395,7 +395,7 @@ __device__ __forceinline__ void merge_pod_fast(const MergeArgs &A, const int b, 
             };
             for (int it = 0; stale(); ++it) {
                 if (it == (1 << 22)) {  // (never seen: a lost store) -- report, do not hang
-                    if (A.err) atomicCAS(A.err, 0, 11);
+                    if (A.err) atomicCAS(A.err, 0, kErrRankBarrier);
                     break;
                 }
                 __builtin_amdgcn_s_sleep(1);

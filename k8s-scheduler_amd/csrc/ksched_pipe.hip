@@ -126,8 +126,8 @@ __device__ __forceinline__ bool granule_wait(const uint64_t *p, uint32_t tag, in
     return true;
 }
 
-// Rank merge of pod m's R exchanged lists (one wave, lane = source rank; the stream pipeline's
-// k_merge<INPUT_REC> rule): K rounds of wave arg-best over the lists' heads, entries ranking below the
+// Rank merge of pod m's R exchanged lists (one wave, lane = source rank; the rule of the stream pipeline's
+// rank merge, k_merge): K rounds of wave arg-best over the lists' heads, entries ranking below the
 // best cutoff of a cut list dropped, cut when any input was cut or entries were left over.
 template <int K>
 __device__ __forceinline__ void rank_merge_msgs(const uint32_t *all, int R, Rec *out, int64_t *out_fc) {
@@ -487,7 +487,7 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                     if (b >= kPipeLag && early_c < need) {
                         prog_at(P, g, b, kProgWaitCommit, 0);
                         if (!spin_ge(P, g, &ctl->committed_x[g % kCtlReplicas].v, need, &seen)) {
-                            set_err(P.err, 6);
+                            set_err(P.err, kErrWaitCommit);
                             prog_at(P, g, b, kProgWaitCommit | kProgTimedOut, seen);
                             stop = 2;
                         }
@@ -517,7 +517,7 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
             if (tid == 0) prog_at(P, g, b, kProgIdle, (uint64_t)p0);
             // a truncation re-plans within kPipeLag batches; a longer run of empty plans is a protocol error
             if (++idle > kPlanRing) {
-                if (tid == 0) set_err(P.err, 8);
+                if (tid == 0) set_err(P.err, kErrScorePlan);
                 return;
             }
             sync();  // every wave has read s_done before wave 0 rewrites it
@@ -1246,7 +1246,7 @@ __device__ __forceinline__ void merge_role(const PersistArgs &P, char *sbase, co
         }
     };
     for (int64_t b = 0;; ++b) {
-        if (b >= kPipeLag && !mwait(b, &ctl->committed_x[g % kCtlReplicas].v, (unsigned long long)(b - kPipeLag + 1), 6,
+        if (b >= kPipeLag && !mwait(b, &ctl->committed_x[g % kCtlReplicas].v, (unsigned long long)(b - kPipeLag + 1), kErrWaitCommit,
                                     kProgWaitCommit))
             return;
         if (mtid == 0) {
@@ -1261,7 +1261,7 @@ __device__ __forceinline__ void merge_role(const PersistArgs &P, char *sbase, co
         if (p0 < 0 || p0 >= NP) {
             if (mtid == 0) prog_at(P, slot_prog, b, kProgIdle, (uint64_t)p0);
             if (++idle > kPlanRing) {
-                if (mtid == 0) set_err(P.err, 8);
+                if (mtid == 0) set_err(P.err, kErrScorePlan);
                 return;
             }
             sync();  // m_p0 / m_done are rewritten next iteration
@@ -1274,12 +1274,12 @@ __device__ __forceinline__ void merge_role(const PersistArgs &P, char *sbase, co
         // the pods' keys against the older inherited export, while the score workgroups still scan the batch: off
         // the merge -> commit path (after the merge instead, c4 measured 10 % slower: the merges then end later)
         if (P.inh && b >= 2) {
-            if (!mwait(b, &ctl->committed_x[g % kCtlReplicas].v, (unsigned long long)(b - 1), 6, kProgWaitCommit)) return;
+            if (!mwait(b, &ctl->committed_x[g % kCtlReplicas].v, (unsigned long long)(b - 1), kErrWaitCommit, kProgWaitCommit)) return;
             jitter_at(P.jitter, b, 3);
             for (int m = g; m < P.B; m += kMS * P.M)
                 if (p0 + m < NP) inherit_x2_keys<PRIO, DOM, LAB, F53>(P, b, m, p0 + m, mtid);
         }
-        if (!mwait(b, &ctl->arrive[slot].v, (use + 1) * (unsigned long long)G, 7, kProgWaitArrive)) return;
+        if (!mwait(b, &ctl->arrive[slot].v, (use + 1) * (unsigned long long)G, kErrWaitArrive, kProgWaitArrive)) return;
         if (mtid == 0 && g == 0) trace_at(P, b, 7);
         const size_t part_elems = (size_t)P.B * G;
         char *lb = P.lring + (size_t)(b % 4) * P.lists_bytes;
@@ -1335,7 +1335,7 @@ __device__ __forceinline__ void merge_role(const PersistArgs &P, char *sbase, co
                     if (ok && !granule_wait(src + w, tag, P.timeout_ticks, &word)) ok = false;
                     s_all[e] = word;
                 }
-                if (!ok) { set_err(P.err, 10); pc->m_stop = 1; }
+                if (!ok) { set_err(P.err, kErrWaitPeerLists); pc->m_stop = 1; }
                 sync();
                 if (pc->m_stop) return;
 #if KSCHED_XCHG_DEBUG  // diagnostics build (tests/diag/xchg_ring_experiment.py): message hashes and the first messages
@@ -1433,7 +1433,7 @@ __device__ __forceinline__ void commit_role(const PersistArgs &P, char *smem, co
         if (!act && ++idle > kPlanRing) {
             // pods remain but nothing is planned: a truncation re-plans within kPipeLag batches, so this is a
             // protocol error -- stop everyone instead of spinning
-            if (threadIdx.x == 0) atomicCAS(P.err, 0, 9);
+            if (threadIdx.x == 0) atomicCAS(P.err, 0, kErrCommitPlan);
             if (threadIdx.x < 64) publish_committed_all(ctl, 1ull << 62);
             return;
         }
@@ -1565,14 +1565,14 @@ __device__ __forceinline__ void commit_role(const PersistArgs &P, char *smem, co
         const int rc = commit_spc_batch<K, PRIO, DOM, LAB, F53, true, kPipeThreads>(ca, cs, &pre, wait_merged, handoff);
         if (rc == 2) return;  // the call ended (or failed) elsewhere
         if (rc == 0) {
-            if (threadIdx.x == 0) atomicCAS(P.err, 0, 5);
+            if (threadIdx.x == 0) atomicCAS(P.err, 0, kErrWaitMerged);
             if (threadIdx.x < 64) publish_committed_all(ctl, 1ull << 62);
             return;
         }
         __syncthreads();
         if (threadIdx.x < kCanaryBytes / 4 && canary[threadIdx.x] != (0xA5A5A5A5u ^ threadIdx.x)) {
             // an LDS write below the commit's arrays: report which word, once
-            if (atomicCAS(P.err, 0, 15) == 0 && P.prog)
+            if (atomicCAS(P.err, 0, kErrLdsCanary) == 0 && P.prog)
                 P.prog[kProgWords * cslot + 2] = (uint64_t)b << 32 | (uint64_t)threadIdx.x << 16 | (canary[threadIdx.x] & 0xffffu);
         }
         if (threadIdx.x == 0) {
@@ -1721,7 +1721,7 @@ __global__ __launch_bounds__(64) void k_xchg_min(PersistArgs P, int32_t mine, in
     v = wave_min_i32(v);
     const bool bad = __ballot(!ok) != 0;
     if (lane == 0) {
-        if (bad) set_err(P.err, 11);
+        if (bad) set_err(P.err, kErrRankBarrier);
         *out = bad ? -1 : v;
     }
 }

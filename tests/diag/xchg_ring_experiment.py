@@ -8,7 +8,9 @@ group checked against the oracle.  Variants change one thing at a time: the ring
   python tests/diag/xchg_ring_experiment.py [variant ...]     (one subprocess per variant; default: all)
 
 The *_dump variants need the diagnostics build (the device-side dumps are compiled out of the product):
-  bash tools/build_variant.sh xdbg "-DKSCHED_XCHG_DEBUG=1"     -> k8s-scheduler_amd/libksched_xdbg.so
+  make -C k8s-scheduler_amd clean
+  make -C k8s-scheduler_amd HIPCC="/opt/rocm/bin/hipcc -DKSCHED_XCHG_DEBUG=1"
+  mv k8s-scheduler_amd/libksched.so k8s-scheduler_amd/libksched_xdbg.so      (then clean and rebuild the product)
 """
 import json
 import os

@@ -3,7 +3,7 @@
 Each rank owns a contiguous node shard and computes local top-K candidate records for every pod of a
 batch (the CPU restatement of k_score_topk + k_merge), the records are exchanged with a real
 all-gather (the engine uses RCCL ncclAllGather for the same bytes), merged identically on every rank
-(k_merge<INPUT_REC>), and every rank replays the same ordered commit (k_commit), writing back only
+(the rank merge, k_merge), and every rank replays the same ordered commit (k_commit), writing back only
 the nodes it owns.  The result must equal the unsharded sequential semantics bit for bit, and all
 ranks must agree.  Also covers the 128-byte unique-id broadcast used to set up RCCL.
 """

@@ -4,7 +4,7 @@ rank at offset 0).
 RCCL admits one rank per device, so R ranks run as R contexts of this process on GPU 0, one thread
 each, joined by an in-process rank group (ksched_group): the per-batch all-gather of the local
 candidate lists goes through a shared device ring instead of ncclAllGather, and everything around it
-is the RCCL path's code -- global indices at node_offset > 0, the rank merge k_merge<INPUT_REC> over R
+is the RCCL path's code -- global indices at node_offset > 0, the rank merge k_merge over R
 rank blocks with their cut flags, the identical commit replay on every rank and the owner-only
 write-back of committed rows.  Every rank's outputs must equal the sequential oracle's, and the shards'
 final states concatenated must equal the oracle's final state.

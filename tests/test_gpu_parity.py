@@ -291,7 +291,7 @@ def test_hoisted_reciprocal_division_is_bit_exact(gpu_available):
 def test_collective_path_one_rank(gpu_available, oracle_mod):
     """The node-sharded path (RCCL all-gather of the local candidate records + rank merge) on a 1-rank
     communicator: same bits as the oracle.  Exercises ksched_get_unique_id / ksched_set_comm,
-    ncclAllGather inside the engine and k_merge<INPUT_REC>."""
+    ncclAllGather inside the engine and the rank merge (k_merge)."""
     from ksched import Engine, MODE_BATCHED, cluster
     for name, nn, pp, K in (("c3", 20000, 1500, 16), ("c5", 30000, 1500, 8), ("c2", 5000, 1500, 4)):
         cl = cluster.make_cluster(name, n_nodes=nn, n_pods=pp)
@@ -375,3 +375,26 @@ def test_rescue_policies_same_results(gpu_available, oracle_mod, monkeypatch, po
         assert st["rescues"] == 0 and st["truncations"] > 0, st
     else:
         assert st["rescues"] > 0, st
+
+
+@pytest.mark.parametrize("failed_load", [False, True], ids=["reload", "reload_after_failed_load"])
+def test_best_price_reload_smaller_cluster(gpu_available, oracle_mod, failed_load):
+    """Exact mode, best price, one rank, ONE engine: 300 priced nodes and 8 pods, then 200 nodes in another price
+    order and 8 pods -- the one-workgroup exact kernel's price permutation must be the loaded nodes' (the engine
+    records the node count it was built for).  The Engine fixes nodes_global at construction, so a load of 200
+    nodes cannot be made to fail through it; the failing load in between is one of 400 nodes against
+    nodes_global = 300, which returns E_INVALID after the node rows were replaced.  Every result equals the oracle's."""
+    from ksched import Engine, MODE_EXACT, cluster
+    from ksched._lib import E_INVALID, KschedError, PRIORITY_BEST_PRICE
+    a, b, big = (cluster.random_small(seed, n_nodes=nn, n_pods=8, priority=PRIORITY_BEST_PRICE, domain=1, edge=False)
+                 for seed, nn in ((71, 300), (72, 200), (73, 400)))
+    assert not np.array_equal(np.argsort(a.price[:200], kind="stable"), np.argsort(b.price, kind="stable"))
+    with Engine(mode=MODE_EXACT, priority=PRIORITY_BEST_PRICE, domain=1, nranks=1, nodes_global=300) as e:
+        for cl in (a, b):
+            if failed_load and cl is b:
+                with pytest.raises(KschedError) as ex:
+                    e.load_nodes(big.alloc_cpu, big.alloc_mem, big.alloc_pods, price=big.price)
+                assert ex.value.code == E_INVALID
+            e.load_nodes(cl.alloc_cpu, cl.alloc_mem, cl.alloc_pods, price=cl.price)
+            oi, os_, of = e.schedule(cl.req_cpu, cl.req_mem, cl.req_pods, cl.selector)
+            assert_same((oi, os_, of, e.read_nodes()), oracle_mod.schedule(cl), f"{cl.n_nodes} nodes")

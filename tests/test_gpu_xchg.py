@@ -189,7 +189,7 @@ def test_xchg_tags_wrap_across_calls(gpu_available, oracle_mod, monkeypatch):
     """Granule tags keep 15 bits (ksched_kernels.h gran_tag).  Tags started just below 2^15 (KSCHED_XCHG_EPOCH_BASE)
     cross the wrap during these calls, and calls with rescues alternate with short calls that write only some
     message slots and no rescue area: every call zeroes its ring's message and rescue areas before the rank barrier
-    (ksched_engine.hip rx_zero_regions), so no wait can take an earlier call's granule.  Bit-exact."""
+    (ksched_xchg.hip rx_zero_regions), so no wait can take an earlier call's granule.  Bit-exact."""
     from ksched import cluster
     from ksched.dist import make_local_xchg_group
     from ksched.engine import Engine

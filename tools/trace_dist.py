@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-batch distributions of the persistent pipeline's phase stamps (KSCHED_TRACE_DUMP raw file: [cap][16]
-u64: wall-clock stamps at 100 MHz and the commit's counters in column 16, the columns of print_persist_trace in ksched_engine.hip).  The stderr summary
+u64: wall-clock stamps at 100 MHz and the commit's counters in column 16, the columns of print_persist_trace in ksched_diag.hip).  The stderr summary
 gives means; a mean can hide a few long stalls, so this prints percentiles and the stalls.
 
   python tools/trace_dist.py gpurun_out/trace_c4.bin [lag=3]
