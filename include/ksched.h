@@ -215,6 +215,37 @@ int ksched_explain_batch(ksched_ctx *ctx, int64_t p, int64_t *out_counts, int64_
 /* Per-node reasons of pod `pod` of the last schedule call at its turn: the "fit failure on node"
  * lines of its FailedScheduling event (out_reason: n_local bytes, may be NULL). */
 int ksched_explain_pod(ksched_ctx *ctx, int64_t pod, int64_t out_counts[KSCHED_NUM_REASONS], uint8_t *out_reason);
+/* ---- ranked dry run (added within ABI 6: probe with dlsym(lib, "ksched_rank"), the version number did not move) ----
+ * For each of m pod shapes, the k best nodes the scheduler would choose among if that pod were next, against
+ * the current (local) node state: the scheduler-extender filter + prioritize verbs, "why this node and not
+ * that one", capacity what-ifs.  Every pod is evaluated on its own; NOTHING is committed and nothing else a
+ * context holds changes (node rows, staged pods, the last call's results, ksched_explain_batch's validity).
+ * Entry r of pod i (out_*[i * k + r]) is its r-th best ELIGIBLE node in the scheduler's own order -- key
+ * descending, global index ascending.  Eligible: resource priority, score > 0 (and feasible under
+ * KSCHED_DOMAIN_FEASIBLE); best-price, feasible, ranked by price ascending.  So entry 0 is what ksched_schedule
+ * would pick for that pod, count == 0 && feasible == 0 is KSCHED_NO_FIT and count == 0 && feasible > 0 is
+ * KSCHED_NO_POSITIVE_SCORE.  Under KSCHED_DOMAIN_ALL a ranked node may fail the predicate (the reference's
+ * argmax over all nodes): out_reason shows it, the first failing check in ksched_explain's order.
+ *   out_idx      m*k  node index (global across ranks); -1 past out_count[i]
+ *   out_score    m*k  the score (resource priority) or the price (best-price), bit for bit the scheduler's; 0 past the end
+ *   out_reason   m*k  KSCHED_REASON_* of that node for that pod (KSCHED_REASON_FIT past the end)
+ *   out_count    m    valid entries, <= k
+ *   out_feasible m    nodes passing predicate()
+ * 1 <= k <= KSCHED_RANK_MAX; m >= 0 (large m is served in chunks: the device workspace stays below 20 MiB);
+ * selector may be NULL unless opts.use_labels; any output pointer may be NULL.  The call waits for the
+ * context's stream first, as ksched_explain does.  Multi-rank: the lists cover this rank's shard. */
+#define KSCHED_RANK_MAX 64
+int ksched_rank(ksched_ctx *ctx, int64_t m, const int64_t *req_cpu, const int64_t *req_mem, const int64_t *req_pods,
+                const uint64_t *selector, int32_t k, int32_t *out_idx, double *out_score, uint8_t *out_reason,
+                int32_t *out_count, int32_t *out_feasible);
+/* Host only (no context, no GPU; added within ABI 6 with ksched_rank): merges the lists nranks node shards
+ * returned for the same m pods and k -- idx_all / score_all / reason_all [rank][m][k], count_all / feasible_all
+ * [rank][m] -- into the global lists, in the same order (best-price: price ascending); out_feasible is the sum
+ * over the shards.  reason_all, feasible_all and any output pointer may be NULL. */
+int ksched_rank_merge(int32_t priority, int32_t nranks, int64_t m, int32_t k, const int32_t *idx_all,
+                      const double *score_all, const uint8_t *reason_all, const int32_t *count_all,
+                      const int32_t *feasible_all, int32_t *out_idx, double *out_score, uint8_t *out_reason,
+                      int32_t *out_count, int32_t *out_feasible);
 /* Copies the current (local) node state back to the host. */
 int ksched_read_nodes(ksched_ctx *ctx, int64_t n, int64_t *alloc_cpu, int64_t *alloc_mem, int64_t *alloc_pods);
 /* Device-side snapshot / restore of the node state (bench: identical start state every step). */

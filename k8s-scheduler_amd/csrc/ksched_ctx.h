@@ -102,6 +102,7 @@ struct ksched_bufs {
     DevBuf<uint64_t> slots;               // exact mode: the cross-workgroup exchange granules
     DevBuf<int32_t> perm;                 // exact mode on one workgroup, best-price: nodes by (price asc, index asc)
     DevBuf<void> xws, xbuf;               // explain: workspace; counts + NO_FIT pod list, or one pod's state + counts
+    DevBuf<void> rws;                     // ksched_rank: one chunk's pods, span lists and outputs (rank_geometry's bound)
     DevBuf<void> pws;                     // persistent pipeline: part lists, list / export rings, progress words, ...
     DevBuf<uint64_t> trace;               // KSCHED_PERSIST_TRACE: per-batch wall-clock stamps [rows][kTraceCols]
     DevBuf<uint64_t> trace_wg;            // KSCHED_TRACE_WG: per batch and score workgroup {start, arrival}

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "ksched_ctx.h"
+#include "ksched_rank.h"
 
 using namespace ksched;
 
@@ -277,6 +278,137 @@ int ksched_selftest_fastdiv(ksched_ctx *c, int64_t n, const double *a, const dou
     if (e == hipSuccess) e = hipMemcpy(out_fast, d + 3 * n, (size_t)n * 8, hipMemcpyDeviceToHost);
     hipFree(d);
     if (e != hipSuccess) return fail(c, KSCHED_E_DEVICE, std::string("selftest_fastdiv: ") + hipGetErrorString(e));
+    return KSCHED_OK;
+}
+
+// Ranked dry run (ksched_rank.hip).  Touches nothing a schedule call left behind: its pods, span lists and
+// outputs live in d->rws, and FAST53 is decided here for these m pods alone (c->fast53 stays the last run's).
+int ksched_rank(ksched_ctx *c, int64_t m, const int64_t *rc, const int64_t *rm, const int64_t *rp, const uint64_t *sel,
+                int32_t k, int32_t *out_idx, double *out_score, uint8_t *out_reason, int32_t *out_count,
+                int32_t *out_feasible) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "rank before load_nodes");
+    static_assert(KSCHED_RANK_MAX == kRankList, "one list entry per lane");
+    if (k < 1 || k > KSCHED_RANK_MAX) return fail(c, KSCHED_E_INVALID, "rank: k must be in 1..KSCHED_RANK_MAX");
+    if (m < 0 || (m > 0 && (!rc || !rm || !rp))) return fail(c, KSCHED_E_INVALID, "rank: bad arguments");
+    if (c->o.use_labels && m > 0 && !sel) return fail(c, KSCHED_E_INVALID, "rank: use_labels needs selectors");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (m == 0) return KSCHED_OK;
+    const int64_t n = c->n_local;
+    if (n == 0) {  // an empty shard ranks nothing
+        const size_t e = (size_t)m * (size_t)k;
+        if (out_idx) std::fill(out_idx, out_idx + e, -1);
+        if (out_score) std::fill(out_score, out_score + e, 0.0);
+        if (out_reason) std::memset(out_reason, 0, e);
+        if (out_count) std::fill(out_count, out_count + m, 0);
+        if (out_feasible) std::fill(out_feasible, out_feasible + m, 0);
+        return KSCHED_OK;
+    }
+    uint64_t mxr = 0;
+    for (int64_t i = 0; i < m; ++i) mxr = std::max(mxr, std::max(uabs(rc[i]), std::max(uabs(rm[i]), uabs(rp[i]))));
+    const bool f53 = sat_add(c->max_abs_alloc, mxr) < (1ull << 52);
+    // the workspace of one chunk: pods | span lists | counts | outputs, each 256-byte aligned
+    const int64_t mc_max = std::min<int64_t>(m, kRankChunk);
+    size_t nl = 0;  // span lists of the largest chunk: at most kRankGridWGs * kRankTile (rank_geometry)
+    for (int64_t q : {mc_max, m % kRankChunk}) {  // the full chunk and the tail (fewer pods, more spans)
+        if (q <= 0) continue;
+        int32_t s; int64_t rows;
+        rank_geometry(n, q, &s, &rows);
+        nl = std::max(nl, (size_t)q * (size_t)s);
+    }
+    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t o_pods = 0, o_part = al(o_pods + (size_t)mc_max * 32), o_fc = al(o_part + nl * kRankList * sizeof(Cand)),
+                 o_idx = al(o_fc + nl * 4), o_sc = al(o_idx + (size_t)mc_max * k * 4), o_rs = al(o_sc + (size_t)mc_max * k * 8),
+                 o_cnt = al(o_rs + (size_t)mc_max * k), o_feas = al(o_cnt + (size_t)mc_max * 4),
+                 total = al(o_feas + (size_t)mc_max * 4);
+    HIPCHK(c, c->d->rws.reserve(total));
+    char *w = static_cast<char *>(c->d->rws.p);
+    std::vector<char> stage(std::max((size_t)mc_max * 32, total - o_idx));  // host side of the chunk's two copies
+    for (int64_t at = 0; at < m; at += kRankChunk) {
+        const int64_t mc = std::min<int64_t>(kRankChunk, m - at);
+        RankArgs a{};
+        a.nodes = c->d->nodes; a.n_local = n; a.node_offset = c->o.node_offset;
+        int64_t *dp = reinterpret_cast<int64_t *>(w + o_pods);
+        a.rc = dp; a.rm = dp + mc; a.rp = dp + 2 * mc; a.sel = reinterpret_cast<uint64_t *>(dp + 3 * mc);
+        a.m = (int32_t)mc; a.k = k;
+        rank_geometry(n, mc, &a.spans, &a.span_rows);
+        if ((size_t)mc * a.spans > nl) return fail(c, KSCHED_E_NOMEM, "rank: workspace bound");  // (rank_geometry's bound)
+        a.part = reinterpret_cast<Cand *>(w + o_part); a.part_fc = reinterpret_cast<int32_t *>(w + o_fc);
+        a.out_idx = reinterpret_cast<int32_t *>(w + o_idx); a.out_score = reinterpret_cast<double *>(w + o_sc);
+        a.out_reason = reinterpret_cast<uint8_t *>(w + o_rs); a.out_count = reinterpret_cast<int32_t *>(w + o_cnt);
+        a.out_feasible = reinterpret_cast<int32_t *>(w + o_feas);
+        // one copy in and one copy out per chunk (a one-pod call is mostly copies), in the stream of the kernels
+        int64_t *hp = reinterpret_cast<int64_t *>(stage.data());
+        std::memcpy(hp, rc + at, (size_t)mc * 8);
+        std::memcpy(hp + mc, rm + at, (size_t)mc * 8);
+        std::memcpy(hp + 2 * mc, rp + at, (size_t)mc * 8);
+        if (sel) std::memcpy(hp + 3 * mc, sel + at, (size_t)mc * 8);
+        else std::memset(hp + 3 * mc, 0, (size_t)mc * 8);
+        HIPCHK(c, hipMemcpyAsync(dp, hp, (size_t)mc * 32, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_rank(c->o.priority, c->o.domain, c->o.use_labels != 0, f53, a, c->stream));
+        HIPCHK(c, hipMemcpyAsync(stage.data(), w + o_idx, total - o_idx, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // the next chunk reuses the workspace and the staging buffer
+        const size_t e = (size_t)mc * k, eo = (size_t)at * k;
+        const char *ho = stage.data();  // the outputs, at their workspace offsets less o_idx
+        if (out_idx) std::memcpy(out_idx + eo, ho, e * 4);
+        if (out_score) std::memcpy(out_score + eo, ho + (o_sc - o_idx), e * 8);
+        if (out_reason) std::memcpy(out_reason + eo, ho + (o_rs - o_idx), e);
+        if (out_count) std::memcpy(out_count + at, ho + (o_cnt - o_idx), (size_t)mc * 4);
+        if (out_feasible) std::memcpy(out_feasible + at, ho + (o_feas - o_idx), (size_t)mc * 4);
+    }
+    return KSCHED_OK;
+}
+
+// Host only: the shards' ranked lists -> the global one, in the same order (key descending = score descending, or
+// price ascending; global index ascending on ties), by an R-way merge of the list heads.
+int ksched_rank_merge(int32_t priority, int32_t nranks, int64_t m, int32_t k, const int32_t *idx_all,
+                      const double *score_all, const uint8_t *reason_all, const int32_t *count_all,
+                      const int32_t *feasible_all, int32_t *out_idx, double *out_score, uint8_t *out_reason,
+                      int32_t *out_count, int32_t *out_feasible) {
+    if (priority != KSCHED_PRIORITY_RESOURCE && priority != KSCHED_PRIORITY_BEST_PRICE) return KSCHED_E_INVALID;
+    if (nranks < 1 || k < 1 || k > KSCHED_RANK_MAX || m < 0) return KSCHED_E_INVALID;
+    if (m > 0 && (!idx_all || !score_all || !count_all)) return KSCHED_E_INVALID;
+    const bool price = priority == KSCHED_PRIORITY_BEST_PRICE;
+    std::vector<int32_t> head((size_t)nranks);
+    for (int64_t i = 0; i < m; ++i) {
+        int64_t feas = 0;
+        for (int32_t r = 0; r < nranks; ++r) {
+            head[(size_t)r] = 0;
+            const int32_t cn = count_all[(size_t)r * m + i];
+            if (cn < 0 || cn > k) return KSCHED_E_INVALID;
+            if (feasible_all) feas += feasible_all[(size_t)r * m + i];
+        }
+        int32_t q = 0;
+        for (; q < k; ++q) {
+            int32_t br = -1;
+            size_t be = 0;
+            for (int32_t r = 0; r < nranks; ++r) {
+                if (head[(size_t)r] >= count_all[(size_t)r * m + i]) continue;
+                const size_t e = ((size_t)r * m + i) * k + head[(size_t)r];
+                if (br >= 0) {
+                    const double a = score_all[e], b = score_all[be];
+                    const bool bt = price ? a < b : a > b;
+                    if (!(bt || (a == b && idx_all[e] < idx_all[be]))) continue;
+                }
+                br = r; be = e;
+            }
+            if (br < 0) break;
+            ++head[(size_t)br];
+            const size_t o = (size_t)i * k + q;
+            if (out_idx) out_idx[o] = idx_all[be];
+            if (out_score) out_score[o] = score_all[be];
+            if (out_reason) out_reason[o] = reason_all ? reason_all[be] : 0;
+        }
+        if (out_count) out_count[i] = q;
+        for (; q < k; ++q) {
+            const size_t o = (size_t)i * k + q;
+            if (out_idx) out_idx[o] = -1;
+            if (out_score) out_score[o] = 0.0;
+            if (out_reason) out_reason[o] = 0;
+        }
+        if (out_feasible) out_feasible[i] = (int32_t)feas;
+    }
     return KSCHED_OK;
 }
 

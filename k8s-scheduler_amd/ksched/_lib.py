@@ -31,6 +31,7 @@ PRIORITY_RESOURCE, PRIORITY_BEST_PRICE = 0, 1
 DOMAIN_ALL, DOMAIN_FEASIBLE = 0, 1
 REASON_FIT, REASON_CPU, REASON_MEMORY, REASON_POD, REASON_LABELS = 0, 1, 2, 3, 4
 NUM_REASONS = 5
+RANK_MAX = 64  # KSCHED_RANK_MAX: entries ksched_rank keeps per pod
 XCHG_HANDLE_BYTES = 128
 # the reference's per-node failure text (anchor/predicate.go:135,140,145)
 REASON_TEXT = {REASON_CPU: "Insufficient CPU", REASON_MEMORY: "Insufficient Memory", REASON_POD: "Insufficient Pod",
@@ -70,6 +71,7 @@ U64P = C.POINTER(C.c_uint64)
 I32P = C.POINTER(C.c_int32)
 F64P = C.POINTER(C.c_double)
 F32P = C.POINTER(C.c_float)
+U8P = C.POINTER(C.c_uint8)
 CTX = C.c_void_p
 STRV = C.POINTER(C.c_char_p)
 
@@ -96,6 +98,9 @@ SIGNATURES = [
     ("ksched_explain", C.c_int, [CTX, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, I64P, C.POINTER(C.c_uint8)]),
     ("ksched_explain_batch", C.c_int, [CTX, C.c_int64, I64P, I64P]),
     ("ksched_explain_pod", C.c_int, [CTX, C.c_int64, I64P, C.POINTER(C.c_uint8)]),
+    ("ksched_rank", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, C.c_int32, I32P, F64P, U8P, I32P, I32P]),
+    ("ksched_rank_merge", C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, I32P, F64P, U8P, I32P, I32P,
+                                    I32P, F64P, U8P, I32P, I32P]),
     ("ksched_read_nodes", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P]),
     ("ksched_save_state", C.c_int, [CTX]),
     ("ksched_restore_state", C.c_int, [CTX]),

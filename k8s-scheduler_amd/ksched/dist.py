@@ -97,6 +97,25 @@ def make_sharded_engine(cl, rank: int, world: int, device: int, mode=None, group
     return eng, (lo, hi)
 
 
+def merge_ranked(priority: int, shards):
+    """The global ranked lists from the node shards' (ksched_rank_merge, host only: no context, no device traffic).
+    shards: one Engine.rank() result (idx, score, reason, count, feasible) per rank, in rank order, for the same
+    pods and k.  Returns the same five arrays for the whole cluster (best-price: price ascending)."""
+    import ctypes as C
+    from . import _lib as L
+    r = len(shards)
+    idx, score, reason, count, feas = (np.ascontiguousarray(np.stack([s[j] for s in shards]), dtype=t)
+                                       for j, t in enumerate((np.int32, np.float64, np.uint8, np.int32, np.int32)))
+    m, k = idx.shape[1], idx.shape[2]
+    oi = np.empty((m, k), np.int32); os_ = np.empty((m, k), np.float64); orr = np.empty((m, k), np.uint8)
+    oc = np.empty(m, np.int32); of = np.empty(m, np.int32)
+    L.check(L.lib().ksched_rank_merge(int(priority), r, m, k, L.ptr(idx, C.c_int32), L.ptr(score, C.c_double),
+                                      L.ptr(reason, C.c_uint8), L.ptr(count, C.c_int32), L.ptr(feas, C.c_int32),
+                                      L.ptr(oi, C.c_int32), L.ptr(os_, C.c_double), L.ptr(orr, C.c_uint8),
+                                      L.ptr(oc, C.c_int32), L.ptr(of, C.c_int32)), what="rank_merge")
+    return oi, os_, orr, oc, of
+
+
 def gather_node_state(local_state, world: int):
     """Concatenate every rank's (cpu, mem, pods) node state in rank order (torch.distributed)."""
     import torch

@@ -189,6 +189,24 @@ class Engine:
                   "explain_pod")
         return cnt, rs
 
+    def rank(self, req_cpu, req_mem, req_pods, selector=None, k: int = 16):
+        """Ranked dry run (ksched_rank): for each pod shape, its k best eligible nodes against the current node
+        state, in the scheduler's order; nothing is committed.  Returns (idx int32[m, k] (-1 past count),
+        score f64[m, k] (score, or price), reason uint8[m, k] (REASON_* of that node), count int32[m],
+        feasible int32[m]).  Entry 0 is what schedule() would pick for that pod if it were next."""
+        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
+        m = rc.shape[0]
+        assert rm.shape[0] == m and rp.shape[0] == m
+        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
+        kk = max(int(k), 0)
+        idx = np.empty((m, kk), np.int32); score = np.empty((m, kk), np.float64); reason = np.empty((m, kk), np.uint8)
+        count = np.empty(m, np.int32); feas = np.empty(m, np.int32)
+        self._chk(L.lib().ksched_rank(self._ctx, m, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64), L.ptr(rp, C.c_int64),
+                                      L.ptr(sel, C.c_uint64), int(k), L.ptr(idx, C.c_int32), L.ptr(score, C.c_double),
+                                      L.ptr(reason, C.c_uint8), L.ptr(count, C.c_int32), L.ptr(feas, C.c_int32)),
+                  "rank")
+        return idx, score, reason, count, feas
+
     def read_nodes(self):
         ac = np.empty(self.n, np.int64); am = np.empty(self.n, np.int64); ap = np.empty(self.n, np.int64)
         self._chk(L.lib().ksched_read_nodes(self._ctx, self.n, L.ptr(ac, C.c_int64), L.ptr(am, C.c_int64),

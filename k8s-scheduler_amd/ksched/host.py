@@ -296,6 +296,18 @@ class FakeCluster:
         no host replay and no state change."""
         return {i: self.engine.explain_pod(i)[1] for i, x in enumerate(idx) if x == L.NO_FIT}
 
+    def rank_pod(self, pod: Pod, k: int = 16, selector: Optional[int] = None):
+        """The scheduler-extender filter + prioritize answer for one pod, without placing it (ksched_rank): its k
+        best nodes in the scheduler's order as [(Node, score | price, reason text | None)].  The text (REASON_TEXT)
+        is set only where a ranked node fails the predicate -- the all-node domain's quirk."""
+        rc, rm, rp = pack_pods([pod])
+        if selector is None:
+            selector = self.selector_of(pod)
+        sel = np.asarray([selector], dtype=np.uint64) if self.use_labels else None
+        idx, score, reason, count, _ = self.engine.rank(rc, rm, rp, sel, k=k)
+        return [(self.nodes[int(idx[0, r])], float(score[0, r]), L.REASON_TEXT.get(int(reason[0, r])))
+                for r in range(int(count[0]))]
+
     def bind(self, pod: Pod, node: Node) -> None:
         """POST Binding + Scheduled event (anchor/schedule.go:200-261), in memory."""
         pod.node_name = node.name
