@@ -39,6 +39,7 @@ extern "C" {
 /* per-pod outcome in out_idx[] */
 #define KSCHED_NO_FIT (-1)            /* predicate found no node: reference returns "failed to fit" (anchor/schedule.go:74-76) */
 #define KSCHED_NO_POSITIVE_SCORE (-2) /* no node scored > 0: reference binds a nil node and panics (anchor/priorities.go:55-62, anchor/schedule.go:208); documented divergence */
+#define KSCHED_GANG_REJECTED (-3)     /* ksched_schedule_gangs only: the pod found a node, but too few members of its gang did; its commit was undone */
 
 /* options */
 #define KSCHED_MODE_EXACT 0     /* pod-by-pod: one full node scan + grid-wide arg-best per pod (persistent kernel) */
@@ -262,6 +263,37 @@ int ksched_restore_state(ksched_ctx *ctx);
 int ksched_schedule(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,
                     const int64_t *req_pods, const uint64_t *selector,
                     int32_t *out_idx, double *out_score, int32_t *out_feasible);
+
+/* ---- gang scheduling (added within ABI 6: probe with dlsym(lib, "ksched_schedule_gangs"); ksched_stats did not change) ----
+ * The same p pods in all-or-nothing groups (Kubernetes coscheduling, PodGroup.minMember), resolved by ONE launch of
+ * the exact kernel whatever opts.mode says (stats.pipeline == KSCHED_PIPE_EXACT).  A build extension: the reference's
+ * schedulePods (anchor/schedule.go:185-197) knows no groups.
+ *   gang_off  n_gangs + 1 CSR offsets (the idiom of cont_off below): gang_off[0] == 0, gang_off[n_gangs] == p,
+ *             strictly increasing (no empty gang); gang g is pods [gang_off[g], gang_off[g + 1]), at most
+ *             KSCHED_GANG_MAX of them
+ *   gang_min  n_gangs minimum members, 1 <= gang_min[g] <= size; NULL: every member is required
+ * Gangs are processed in order and members in order within a gang.  Every member is evaluated exactly as
+ * ksched_schedule evaluates a pod in exact mode, against the current state -- which includes the tentative
+ * placements of the earlier members of its own gang -- and is tentatively committed as usual (alloc -= (req_cpu,
+ * req_mem, 1), wrapping).  No member is skipped, even after an earlier member of its gang failed, so every pod's
+ * out_feasible is defined.  A member counts as placed when its outcome is a node index (>= 0; under
+ * KSCHED_DOMAIN_ALL that node may fail the predicate, as in the reference).  At the end of gang g:
+ *   placed >= gang_min[g]: accepted.  The commits stand; members that failed keep KSCHED_NO_FIT /
+ *     KSCHED_NO_POSITIVE_SCORE.
+ *   placed <  gang_min[g]: rejected.  Every tentative commit of the gang is undone (a wrapping add): the node rows
+ *     are bit-identical to the rows before the gang.  Members that had been placed get out_idx =
+ *     KSCHED_GANG_REJECTED and out_score = 0; members that failed keep their own code -- the reason the gang
+ *     failed; out_feasible keeps the count each member saw at its turn.
+ *   out_gang_placed[g] (may be NULL) = members bound: 0 for a rejected gang.
+ * A call whose gangs all have size 1 is ksched_schedule in exact mode.  KSCHED_E_INVALID (nothing changed): a gang
+ * above KSCHED_GANG_MAX, bad offsets or minima, opts.nranks > 1.  Afterwards ksched_explain_batch /
+ * ksched_explain_pod return KSCHED_E_STATE (they rebuild a pod's state from final placements, which a rolled-back
+ * gang does not have); after a device error the node state is as unspecified as after a failed ksched_schedule. */
+#define KSCHED_GANG_MAX 1024
+int ksched_schedule_gangs(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,
+                          const int64_t *req_pods, const uint64_t *selector, int64_t n_gangs, const int64_t *gang_off,
+                          const int32_t *gang_min, int32_t *out_idx, double *out_score, int32_t *out_feasible,
+                          int32_t *out_gang_placed);
 
 /* Same, in two halves, with the pods staged in HBM: upload once, run many times (bench). */
 int ksched_upload_pods(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,

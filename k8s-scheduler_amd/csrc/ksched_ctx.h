@@ -101,6 +101,7 @@ struct ksched_bufs {
     DevBuf<int64_t> dbg, mdbg;            // KSCHED_COMMIT_STAMPS / KSCHED_MERGE_STAMPS cycle sums
     DevBuf<uint64_t> slots;               // exact mode: the cross-workgroup exchange granules
     DevBuf<int32_t> perm;                 // exact mode on one workgroup, best-price: nodes by (price asc, index asc)
+    DevBuf<int32_t> gend, gplaced;        // ksched_schedule_gangs: ExactArgs::gang_end per pod, members bound per gang
     DevBuf<void> xws, xbuf;               // explain: workspace; counts + NO_FIT pod list, or one pod's state + counts
     DevBuf<void> rws;                     // ksched_rank: one chunk's pods, span lists and outputs (rank_geometry's bound)
     DevBuf<void> pws;                     // persistent pipeline: part lists, list / export rings, progress words, ...

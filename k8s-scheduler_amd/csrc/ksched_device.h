@@ -145,6 +145,7 @@ template <bool COH>
 __device__ __forceinline__ void store_i64(int64_t *p, int64_t v) { if (COH) st_coh(p, (uint64_t)v); else *p = v; }
 
 __host__ __device__ inline int64_t wsub(int64_t a, int64_t b) { return (int64_t)((uint64_t)a - (uint64_t)b); }
+__host__ __device__ inline int64_t wadd(int64_t a, int64_t b) { return (int64_t)((uint64_t)a + (uint64_t)b); }
 
 
 

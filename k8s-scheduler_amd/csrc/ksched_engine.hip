@@ -462,7 +462,9 @@ int enqueue_persistent(ksched_ctx *c) {
     return KSCHED_OK;
 }
 
-int enqueue_exact(ksched_ctx *c) {
+// gang: the run of ksched_schedule_gangs (the staged gangs in d->gend) -- always k_exact<GANG>, the
+// multi-slot kernel, under the same geometry and launch rule as a plain exact run
+int enqueue_exact(ksched_ctx *c, bool gang) {
     if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "exact mode is single-GPU; use batched mode across ranks");
     const int64_t n = c->n_local;
     // the whole node set in ONE workgroup's registers (k_exact1): no cross-workgroup exchange per pod
@@ -473,7 +475,7 @@ int enqueue_exact(ksched_ctx *c) {
     a.pods = PodArgs{c->d->rc, c->d->rm, c->d->rp, c->d->sel, c->p};
     a.out = OutArgs{c->d->oidx, c->d->osc, c->d->ofeas};
     a.err = c->d->err;
-    if (c->o.exact_wgs <= 1 && n > 0 && n <= (int64_t)kExact1Block * max1 && (!price || c->perm_n == n)) {
+    if (!gang && c->o.exact_wgs <= 1 && n > 0 && n <= (int64_t)kExact1Block * max1 && (!price || c->perm_n == n)) {
         int bs = kExact1Block;
         if (price && c->diag.exact1_bs == 512 && n <= 5120) bs = 512;
         if (price && c->diag.exact1_bs == 256 && n <= 5120) bs = 256;
@@ -513,8 +515,14 @@ int enqueue_exact(ksched_ctx *c) {
     a.timeout_ticks = c->diag.exchange_timeout_ms * 100000;  // 100 MHz wall clock
     int e0 = -1;
     HIPCHK(c, ev_begin(c, c->o.timing != 0, &e0, c->stream));
-    HIPCHK(c, launch_exact(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
-                           G > 1 && !c->diag.plain_launch, c->stream));
+    if (gang) {
+        a.gang_end = c->d->gend; a.gang_placed = c->d->gplaced;
+        HIPCHK(c, launch_exact_gang(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
+                                    G > 1 && !c->diag.plain_launch, c->stream));
+    } else {
+        HIPCHK(c, launch_exact(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
+                               G > 1 && !c->diag.plain_launch, c->stream));
+    }
     HIPCHK(c, ev_end(c, c->o.timing != 0, 0, e0, c->p * n, c->stream));
     c->st.pair_evals = c->p * n;
     return KSCHED_OK;
@@ -617,8 +625,8 @@ int ksched_destroy(ksched_ctx *c) {
 
 const char *ksched_last_error(const ksched_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
-int ksched_run(ksched_ctx *c) {
-    if (!c) return KSCHED_E_INVALID;
+// ksched_run, or (gang) the run of ksched_schedule_gangs: the exact kernel over the staged gangs whatever opts.mode
+static int run_impl(ksched_ctx *c, bool gang) {
     if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "run before load_nodes");
     if (c->o.nranks > 1 && !c->comm && !c->group && !c->xchg_ready)
         return fail(c, KSCHED_E_STATE, "run: multi-rank context without ksched_set_comm / ksched_set_group / "
@@ -631,6 +639,7 @@ int ksched_run(ksched_ctx *c) {
     c->st.pods = c->p;
     int mode = c->o.mode;
     if (mode == KSCHED_MODE_AUTO) mode = c->o.nranks > 1 ? KSCHED_MODE_BATCHED : KSCHED_MODE_EXACT;
+    if (gang) mode = KSCHED_MODE_EXACT;
     c->xchg_run = c->xchg_ready && mode == KSCHED_MODE_BATCHED && c->p > 0;
     // a multi-rank batched call needs a transport: the device exchange, an RCCL communicator or a rank group
     // (never a rank committing from its own shard alone)
@@ -642,7 +651,7 @@ int ksched_run(ksched_ctx *c) {
     if (c->p > 0) {
         c->persist_stats = false;
         if (mode == KSCHED_MODE_EXACT) {
-            r = enqueue_exact(c);
+            r = enqueue_exact(c, gang);
             c->st.pipeline = KSCHED_PIPE_EXACT;
         } else {
             r = enqueue_persistent(c);
@@ -663,8 +672,14 @@ int ksched_run(ksched_ctx *c) {
     // the call's commits move every allocatable by at most the sum of the staged requests: keep the
     // FAST53 bound true of the state the NEXT call starts from
     if (r == KSCHED_OK) c->max_abs_alloc = sat_add(c->max_abs_alloc, c->sum_abs_req);
-    c->explain_valid = r == KSCHED_OK;
+    // (a rolled-back gang leaves no final placements for ksched_explain_batch to rebuild a pod's state from)
+    c->explain_valid = r == KSCHED_OK && !gang;
     return r;
+}
+
+int ksched_run(ksched_ctx *c) {
+    if (!c) return KSCHED_E_INVALID;
+    return run_impl(c, false);
 }
 
 static int sync_impl(ksched_ctx *c) {
@@ -751,6 +766,55 @@ int ksched_schedule(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *
     if ((r = ksched_run(c)) != KSCHED_OK) { ksched_sync(c); return r; }
     if ((r = ksched_sync(c)) != KSCHED_OK) return r;
     return ksched_download_results(c, p, oi, os, of);
+}
+
+int ksched_schedule_gangs(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                          const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
+                          int32_t *oi, double *os, int32_t *of, int32_t *out_gang_placed) {
+    if (!c) return KSCHED_E_INVALID;
+    static_assert(KSCHED_GANG_MAX == kGangMax && KSCHED_GANG_REJECTED == kGangRejected, "gang constants");
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_gangs before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_gangs is single-GPU (the exact kernel)");
+    if (p < 0 || n_gangs < 0 || n_gangs > p || !gang_off || gang_off[0] != 0 || gang_off[n_gangs] != p)
+        return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_off must run from 0 to p over n_gangs <= p gangs");
+    // every offset and minimum is checked before anything is written or allocated: each offset above its
+    // predecessor and at most p (so every gang's pods lie in [0, p)), each gang within the cap
+    for (int64_t g = 0; g < n_gangs; ++g) {
+        if (gang_off[g + 1] <= gang_off[g] || gang_off[g + 1] > p)
+            return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_off must be strictly increasing and end at p");
+        const int64_t size = gang_off[g + 1] - gang_off[g];
+        if (size > KSCHED_GANG_MAX) return fail(c, KSCHED_E_INVALID, "schedule_gangs: a gang has more than KSCHED_GANG_MAX members");
+        if (gang_min && (gang_min[g] < 1 || gang_min[g] > size))
+            return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_min must be in 1..size");
+    }
+    // staged per pod, so the kernel reads a gang's end with its last member's request: 0, or size | minimum << 16
+    static_assert(KSCHED_GANG_MAX < (1 << 15), "ExactArgs::gang_end packs size and minimum into 16 bits each");
+    std::vector<int32_t> gend;
+    try {
+        gend.assign((size_t)p, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "schedule_gangs: host staging buffer");
+    }
+    for (int64_t g = 0; g < n_gangs; ++g) {
+        const int32_t size = (int32_t)(gang_off[g + 1] - gang_off[g]);
+        gend[(size_t)gang_off[g + 1] - 1] = size | (gang_min ? gang_min[g] : size) << 16;
+    }
+    int r = ksched_upload_pods(c, p, rc, rm, rp, sel);
+    if (r != KSCHED_OK) return r;
+    const size_t ng = (size_t)n_gangs;
+    HIPCHK(c, c->d->gend.reserve((size_t)p * 4)); HIPCHK(c, c->d->gplaced.reserve(ng * 4));
+    // in the stream of the kernel that reads it, finished before `gend` goes (ksched_upload_pods)
+    if (p > 0) HIPCHK(c, hipMemcpyAsync(c->d->gend, gend.data(), (size_t)p * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((r = run_impl(c, true)) != KSCHED_OK) { ksched_sync(c); return r; }
+    if ((r = ksched_sync(c)) != KSCHED_OK) return r;
+    if ((r = ksched_download_results(c, p, oi, os, of)) != KSCHED_OK) return r;
+    std::vector<int32_t> gp(ng);
+    if (ng > 0) HIPCHK(c, hipMemcpy(gp.data(), c->d->gplaced, ng * 4, hipMemcpyDeviceToHost));
+    c->st.placed = 0;
+    for (int32_t v : gp) c->st.placed += v;
+    if (out_gang_placed && ng > 0) std::memcpy(out_gang_placed, gp.data(), ng * 4);
+    return KSCHED_OK;
 }
 
 }  // extern "C"

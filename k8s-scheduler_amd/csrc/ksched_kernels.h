@@ -195,7 +195,14 @@ struct ExactArgs {
     int32_t *err;     // device error word (kErrExactExchange)
     int64_t timeout_ticks;
     const int32_t *perm;  // k_exact1: slot -> node (best-price: nodes by price asc, index asc); null: slot = node
+    // k_exact<GANG> (ksched_schedule_gangs): per pod, 0 or -- at the last member of its gang -- the gang's size
+    // (<= kGangMax) | the members it needs << 16 (both fit 15 bits: kGangMax < 2^15, asserted where the host packs
+    // them); the kernel reads it with the pod's request
+    const int32_t *gang_end;
+    int32_t *gang_placed;     // out: members bound per gang, 0 for a rejected one (may be null)
 };
+constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
+constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
 
 struct ScoreArgs {
     NodeRec *nodes;    // read; the rows of `patch` are written back by their chunk's wave
@@ -414,6 +421,9 @@ hipError_t explain_pod_at(const ExplainArgs &a, int64_t pod, int64_t *state, uin
 hipError_t launch_prep_nodes(NodeRec *nodes, int64_t n, hipStream_t s);
 hipError_t launch_exact(int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
                         bool cooperative, hipStream_t s);
+// the same launch of k_exact<GANG>: a.gang_end set (a.gang_placed may be null)
+hipError_t launch_exact_gang(int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
+                             bool cooperative, hipStream_t s);
 hipError_t launch_score_topk(int KC, int prio, int dom, bool lab, bool fast53, const ScoreArgs &a, int pod_groups,
                              hipStream_t s);
 // one workgroup per pod: the score kernel's workgroup lists -> the pod's K-entry Rec list (C_in <= 256)

@@ -6,10 +6,10 @@ Product surface:
   ksched.dist              node-sharded multi-GPU helpers (RCCL inside the engine)
   ksched.cluster           seeded synthetic clusters for the BASELINE configs
 """
-from ._lib import (DOMAIN_ALL, DOMAIN_FEASIBLE, MODE_AUTO, MODE_BATCHED, MODE_EXACT, NO_FIT, NO_POSITIVE_SCORE,
-                   PRIORITY_BEST_PRICE, PRIORITY_RESOURCE, KschedError, lib)
+from ._lib import (DOMAIN_ALL, DOMAIN_FEASIBLE, MODE_AUTO, MODE_BATCHED, MODE_EXACT, GANG_REJECTED, NO_FIT,
+                   NO_POSITIVE_SCORE, PRIORITY_BEST_PRICE, PRIORITY_RESOURCE, KschedError, lib)
 from .engine import Engine, Group, engine_for
 
 __all__ = ["Engine", "Group", "engine_for", "KschedError", "lib", "MODE_AUTO", "MODE_BATCHED", "MODE_EXACT",
            "PRIORITY_RESOURCE", "PRIORITY_BEST_PRICE", "DOMAIN_ALL", "DOMAIN_FEASIBLE", "NO_FIT",
-           "NO_POSITIVE_SCORE"]
+           "NO_POSITIVE_SCORE", "GANG_REJECTED"]

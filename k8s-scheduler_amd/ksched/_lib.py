@@ -22,6 +22,7 @@ E_NOMEM = -5
 E_UNKNOWN_NODE = -6
 NO_FIT = -1
 NO_POSITIVE_SCORE = -2
+GANG_REJECTED = -3  # KSCHED_GANG_REJECTED (ksched_schedule_gangs): placed, but its gang was rolled back
 
 ABI_VERSION = 6
 XCHG_RINGS_UNCACHED, XCHG_RINGS_IPC = 1, 2
@@ -32,6 +33,7 @@ DOMAIN_ALL, DOMAIN_FEASIBLE = 0, 1
 REASON_FIT, REASON_CPU, REASON_MEMORY, REASON_POD, REASON_LABELS = 0, 1, 2, 3, 4
 NUM_REASONS = 5
 RANK_MAX = 64  # KSCHED_RANK_MAX: entries ksched_rank keeps per pod
+GANG_MAX = 1024  # KSCHED_GANG_MAX: members of one gang
 XCHG_HANDLE_BYTES = 128
 # the reference's per-node failure text (anchor/predicate.go:135,140,145)
 REASON_TEXT = {REASON_CPU: "Insufficient CPU", REASON_MEMORY: "Insufficient Memory", REASON_POD: "Insufficient Pod",
@@ -105,6 +107,8 @@ SIGNATURES = [
     ("ksched_save_state", C.c_int, [CTX]),
     ("ksched_restore_state", C.c_int, [CTX]),
     ("ksched_schedule", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, I32P, F64P, I32P]),
+    ("ksched_schedule_gangs", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, C.c_int64, I64P, I32P, I32P, F64P,
+                                        I32P, I32P]),
     ("ksched_upload_pods", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P]),
     ("ksched_run", C.c_int, [CTX]),
     ("ksched_sync", C.c_int, [CTX]),

@@ -265,6 +265,29 @@ class Engine:
         self.sync()
         return self.results()
 
+    def schedule_gangs(self, req_cpu, req_mem, req_pods, selector, gang_off, gang_min=None):
+        """The pending pods in all-or-nothing groups (ksched_schedule_gangs): gang g is pods [gang_off[g],
+        gang_off[g + 1]) and is bound only if at least gang_min[g] of its members (None: all) find a node; a
+        rejected gang's commits are undone before the next gang is evaluated.  One launch of the exact kernel,
+        whatever the engine's mode.  Returns (idx, score, feasible, gang_placed): idx is GANG_REJECTED for a member
+        that found a node in a rejected gang; gang_placed[g] = members bound (0 for a rejected gang)."""
+        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
+        p = rc.shape[0]
+        assert rm.shape[0] == p and rp.shape[0] == p
+        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
+        off = _i64(gang_off)
+        ng = off.shape[0] - 1
+        gmin = None if gang_min is None else np.ascontiguousarray(gang_min, dtype=np.int32)
+        assert ng >= 0 and (gmin is None or gmin.shape[0] == ng)
+        oi = np.empty(p, np.int32); os_ = np.empty(p, np.float64); of = np.empty(p, np.int32)
+        gp = np.empty(ng, np.int32)
+        self._chk(L.lib().ksched_schedule_gangs(self._ctx, p, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64),
+                                                L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64), ng, L.ptr(off, C.c_int64),
+                                                L.ptr(gmin, C.c_int32), L.ptr(oi, C.c_int32), L.ptr(os_, C.c_double),
+                                                L.ptr(of, C.c_int32), L.ptr(gp, C.c_int32)), "schedule_gangs")
+        self.p = p
+        return oi, os_, of, gp
+
 
 def engine_for(cl, mode: Optional[int] = None, **kw) -> Engine:
     """Engine configured for a ksched.cluster.Cluster and loaded with its nodes."""

@@ -30,6 +30,11 @@ class NilNodeError(Exception):
     anchor/schedule.go:208); the build reports it instead."""
 
 
+class GangRejected(Exception):
+    """The pod found a node, but fewer members of its gang than the gang needs did: nothing of the gang is bound
+    (KSCHED_GANG_REJECTED; build extension, the reference has no pod groups)."""
+
+
 class FatalParse(Exception):
     """The reference's errFatal on an unparseable quantity (anchor/predicate.go:15,31,39,49)."""
 
@@ -64,6 +69,10 @@ SCHEDULER_ANNOTATION = "scheduler.alpha.kubernetes.io/name"  # anchor/schedule.g
 # The README's per-node price (README.md:37-48) has no key in the reference's code; the build reads
 # it from this annotation (the upstream Hightower scheduler's key; build-defined).
 PRICE_ANNOTATION = "hightower.com/cost"
+# Pod groups (Kubernetes coscheduling's PodGroup as the kube-batch annotations; build extension): pods naming the
+# same group are bound all-or-nothing, or when at least group-min-member of them fit.
+GROUP_NAME_ANNOTATION = "scheduling.k8s.io/group-name"
+GROUP_MIN_ANNOTATION = "scheduling.k8s.io/group-min-member"
 
 
 def _as_obj(x):
@@ -172,6 +181,44 @@ def pack_pods(pods: List[Pod]):
         raise FatalParse("quantity parse failed")
     L.check(r, what="pack_pods")
     return rc, rm, rp
+
+
+def group_gangs(pods: List[Pod]):
+    """Pending pods -> the gangs of ksched_schedule_gangs.  Pods are stable-grouped by GROUP_NAME_ANNOTATION: a gang
+    sits at the position of its first member and keeps its members' order; a pod without the annotation is a gang
+    of one.  GROUP_MIN_ANNOTATION (on any member; the members must agree) is the gang's minimum, all members by
+    default.  Returns (pods reordered, gang_off int64[g + 1], gang_min int32[g]); ValueError for a minimum that is
+    not an integer in 1..size or that the members disagree on."""
+    gangs: List[List[Pod]] = []
+    by_name: Dict[str, int] = {}
+    for pod in pods:
+        name = pod.annotations.get(GROUP_NAME_ANNOTATION)
+        if not name:
+            gangs.append([pod])
+        elif name in by_name:
+            gangs[by_name[name]].append(pod)
+        else:
+            by_name[name] = len(gangs)
+            gangs.append([pod])
+    off = [0]
+    mins = []
+    for members in gangs:
+        name = members[0].annotations.get(GROUP_NAME_ANNOTATION) or members[0].name
+        stated = {m.annotations[GROUP_MIN_ANNOTATION] for m in members if GROUP_MIN_ANNOTATION in m.annotations}
+        if len(stated) > 1:
+            raise ValueError(f"gang ({name}): members disagree on {GROUP_MIN_ANNOTATION}: {sorted(stated)}")
+        need = len(members)
+        if stated:
+            try:
+                need = int(next(iter(stated)))
+            except ValueError:
+                raise ValueError(f"gang ({name}): {GROUP_MIN_ANNOTATION} is not an integer") from None
+            if need < 1 or need > len(members):
+                raise ValueError(f"gang ({name}): {GROUP_MIN_ANNOTATION} {need} is not in 1..{len(members)}")
+        off.append(off[-1] + len(members))
+        mins.append(need)
+    return ([m for members in gangs for m in members], np.asarray(off, dtype=np.int64),
+            np.asarray(mins, dtype=np.int32))
 
 
 def parse_price(s: str) -> float:
@@ -339,6 +386,45 @@ class FakeCluster:
                 node = self.nodes[int(i)]
                 self.bind(pod, node)
                 out.append((pod, node))
+        return out
+
+    def schedule_gangs(self, pending: Optional[List[Pod]] = None):
+        """schedule_pods with pod groups (group_gangs; ksched_schedule_gangs): one engine call resolves every gang
+        in order.  An accepted gang's placed members are bound in order; a rejected gang binds nothing and posts one
+        FailedScheduling event per member.  Returns (pod, node | Exception) in the gangs' order -- GangRejected for
+        a member that found a node in a rejected gang.  (No per-node "fit failure" lines: a rolled-back gang
+        leaves no placements to rebuild a pod's state from.)"""
+        pending = self.unscheduled_pods() if pending is None else pending
+        pods, off, gmin = group_gangs(pending)
+        rc, rm, rp = pack_pods(pods)
+        sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
+        idx, _, _, placed = self.engine.schedule_gangs(rc, rm, rp, sel, off, gmin)
+        out = []
+        for g in range(len(gmin)):
+            lo, hi = int(off[g]), int(off[g + 1])
+            gname = pods[lo].annotations.get(GROUP_NAME_ANNOTATION) or pods[lo].name
+            found = int(np.sum((idx[lo:hi] >= 0) | (idx[lo:hi] == L.GANG_REJECTED)))
+            rejected = found < int(gmin[g])
+            assert int(placed[g]) == (0 if rejected else found)
+            for pod, i in zip(pods[lo:hi], idx[lo:hi]):
+                if i == L.GANG_REJECTED:
+                    msg = (f"pod ({pod.name}) rejected with its gang ({gname}): {found} of {hi - lo} members placed, "
+                           f"{int(gmin[g])} needed")
+                    self.events.append(dict(reason="FailedScheduling", message=msg, type="Warning", involved=pod.name))
+                    out.append((pod, GangRejected(msg)))
+                elif i == L.NO_FIT:
+                    self.events.append(dict(reason="FailedScheduling", message=f"pod ({pod.name}) failed to fit in any node",
+                                            type="Warning", involved=pod.name))
+                    out.append((pod, FitError(f"Unable to schedule pod ({pod.name}) failed to fit in any node")))
+                elif i == L.NO_POSITIVE_SCORE:
+                    if rejected:
+                        self.events.append(dict(reason="FailedScheduling", type="Warning", involved=pod.name,
+                                                message=f"pod ({pod.name}) found no node with a positive score"))
+                    out.append((pod, NilNodeError(pod.name)))
+                else:
+                    node = self.nodes[int(i)]
+                    self.bind(pod, node)
+                    out.append((pod, node))
         return out
 
     def schedule_pod(self, pod: Pod, selector: Optional[int] = None):
