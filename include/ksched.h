@@ -247,6 +247,50 @@ int ksched_rank_merge(int32_t priority, int32_t nranks, int64_t m, int32_t k, co
                       const double *score_all, const uint8_t *reason_all, const int32_t *count_all,
                       const int32_t *feasible_all, int32_t *out_idx, double *out_score, uint8_t *out_reason,
                       int32_t *out_count, int32_t *out_feasible);
+/* ---- preemption dry run (added within ABI 6: probe with dlsym(lib, "ksched_preempt"), the version number did not move) ----
+ * kube-scheduler's default preemption (the PostFilter step) without PDBs and start times: for a pod that fits
+ * nowhere, which lower-priority bound pods would have to go, and on which node.  A build extension: the reference
+ * knows no priorities.
+ *
+ * ksched_load_bound: the table of bound pods, a snapshot the caller owns.  Pod t of the table (its TABLE INDEX, the
+ * name every answer uses) is bound to local node node_idx[t], holds (cpu[t], mem[t]) and one pod slot there -- what
+ * its commit subtracted from the node's row -- and has priority prio[t].  Call it after ksched_load_nodes.  nb == 0
+ * is a valid, empty table.  KSCHED_E_INVALID: a node index outside [0, n_local), or more than
+ * KSCHED_BOUND_MAX_PER_NODE pods on one node; KSCHED_E_NOMEM: the table could not be allocated (the context then
+ * holds no table).  The call changes no node row and nothing else the context holds.  ksched_load_nodes
+ * invalidates the table (ksched_preempt returns KSCHED_E_STATE until it is loaded again); schedule calls,
+ * ksched_apply_delta and ksched_restore_state leave it alone -- they move the rows, and keeping the table in step
+ * with them is the caller's business (FakeCluster.preempt_pod reloads it on every call).
+ *
+ * ksched_preempt: each of the m pods is evaluated on its own against the current (local) rows and the table.
+ * NOTHING is committed and nothing else a context holds changes -- ksched_rank's promise.  Sums are wrapping int64;
+ * fits is the scheduler's predicate, the label check included under opts.use_labels.  Per pod i and node j:
+ *   1. potential victims: the table's pods on j with prio < prio[i].  Importance order: priority descending, then
+ *      table index ascending (earlier = older = more important).
+ *   2. free = alloc[j] + sum of (cpu, mem, 1) over the potential victims.  !fits(req[i], free): j is no candidate.
+ *   3. reprieve: walk the potential victims, most important first.  fits(req[i], free - v): free -= v, v is
+ *      reprieved; otherwise v is a victim.
+ *   4. the node's key: (max victim prio, sum of (prio + 2^31) over the victims as int64, victim count); the max is
+ *      KSCHED_PREEMPT_NO_VICTIM_PRIO without a victim (pickOneNodeForPreemption's order).
+ * The chosen node is the candidate with the lexicographically smallest key, then the lowest global index: a node
+ * that fits already has no victim and wins.  Outputs per pod (any pointer may be NULL):
+ *   out_node       global node index, or KSCHED_NO_FIT when no node is a candidate (the next three are then 0,
+ *                  KSCHED_PREEMPT_NO_VICTIM_PRIO, 0 and the pod's victim row all -1)
+ *   out_nvictims   the chosen node's victim count, in full even above vcap
+ *   out_max_prio, out_sum_prio   the chosen key
+ *   out_candidates candidate nodes of this rank's shard
+ *   out_victims    m*vcap: out_victims[i * vcap + r] = table index of the chosen node's r-th victim in step 3's order,
+ *                  at most vcap of them, -1 past the end
+ * 1 <= vcap <= KSCHED_BOUND_MAX_PER_NODE; m >= 0 (large m is served in chunks with a bounded device workspace);
+ * selector may be NULL unless opts.use_labels.  The call waits for the context's stream first.  Multi-rank: the
+ * answer covers this rank's shard (ksched.dist.merge_preempt picks among the shards' answers). */
+#define KSCHED_BOUND_MAX_PER_NODE 1024
+#define KSCHED_PREEMPT_NO_VICTIM_PRIO INT32_MIN
+int ksched_load_bound(ksched_ctx *ctx, int64_t nb, const int32_t *node_idx, const int64_t *cpu, const int64_t *mem,
+                      const int32_t *prio);
+int ksched_preempt(ksched_ctx *ctx, int64_t m, const int64_t *req_cpu, const int64_t *req_mem, const int64_t *req_pods,
+                   const uint64_t *selector, const int32_t *prio, int32_t vcap, int32_t *out_node, int32_t *out_nvictims,
+                   int32_t *out_max_prio, int64_t *out_sum_prio, int32_t *out_candidates, int32_t *out_victims);
 /* Copies the current (local) node state back to the host. */
 int ksched_read_nodes(ksched_ctx *ctx, int64_t n, int64_t *alloc_cpu, int64_t *alloc_mem, int64_t *alloc_pods);
 /* Device-side snapshot / restore of the node state (bench: identical start state every step). */

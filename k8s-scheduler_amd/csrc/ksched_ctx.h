@@ -104,6 +104,9 @@ struct ksched_bufs {
     DevBuf<int32_t> gend, gplaced;        // ksched_schedule_gangs: ExactArgs::gang_end per pod, members bound per gang
     DevBuf<void> xws, xbuf;               // explain: workspace; counts + NO_FIT pod list, or one pod's state + counts
     DevBuf<void> rws;                     // ksched_rank: one chunk's pods, span lists and outputs (rank_geometry's bound)
+    DevBuf<int64_t> bcpu, bmem, boff;     // ksched_load_bound: the bound-pod table (BoundTable, ksched_preempt.h)
+    DevBuf<int32_t> bprio, btidx, bdepth, bseg;
+    DevBuf<void> vws;                     // ksched_preempt: one chunk's pods, span parts and outputs
     DevBuf<void> pws;                     // persistent pipeline: part lists, list / export rings, progress words, ...
     DevBuf<uint64_t> trace;               // KSCHED_PERSIST_TRACE: per-batch wall-clock stamps [rows][kTraceCols]
     DevBuf<uint64_t> trace_wg;            // KSCHED_TRACE_WG: per batch and score workgroup {start, arrival}
@@ -185,6 +188,7 @@ struct ksched_ctx {
     uint64_t sum_abs_req = 0;    // saturating sum of |request| over the staged pods
     uint64_t snap_max_abs_alloc = 0;  // max_abs_alloc of the save_state snapshot
     int64_t perm_n = -1;         // the node count d->perm was built for (-1: none; k_exact1 needs perm_n == n_local)
+    bool bound_valid = false;    // ksched_load_bound's table describes the loaded nodes (every load_nodes clears it)
     // pods
     int64_t p = 0;
     // batched workspace

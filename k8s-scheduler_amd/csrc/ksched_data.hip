@@ -3,12 +3,60 @@
 #include <cmath>
 #include <cstring>
 
+#include <new>
+
 #include "ksched_ctx.h"
+#include "ksched_preempt.h"
 #include "ksched_rank.h"
 
 using namespace ksched;
 
 static uint64_t uabs(int64_t v) { return v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v; }
+
+// The bound-pod table, grouped and laid out for the device (ksched_preempt.h: BoundTable).  A counting sort by node
+// keeps the table's order inside a node; reading a segment backwards and stable-sorting it by priority then gives
+// ascending importance (prio ascending, table index descending).
+bool ksched::build_bound_table(int64_t n, int64_t nb, const int32_t *node_idx, const int64_t *cpu, const int64_t *mem,
+                               const int32_t *prio, BoundTableHost *out, const char **why) {
+    const int64_t blocks = (n + 63) / 64;
+    out->seg.assign((size_t)n, 0);
+    for (int64_t t = 0; t < nb; ++t) {
+        if (node_idx[t] < 0 || node_idx[t] >= n) { *why = "node index out of range"; return false; }
+        if (++out->seg[(size_t)node_idx[t]] > kBoundMaxPerNode) { *why = "more than KSCHED_BOUND_MAX_PER_NODE pods on one node"; return false; }
+    }
+    std::vector<int64_t> start((size_t)n + 1, 0);  // the counting sort: node j's pods are order[start[j] .. start[j + 1])
+    for (int64_t j = 0; j < n; ++j) start[(size_t)j + 1] = start[(size_t)j] + out->seg[(size_t)j];
+    std::vector<int32_t> order((size_t)nb);
+    {
+        std::vector<int64_t> at(start.begin(), start.end() - 1);
+        for (int64_t t = 0; t < nb; ++t) order[(size_t)at[(size_t)node_idx[t]]++] = (int32_t)t;
+    }
+    out->off.assign((size_t)blocks, 0);
+    out->depth.assign((size_t)blocks, 0);
+    int64_t entries = 0;
+    for (int64_t b = 0; b < blocks; ++b) {
+        int32_t d = 0;
+        for (int64_t j = b * 64; j < std::min<int64_t>(n, b * 64 + 64); ++j) d = std::max(d, out->seg[(size_t)j]);
+        out->off[(size_t)b] = entries;
+        out->depth[(size_t)b] = d;
+        entries += (int64_t)d * 64;
+    }
+    out->cpu.assign((size_t)entries, 0);
+    out->mem.assign((size_t)entries, 0);
+    out->prio.assign((size_t)entries, INT32_MAX);  // padding: below no preemptor's priority
+    out->tidx.assign((size_t)entries, -1);
+    for (int64_t j = 0; j < n; ++j) {
+        int32_t *lo = order.data() + start[(size_t)j], *hi = order.data() + start[(size_t)j + 1];
+        std::reverse(lo, hi);  // table index descending ...
+        std::stable_sort(lo, hi, [&](int32_t x, int32_t y) { return prio[x] < prio[y]; });  // ... within a priority
+        const int64_t e0 = out->off[(size_t)(j >> 6)] + (j & 63);
+        for (int32_t *q = lo; q < hi; ++q) {
+            const size_t e = (size_t)(e0 + (int64_t)(q - lo) * 64);
+            out->cpu[e] = cpu[*q]; out->mem[e] = mem[*q]; out->prio[e] = prio[*q]; out->tidx[e] = *q;
+        }
+    }
+    return true;
+}
 
 extern "C" {
 
@@ -39,6 +87,7 @@ int ksched_load_nodes(ksched_ctx *c, int64_t n, const int64_t *ac, const int64_t
     HIPCHK(c, hipSetDevice(c->dev));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->perm_n = -1;  // first: whatever happens below, d->perm no longer describes the loaded nodes
+    c->bound_valid = false;  // ... and neither does the bound-pod table (ksched_load_bound)
     HIPCHK(c, c->d->nodes.reserve((size_t)n * sizeof(NodeRec)));
     c->d->snap.release();
     // in the stream of the kernels that read it (a legacy hipMemcpy from pageable memory may return before its DMA
@@ -408,6 +457,138 @@ int ksched_rank_merge(int32_t priority, int32_t nranks, int64_t m, int32_t k, co
             if (out_reason) out_reason[o] = 0;
         }
         if (out_feasible) out_feasible[i] = (int32_t)feas;
+    }
+    return KSCHED_OK;
+}
+
+// The bound-pod table of ksched_preempt: built on the host (build_bound_table), uploaded in the stream of the
+// kernels that read it.  Touches no node row; the context holds no table until the last copy has landed.
+int ksched_load_bound(ksched_ctx *c, int64_t nb, const int32_t *node_idx, const int64_t *cpu, const int64_t *mem,
+                      const int32_t *prio) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_bound before load_nodes");
+    static_assert(KSCHED_BOUND_MAX_PER_NODE == kBoundMaxPerNode, "segment bound");
+    if (nb < 0 || nb >= 0x7fffffff || (nb > 0 && (!node_idx || !cpu || !mem || !prio)))
+        return fail(c, KSCHED_E_INVALID, "load_bound: bad arguments");
+    BoundTableHost h;
+    const char *why = "";
+    try {
+        if (!build_bound_table(c->n_local, nb, node_idx, cpu, mem, prio, &h, &why))
+            return fail(c, KSCHED_E_INVALID, std::string("load_bound: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "load_bound: host allocation of the table failed");
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->bound_valid = false;
+    ksched_bufs &d = *c->d;
+    const size_t e = h.cpu.size(), nblk = h.off.size(), n = h.seg.size();
+    hipError_t r = d.bcpu.reserve(e * 8);
+    if (r == hipSuccess) r = d.bmem.reserve(e * 8);
+    if (r == hipSuccess) r = d.bprio.reserve(e * 4);
+    if (r == hipSuccess) r = d.btidx.reserve(e * 4);
+    if (r == hipSuccess) r = d.boff.reserve(nblk * 8);
+    if (r == hipSuccess) r = d.bdepth.reserve(nblk * 4);
+    if (r == hipSuccess) r = d.bseg.reserve(n * 4);
+    if (r != hipSuccess) {
+        (void)hipGetLastError();
+        if (r == hipErrorOutOfMemory) return fail(c, KSCHED_E_NOMEM, "load_bound: device allocation of the table failed");
+        return fail(c, KSCHED_E_DEVICE, std::string("load_bound: ") + hipGetErrorString(r));
+    }
+    auto up = [&](void *dst, const void *src, size_t bytes) {
+        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
+    };
+    HIPCHK(c, up(d.bcpu, h.cpu.data(), e * 8)); HIPCHK(c, up(d.bmem, h.mem.data(), e * 8));
+    HIPCHK(c, up(d.bprio, h.prio.data(), e * 4)); HIPCHK(c, up(d.btidx, h.tidx.data(), e * 4));
+    HIPCHK(c, up(d.boff, h.off.data(), nblk * 8)); HIPCHK(c, up(d.bdepth, h.depth.data(), nblk * 4));
+    HIPCHK(c, up(d.bseg, h.seg.data(), n * 4));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go away with this call
+    c->bound_valid = true;
+    return KSCHED_OK;
+}
+
+// Preemption dry run (ksched_preempt.hip).  As ksched_rank: its pods, span parts and outputs live in a workspace of its
+// own (d->vws), one chunk of kPreemptChunk pods at a time; nothing a schedule call left behind is touched.
+int ksched_preempt(ksched_ctx *c, int64_t m, const int64_t *rc, const int64_t *rm, const int64_t *rp, const uint64_t *sel,
+                   const int32_t *prio, int32_t vcap, int32_t *out_node, int32_t *out_nvictims, int32_t *out_max_prio,
+                   int64_t *out_sum_prio, int32_t *out_candidates, int32_t *out_victims) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "preempt before load_nodes");
+    if (vcap < 1 || vcap > KSCHED_BOUND_MAX_PER_NODE)
+        return fail(c, KSCHED_E_INVALID, "preempt: vcap must be in 1..KSCHED_BOUND_MAX_PER_NODE");
+    if (m < 0 || (m > 0 && (!rc || !rm || !rp || !prio))) return fail(c, KSCHED_E_INVALID, "preempt: bad arguments");
+    if (c->o.use_labels && m > 0 && !sel) return fail(c, KSCHED_E_INVALID, "preempt: use_labels needs selectors");
+    if (!c->bound_valid) return fail(c, KSCHED_E_STATE, "preempt: no bound-pod table (ksched_load_bound after every ksched_load_nodes)");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (m == 0) return KSCHED_OK;
+    const int64_t n = c->n_local;
+    if (n == 0) {  // an empty shard has no candidate
+        if (out_node) std::fill(out_node, out_node + m, KSCHED_NO_FIT);
+        if (out_nvictims) std::fill(out_nvictims, out_nvictims + m, 0);
+        if (out_max_prio) std::fill(out_max_prio, out_max_prio + m, KSCHED_PREEMPT_NO_VICTIM_PRIO);
+        if (out_sum_prio) std::fill(out_sum_prio, out_sum_prio + m, (int64_t)0);
+        if (out_candidates) std::fill(out_candidates, out_candidates + m, 0);
+        if (out_victims) std::fill(out_victims, out_victims + (size_t)m * vcap, -1);
+        return KSCHED_OK;
+    }
+    // the workspace of one chunk: pods | span parts | counts | outputs, each 256-byte aligned
+    const int64_t mc_max = std::min<int64_t>(m, kPreemptChunk);
+    size_t np = 0;  // span parts of the largest chunk: at most kPreemptGridWGs * kPreemptTile (preempt_geometry)
+    for (int64_t q : {mc_max, m % kPreemptChunk}) {  // the full chunk and the tail (fewer pods, more spans)
+        if (q <= 0) continue;
+        int32_t s; int64_t rows;
+        preempt_geometry(n, q, &s, &rows);
+        np = std::max(np, (size_t)q * (size_t)s);
+    }
+    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t q = (size_t)mc_max;
+    const size_t o_pods = 0, o_part = al(o_pods + q * 36), o_nc = al(o_part + np * sizeof(PreemptPart)),
+                 o_node = al(o_nc + np * 4), o_nv = al(o_node + q * 4), o_mx = al(o_nv + q * 4), o_sum = al(o_mx + q * 4),
+                 o_cand = al(o_sum + q * 8), o_vic = al(o_cand + q * 4), total = al(o_vic + q * (size_t)vcap * 4);
+    HIPCHK(c, c->d->vws.reserve(total));
+    char *w = static_cast<char *>(c->d->vws.p);
+    // the victims leave only when asked for: up to 4 MiB of the chunk's copy out
+    const size_t out_bytes = (out_victims ? total : o_vic) - o_node;
+    std::vector<char> stage(std::max(q * 36, out_bytes));  // host side of the chunk's two copies
+    const ksched_bufs &d = *c->d;
+    for (int64_t at = 0; at < m; at += kPreemptChunk) {
+        const int64_t mc = std::min<int64_t>(kPreemptChunk, m - at);
+        PreemptArgs a{};
+        a.nodes = d.nodes; a.n_local = n; a.node_offset = c->o.node_offset;
+        a.tb.cpu = d.bcpu; a.tb.mem = d.bmem; a.tb.prio = d.bprio; a.tb.tidx = d.btidx;
+        a.tb.off = d.boff; a.tb.depth = d.bdepth; a.tb.seg = d.bseg;
+        int64_t *dp = reinterpret_cast<int64_t *>(w + o_pods);
+        a.rc = dp; a.rm = dp + mc; a.rp = dp + 2 * mc; a.sel = reinterpret_cast<uint64_t *>(dp + 3 * mc);
+        a.prio = reinterpret_cast<int32_t *>(dp + 4 * mc);
+        a.m = (int32_t)mc; a.vcap = vcap;
+        preempt_geometry(n, mc, &a.spans, &a.span_rows);
+        if ((size_t)mc * a.spans > np) return fail(c, KSCHED_E_NOMEM, "preempt: workspace bound");  // (preempt_geometry's bound)
+        a.part = reinterpret_cast<PreemptPart *>(w + o_part); a.part_nc = reinterpret_cast<int32_t *>(w + o_nc);
+        a.out_node = reinterpret_cast<int32_t *>(w + o_node); a.out_nvictims = reinterpret_cast<int32_t *>(w + o_nv);
+        a.out_max_prio = reinterpret_cast<int32_t *>(w + o_mx); a.out_sum_prio = reinterpret_cast<int64_t *>(w + o_sum);
+        a.out_candidates = reinterpret_cast<int32_t *>(w + o_cand); a.out_victims = reinterpret_cast<int32_t *>(w + o_vic);
+        // one copy in and one copy out per chunk, in the stream of the kernels
+        int64_t *hp = reinterpret_cast<int64_t *>(stage.data());
+        std::memcpy(hp, rc + at, (size_t)mc * 8);
+        std::memcpy(hp + mc, rm + at, (size_t)mc * 8);
+        std::memcpy(hp + 2 * mc, rp + at, (size_t)mc * 8);
+        if (sel) std::memcpy(hp + 3 * mc, sel + at, (size_t)mc * 8);
+        else std::memset(hp + 3 * mc, 0, (size_t)mc * 8);
+        std::memcpy(hp + 4 * mc, prio + at, (size_t)mc * 4);
+        HIPCHK(c, hipMemcpyAsync(dp, hp, (size_t)mc * 36, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_preempt(c->o.use_labels != 0, a, c->stream));
+        // (a short chunk's victims are [mc][vcap] from o_vic: the copy covers them)
+        const size_t cp = out_victims ? (o_vic - o_node) + (size_t)mc * vcap * 4 : out_bytes;
+        HIPCHK(c, hipMemcpyAsync(stage.data(), w + o_node, cp, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // the next chunk reuses the workspace and the staging buffer
+        const char *ho = stage.data();  // the outputs, at their workspace offsets less o_node
+        if (out_node) std::memcpy(out_node + at, ho, (size_t)mc * 4);
+        if (out_nvictims) std::memcpy(out_nvictims + at, ho + (o_nv - o_node), (size_t)mc * 4);
+        if (out_max_prio) std::memcpy(out_max_prio + at, ho + (o_mx - o_node), (size_t)mc * 4);
+        if (out_sum_prio) std::memcpy(out_sum_prio + at, ho + (o_sum - o_node), (size_t)mc * 8);
+        if (out_candidates) std::memcpy(out_candidates + at, ho + (o_cand - o_node), (size_t)mc * 4);
+        if (out_victims) std::memcpy(out_victims + (size_t)at * vcap, ho + (o_vic - o_node), (size_t)mc * vcap * 4);
     }
     return KSCHED_OK;
 }

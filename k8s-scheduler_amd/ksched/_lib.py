@@ -34,6 +34,8 @@ REASON_FIT, REASON_CPU, REASON_MEMORY, REASON_POD, REASON_LABELS = 0, 1, 2, 3, 4
 NUM_REASONS = 5
 RANK_MAX = 64  # KSCHED_RANK_MAX: entries ksched_rank keeps per pod
 GANG_MAX = 1024  # KSCHED_GANG_MAX: members of one gang
+BOUND_MAX_PER_NODE = 1024  # KSCHED_BOUND_MAX_PER_NODE: bound pods of one node in ksched_load_bound's table
+PREEMPT_NO_VICTIM_PRIO = -(1 << 31)  # KSCHED_PREEMPT_NO_VICTIM_PRIO: the key's max priority without a victim
 XCHG_HANDLE_BYTES = 128
 # the reference's per-node failure text (anchor/predicate.go:135,140,145)
 REASON_TEXT = {REASON_CPU: "Insufficient CPU", REASON_MEMORY: "Insufficient Memory", REASON_POD: "Insufficient Pod",
@@ -103,6 +105,9 @@ SIGNATURES = [
     ("ksched_rank", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, C.c_int32, I32P, F64P, U8P, I32P, I32P]),
     ("ksched_rank_merge", C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, I32P, F64P, U8P, I32P, I32P,
                                     I32P, F64P, U8P, I32P, I32P]),
+    ("ksched_load_bound", C.c_int, [CTX, C.c_int64, I32P, I64P, I64P, I32P]),
+    ("ksched_preempt", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, I32P, C.c_int32, I32P, I32P, I32P, I64P,
+                                 I32P, I32P]),
     ("ksched_read_nodes", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P]),
     ("ksched_save_state", C.c_int, [CTX]),
     ("ksched_restore_state", C.c_int, [CTX]),

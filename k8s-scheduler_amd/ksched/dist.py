@@ -116,6 +116,24 @@ def merge_ranked(priority: int, shards):
     return oi, os_, orr, oc, of
 
 
+def merge_preempt(shards):
+    """The cluster's preemption answer from the node shards' (numpy, host only).  shards: one Engine.preempt() result
+    (node, nvictims, max_prio, sum_prio, candidates, victims) per rank, in rank order, for the same pods and vcap.
+    Per pod the shard with the smallest (max_prio, sum_prio, nvictims, node) among those with a candidate wins --
+    ksched_preempt's own order, nodes being global indices -- and `candidates` is the sum over the shards.  Returns the
+    same six arrays plus shard int32[m], the winning rank (-1: NO_FIT everywhere): the victims are that rank's row
+    as it stands, indices into the table that rank loaded."""
+    node, nv, mx, sm, cand, vic = (np.stack([np.asarray(s[j]) for s in shards]) for j in range(6))
+    m = node.shape[1]
+    none = node < 0
+    # lexsort: last key first; shards without a candidate sort behind every other
+    order = np.lexsort((np.where(none, np.iinfo(np.int32).max, node), nv, sm, mx, none), axis=0)
+    win = order[0]
+    at = np.arange(m)
+    shard = np.where(none[win, at], -1, win).astype(np.int32)
+    return (node[win, at], nv[win, at], mx[win, at], sm[win, at], cand.sum(axis=0).astype(np.int32), vic[win, at], shard)
+
+
 def gather_node_state(local_state, world: int):
     """Concatenate every rank's (cpu, mem, pods) node state in rank order (torch.distributed)."""
     import torch

@@ -207,6 +207,38 @@ class Engine:
                   "rank")
         return idx, score, reason, count, feas
 
+    def load_bound(self, node_idx, cpu, mem, prio):
+        """The bound-pod table of preempt() (ksched_load_bound): pod t is bound to local node node_idx[t], holds
+        (cpu[t], mem[t]) and one pod slot there and has priority prio[t].  A snapshot: load_nodes() invalidates it,
+        schedule calls and apply_delta() leave it alone."""
+        ix = np.ascontiguousarray(node_idx, dtype=np.int32)
+        bc, bm = _i64(cpu), _i64(mem)
+        bp = np.ascontiguousarray(prio, dtype=np.int32)
+        nb = ix.shape[0]
+        assert bc.shape[0] == nb and bm.shape[0] == nb and bp.shape[0] == nb
+        self._chk(L.lib().ksched_load_bound(self._ctx, nb, L.ptr(ix, C.c_int32), L.ptr(bc, C.c_int64),
+                                            L.ptr(bm, C.c_int64), L.ptr(bp, C.c_int32)), "load_bound")
+
+    def preempt(self, req_cpu, req_mem, req_pods, selector, prio, vcap: int = 16):
+        """Preemption dry run (ksched_preempt): for each pod, the node where the cheapest set of lower-priority bound
+        pods would have to go for it to fit, against the current node state and the load_bound() table; nothing is
+        committed.  Returns (node int32[m] (global index | NO_FIT), nvictims int32[m] (in full, even above vcap),
+        max_prio int32[m], sum_prio int64[m] (the chosen node's key), candidates int32[m], victims int32[m, vcap]
+        (table indices, most important first, -1 past the end))."""
+        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
+        m = rc.shape[0]
+        pr = np.ascontiguousarray(prio, dtype=np.int32)
+        assert rm.shape[0] == m and rp.shape[0] == m and pr.shape[0] == m
+        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
+        node = np.empty(m, np.int32); nv = np.empty(m, np.int32); mx = np.empty(m, np.int32)
+        sm = np.empty(m, np.int64); cand = np.empty(m, np.int32)
+        vic = np.empty((m, max(int(vcap), 0)), np.int32)
+        self._chk(L.lib().ksched_preempt(self._ctx, m, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64), L.ptr(rp, C.c_int64),
+                                         L.ptr(sel, C.c_uint64), L.ptr(pr, C.c_int32), int(vcap), L.ptr(node, C.c_int32),
+                                         L.ptr(nv, C.c_int32), L.ptr(mx, C.c_int32), L.ptr(sm, C.c_int64),
+                                         L.ptr(cand, C.c_int32), L.ptr(vic, C.c_int32)), "preempt")
+        return node, nv, mx, sm, cand, vic
+
     def read_nodes(self):
         ac = np.empty(self.n, np.int64); am = np.empty(self.n, np.int64); ap = np.empty(self.n, np.int64)
         self._chk(L.lib().ksched_read_nodes(self._ctx, self.n, L.ptr(ac, C.c_int64), L.ptr(am, C.c_int64),

@@ -53,6 +53,7 @@ class Pod:
     annotations: Dict[str, str] = dataclasses.field(default_factory=dict)
     uid: str = ""
     node_selector: Dict[str, str] = dataclasses.field(default_factory=dict)
+    priority: int = 0  # spec.priority (preemption; build extension, the reference knows no priorities)
 
 
 @dataclasses.dataclass
@@ -118,14 +119,14 @@ def node_from_kube(obj: dict) -> Node:
 
 def pod_from_kube(obj: dict) -> Pod:
     """One PodList item / watch event object (anchor/types.go:57-80): containers' resources.requests
-    (limits are ignored, anchor/predicate.go:73-77) and spec.nodeName."""
+    (limits are ignored, anchor/predicate.go:73-77) and spec.nodeName; spec.priority (absent: 0) for preemption."""
     md = obj.get("metadata") or {}
     sp = obj.get("spec") or {}
     conts = [Container(name=c.get("name", ""), requests=dict((c.get("resources") or {}).get("requests") or {}))
              for c in (sp.get("containers") or [])]
     return Pod(name=md.get("name", ""), containers=conts, node_name=sp.get("nodeName") or "",
                annotations=dict(md.get("annotations") or {}), uid=md.get("uid", ""),
-               node_selector=dict(sp.get("nodeSelector") or {}))
+               node_selector=dict(sp.get("nodeSelector") or {}), priority=int(sp.get("priority") or 0))
 
 
 def _strv(items):
@@ -354,6 +355,32 @@ class FakeCluster:
         idx, score, reason, count, _ = self.engine.rank(rc, rm, rp, sel, k=k)
         return [(self.nodes[int(idx[0, r])], float(score[0, r]), L.REASON_TEXT.get(int(reason[0, r])))
                 for r in range(int(count[0]))]
+
+    def preempt_pod(self, pod: Pod, evict: bool = False, selector: Optional[int] = None):
+        """kube-scheduler's default preemption for one pod that fits nowhere (ksched_preempt): the node on which the
+        cheapest set of lower-priority bound pods would have to go, and those pods, most important first, as
+        (Node, [victim Pods]); FitError when no node is a candidate.  The bound-pod table is reloaded from self.pods
+        on every call.  evict=True also removes the victims -- through the DELETED path of handle_event, which gives
+        their resources back to the node -- and appends one Preempted event per victim.  The pod is never bound: it
+        is scheduled by the next schedule call, as kube-scheduler's nominated pods are."""
+        bound = [p for p in self.pods if p.node_name]
+        bc, bm, _ = pack_pods(bound)
+        self.engine.load_bound([self._node_index(p.node_name) for p in bound], bc, bm, [p.priority for p in bound])
+        rc, rm, rp = pack_pods([pod])
+        if selector is None:
+            selector = self.selector_of(pod)
+        sel = np.asarray([selector], dtype=np.uint64) if self.use_labels else None
+        node, nv, _, _, _, vic = self.engine.preempt(rc, rm, rp, sel, [pod.priority], vcap=L.BOUND_MAX_PER_NODE)
+        if node[0] == L.NO_FIT:
+            raise FitError(f"Unable to schedule pod ({pod.name}): no node fits it even without its lower-priority pods")
+        target = self.nodes[int(node[0])]
+        victims = [bound[int(t)] for t in vic[0, :int(nv[0])]]
+        if evict:
+            for v in victims:
+                self.handle_event(dict(type="DELETED", object=dict(metadata=dict(name=v.name))))
+                self.events.append(dict(reason="Preempted", type="Normal", involved=v.name,
+                                        message=f"Preempted by pod ({pod.name}) on node {target.name}"))
+        return target, victims
 
     def bind(self, pod: Pod, node: Node) -> None:
         """POST Binding + Scheduled event (anchor/schedule.go:200-261), in memory."""
