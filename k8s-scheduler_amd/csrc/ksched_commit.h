@@ -23,6 +23,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #ifndef KSCHED_XCHG_DEBUG
 #define KSCHED_XCHG_DEBUG 0  // the exchange diagnostics of tests/diag/xchg_ring_experiment.py (a separate build)
 #endif
@@ -97,6 +99,9 @@ struct SpcSmem {
     float *thr;       // [64] per pod: a touched node's key screens below this -> it cannot matter (kSkipKey)
     // persistent commit: the slots of the older export (batch b - 2) are keyed by the merger workgroups
     int16_t *x2s;     // [64] slot of that export's entry e (-1: the node is also in export(b - 1): no slot)
+    float *rb2;       // [64] per pod, once the batch tracks it (trk): an upper bound of the real keys of every confirmed
+                      // slot but the pod's best one (rounded up to f32; in LDS: the kernel is at its register limit).
+                      // Aliases dfacc, which is dead once the wave-0 state has read it
 };
 
 __device__ __forceinline__ uint32_t spc_hash(int32_t idx) {
@@ -431,6 +436,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
         m.own = reinterpret_cast<int32_t *>(m.pbk);
         m.s0 = reinterpret_cast<int64_t *>(m.D);
         m.iy = reinterpret_cast<double *>(m.GS);
+        m.rb2 = reinterpret_cast<float *>(m.dfacc);
     }
     const int nb = (int)((A.pods.p - p0 < A.B) ? A.pods.p - p0 : A.B);  // <= 64 (host-checked)
     // every wave: lane = pod j of the batch (lanes >= nb carry a zero request and are never read).
@@ -707,6 +713,16 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
     int32_t fcc = 0;          // predicate count with the confirmed commits
     double rbk = -__builtin_inf();  // best confirmed touched slot (key, node, slot)
     int32_t rbi = kNoIdx, rbs = -1;
+    // SpcSmem::rb2, an upper bound of every OTHER confirmed slot's real key: while the holder's key stays above it, a
+    // holder that got worse is still the best and no rescan is needed.  Kept only once the batch tracks it (trk: from
+    // its first rescan that found the holder still the best; +inf then, until the lane's next rescan has computed
+    // the second-best key).  Like rbk it means something only for the lanes after the pod being resolved (lanes > f);
+    // the fold of the confirmed guesses is skipped with rbk's when f == nb, where the batch ends.
+    // Built into the all-node resource kernels only (c4's and c3's: on c4 1,901 of 4,186 steps with a worsened holder
+    // keep it).  The feasible-domain and best-price kernels keep no holder that way (c5hc: 1 of 452 steps), and
+    // any addition to this function costs them 0.3-3 % through register allocation alone.
+    constexpr bool RB2 = COH && PRIO == kPrioResource && DOM == kDomAll;
+    bool trk = false;  // wave 0, uniform; never set without RB2, which compiles everything under it away
     int cv = 0, cut = 0;      // list length, cut flag
     int32_t my_idx = 0, my_feas = 0;
     int32_t my_src = 0;  // diagnostics: the path that set my_idx (reported with device error 14)
@@ -787,6 +803,49 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
         }
         if (A.dbg && lane == 0) atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[22]), 1ull);
         (void)nrk;
+    };
+    // wave 0, the lanes whose holder lost: the lane's best confirmed slot again, over its whole row.  Four slots' loads
+    // in flight, two running maxima (better() is a total order on distinct nodes, so the fold order does not change
+    // the result).  top2: also the second-best key, rounded up, into SpcSmem::rb2 -- q0 / q1 are the best key each chain passed over
+    // (NaN and -inf never rise above them).
+    auto rescan_row = [&](auto top2) {
+        constexpr bool T2 = decltype(top2)::value;
+        double k0 = -__builtin_inf(), k1 = -__builtin_inf();
+        double q0 = -__builtin_inf(), q1 = -__builtin_inf();
+        int32_t i0 = kNoIdx, i1 = kNoIdx;
+        int s0 = -1, s1 = -1;
+        int t = 0;
+        for (; t + 4 <= nT; t += 4) {
+            double v[4];
+            int32_t x[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { v[u] = Srow[t + u]; x[u] = m.ti[t + u]; }
+#pragma unroll
+            for (int u = 0; u < 4; u += 2) {
+                const bool u0 = v[u] != -__builtin_inf() && better(v[u], x[u], k0, i0);
+                if constexpr (T2) { const double o0 = u0 ? k0 : v[u]; q0 = o0 > q0 ? o0 : q0; }
+                if (u0) { k0 = v[u]; i0 = x[u]; s0 = t + u; }
+                const bool u1 = v[u + 1] != -__builtin_inf() && better(v[u + 1], x[u + 1], k1, i1);
+                if constexpr (T2) { const double o1 = u1 ? k1 : v[u + 1]; q1 = o1 > q1 ? o1 : q1; }
+                if (u1) { k1 = v[u + 1]; i1 = x[u + 1]; s1 = t + u + 1; }
+            }
+        }
+        for (; t < nT; ++t) {
+            const double v = Srow[t];
+            const int32_t x = m.ti[t];
+            const bool u0 = v != -__builtin_inf() && better(v, x, k0, i0);
+            if constexpr (T2) { const double o0 = u0 ? k0 : v; q0 = o0 > q0 ? o0 : q0; }
+            if (u0) { k0 = v; i0 = x; s0 = t; }
+        }
+        q0 = q1 > q0 ? q1 : q0;
+        if (k1 != -__builtin_inf() && better(k1, i1, k0, i0)) {
+            q0 = k0 > q0 ? k0 : q0;
+            k0 = k1; i0 = i1; s0 = s1;
+        } else {
+            q0 = k1 > q0 ? k1 : q0;
+        }
+        rbk = k0; rbi = i0; rbs = s0;
+        if constexpr (T2) m.rb2[lane] = __double2float_ru(q0);
     };
     int c = 0;
     if (COH && tid == 0 && A.trace_row) A.trace_row[25] = wall_clock64();  // the rounds start
@@ -1003,6 +1062,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             nT += ncg;
             if (f < nb) {
                 // bring the confirmed state of the pods still to come up to date with [c, f)
+                float b2 = trk ? m.rb2[lane] : 0.0f;
                 for (int k = c; k < f; ++k) {
                     const int32_t g = __builtin_amdgcn_readlane(my_g, k);
                     if (g < 0) continue;
@@ -1010,8 +1070,13 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                     const double v = Srow[s];
                     fcc += m.D[k * 64 + lane];
                     const bool up = v != -__builtin_inf() && better(v, g, rbk, rbi);
+                    if (trk) {
+                        const double o = up ? rbk : v;  // the key that is not (or no longer) the best
+                        b2 = o > (double)b2 ? __double2float_ru(o) : b2;  // (a skipped slot's NaN leaves the bound as it is)
+                    }
                     rbk = up ? v : rbk; rbi = up ? g : rbi; rbs = up ? s : rbs;
                 }
+                if (trk) m.rb2[lane] = b2;
             }
             if (f < cend) {
                 ++nfail;
@@ -1176,38 +1241,49 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                             x.cur[0] = n0; x.cur[1] = n1; x.cur[2] = n2;
                         }
                         lds_order();
-                        // running best: a better value takes over; a holder that got worse forces a rescan
+                        // running best: a better value takes over; a holder that got worse stays the best while its
+                        // key is above every other slot's (rb2, once the batch tracks it), and forces a rescan
+                        // otherwise (a tie with the bound included)
                         const bool up = kv != -__builtin_inf() && better(kv, wi, rbk, rbi);
-                        const bool rescan = !up && rbs == s;
-                        rbk = up ? kv : rbk; rbi = up ? wi : rbi; rbs = up ? s : rbs;
-                        if (__ballot(rescan)) {
-                            if (rescan) {
-                                // four slots' loads in flight, two running maxima (better() is a total order on
-                                // distinct nodes, so the fold order does not change the result)
-                                double k0 = -__builtin_inf(), k1 = -__builtin_inf();
-                                int32_t i0 = kNoIdx, i1 = kNoIdx;
-                                int s0 = -1, s1 = -1;
-                                int t = 0;
-                                for (; t + 4 <= nT; t += 4) {
-                                    double v[4];
-                                    int32_t x[4];
-#pragma unroll
-                                    for (int u = 0; u < 4; ++u) { v[u] = Srow[t + u]; x[u] = m.ti[t + u]; }
-#pragma unroll
-                                    for (int u = 0; u < 4; u += 2) {
-                                        if (v[u] != -__builtin_inf() && better(v[u], x[u], k0, i0)) { k0 = v[u]; i0 = x[u]; s0 = t + u; }
-                                        if (v[u + 1] != -__builtin_inf() && better(v[u + 1], x[u + 1], k1, i1)) {
-                                            k1 = v[u + 1]; i1 = x[u + 1]; s1 = t + u + 1;
-                                        }
-                                    }
+                        const bool hold = rbs == s;
+                        const bool worse = !up && hold;
+                        bool keep = false;
+                        if (trk) {
+                            const float b2 = m.rb2[lane];
+                            keep = worse && kv > (double)b2;
+                            const double o = up ? rbk : kv;
+                            if (!hold && o > (double)b2) m.rb2[lane] = __double2float_ru(o);
+                        }
+                        const bool rescan = worse && !keep;
+                        rbk = (up || keep) ? kv : rbk; rbi = up ? wi : rbi; rbs = up ? s : rbs;
+                        const bool anyr = __ballot(rescan) != 0;
+                        const bool anyw = RB2 && __ballot(worse) != 0;
+                        if (RB2 && A.dbg && lane == 0 && anyw) {  // diagnostics: steps with a worsened holder / all kept
+                            atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[23]), 1ull);
+                            if (!anyr) atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[24]), 1ull);
+                        }
+                        if (anyr) {
+                            const uint64_t tr0 = RB2 && dbg ? __builtin_amdgcn_s_memtime() : 0;
+                            const bool trk_was = trk;
+                            if (trk) {
+                                if (rescan) rescan_row(std::true_type{});
+                            } else {
+                                if (rescan) rescan_row(std::false_type{});
+                                // a rescan that found its holder still the best was for nothing: pods follow one
+                                // node here, and the rest of the batch tracks rb2 (every lane's is +inf up to now)
+                                if constexpr (RB2) {
+                                    trk = __ballot(rescan && rbs == s) != 0;
+                                    if (trk) m.rb2[lane] = __builtin_inff();
                                 }
-                                for (; t < nT; ++t) {
-                                    const double v = Srow[t];
-                                    const int32_t x = m.ti[t];
-                                    if (v != -__builtin_inf() && better(v, x, k0, i0)) { k0 = v; i0 = x; s0 = t; }
+                            }
+                            if (RB2 && dbg) {  // diagnostics: rescans and their cycles, plain / with the second-best key
+                                const uint64_t dt = __builtin_amdgcn_s_memtime() - tr0;
+                                if (lane == 0) {
+                                    const int o = trk_was ? 27 : 25;
+                                    atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[o]), 1ull);
+                                    atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[o + 1]), (unsigned long long)dt);
+                                    if (A.trace_row) A.trace_row[29] += dt;  // trace_dist.py's rescan column
                                 }
-                                if (k1 != -__builtin_inf() && better(k1, i1, k0, i0)) { k0 = k1; i0 = i1; s0 = s1; }
-                                rbk = k0; rbi = i0; rbs = s0;
                             }
                         }
                     }

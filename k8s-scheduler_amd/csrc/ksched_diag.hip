@@ -113,6 +113,11 @@ void print_persist_trace(ksched_ctx *c) {
                     (long long)hd[14], (double)hd[12] / hd[14], (double)hd[5] / std::max<int64_t>(1, hd[12]),
                     (long long)hd[13], (double)hd[6] / hd[14], (double)hd[9] / hd[14] / 11.0, (double)hd[7] / hd[14], (double)hd[10] / hd[14], (double)hd[11] / hd[14], (double)hd[15] / hd[14], (double)hd[0] / hd[14],
                     (double)hd[1] / hd[14], (double)hd[2] / hd[14], (double)hd[3] / hd[14], (double)hd[4] / hd[14]);
+        if (hd[14])  // a step whose commit made some lane's best touched slot worse rescanned before the rb2 bound
+            fprintf(stderr, "persist commit rescans: steps with a worsened holder %lld, every holder kept %lld | plain rescans "
+                    "%lld, %.0f cycles each | with the second-best key %lld, %.0f cycles each\n", (long long)hd[23],
+                    (long long)hd[24], (long long)hd[25], (double)hd[26] / std::max<int64_t>(1, hd[25]), (long long)hd[27],
+                    (double)hd[28] / std::max<int64_t>(1, hd[27]));
     }
     if (c->d->mdbg) {
         int64_t hm[8];
