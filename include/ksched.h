@@ -339,6 +339,65 @@ int ksched_schedule_gangs(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, co
                           const int32_t *gang_min, int32_t *out_idx, double *out_score, int32_t *out_feasible,
                           int32_t *out_gang_placed);
 
+/* ---- topology spread (added within ABI 6: probe with dlsym(lib, "ksched_schedule_spread"); the version number did not move) ----
+ * Pod topology spread constraints (topologySpreadConstraints with whenUnsatisfiable: DoNotSchedule) over ONE topology
+ * key, resolved by ONE launch of the exact kernel whatever opts.mode says (stats.pipeline == KSCHED_PIPE_EXACT,
+ * stats.pair_evals == p * n).  A build extension: the reference knows no constraints.
+ *
+ * The table (ksched_load_spread, after ksched_load_nodes): n_domains = D domains of the key and n_groups = S groups.
+ *   node_domain[j] in [0, D): node j's domain (its zone; its own index for hostname spread); -1: the node does not
+ *                  carry the key
+ *   a group        the pods one constraint's label selector matches
+ *   counts[s*D+d]  the number of such pods already bound in domain d (NULL: all zero)
+ *   max_skew[s]    >= 1
+ * Pods: spread_group[i] in [-1, S), -1: the pod belongs to no group.  spread_enforce[i] != 0 (NULL: every pod): the
+ * pod must satisfy its group's constraint; == 0: the pod only counts -- it matches the selector but carries no
+ * constraint itself.  The flag is ignored where the group is -1.
+ *
+ * Per pod i, in order, with s its group, e whether it enforces, and minc = min over d in [0, D) of counts[s][d]:
+ *   eligible(j) = fits(j) && (!e || (node_domain[j] >= 0 && counts[s][node_domain[j]] + 1 - minc <= max_skew[s]))
+ * fits is the scheduler's predicate, with the label check under opts.use_labels; this is kube-scheduler's
+ * PodTopologySpread filter with selfMatch = 1.  Everything else is ksched_schedule in exact mode with eligible in the
+ * place of fits: out_feasible counts eligible nodes, zero eligible nodes is KSCHED_NO_FIT, the key, the tie-break and
+ * the commit alloc -= (req_cpu, req_mem, 1) are unchanged.  So the constraint joins the predicate exactly as labels
+ * do: under KSCHED_DOMAIN_ALL an ineligible node can still win the argmax, as in the reference; callers who want
+ * enforcement use KSCHED_DOMAIN_FEASIBLE, or best-price, which always ranges over feasible nodes.  If the pod is
+ * placed on w, s >= 0 and node_domain[w] >= 0: counts[s][node_domain[w]] += 1, whether or not the pod enforces.
+ *
+ * State: the counts live in the context and carry over from call to call; ksched_read_spread returns them.
+ * ksched_load_nodes invalidates the table (ksched_schedule_spread and ksched_read_spread return KSCHED_E_STATE until
+ * it is loaded again); ksched_apply_delta and ksched_save_state / ksched_restore_state leave the counts alone --
+ * keeping them in step is the caller's business, as with ksched_load_bound (FakeCluster.schedule_spread reloads the
+ * table on every call).  ksched_schedule, ksched_schedule_gangs, ksched_rank, ksched_explain* and ksched_preempt
+ * neither read nor move the table.  After ksched_schedule_spread, ksched_explain_batch / ksched_explain_pod return
+ * KSCHED_E_STATE: they know no spread reason (KSCHED_NUM_REASONS did not change).
+ *
+ * KSCHED_E_INVALID (nothing changed; a table loaded earlier survives): D or S < 1 or above the caps, S * D >
+ * KSCHED_SPREAD_MAX_CELLS, a node domain outside [-1, D), a domain id in [0, D) that no node carries (the minimum
+ * ranges over all D with no mask: compact the ids), max_skew < 1, a count outside [0, 2^30], spread_group[i] outside
+ * [-1, S), p >= 2^30, opts.nranks > 1.
+ *
+ * Out of scope: ScheduleAnyway scoring; several constraints or topology keys per pod; minDomains;
+ * nodeAffinityPolicy / nodeTaintsPolicy (the minimum ranges over all domains, which is k8s's Ignore); a spread reason
+ * in the explain calls; multi-rank; the batched pipeline.
+ *
+ * Worked example (best-price, feasible domain): nodes n0 (zone A, price 0.1), n1 (A, 0.2), n2 (B, 0.5), all with ample
+ * room; one group with max_skew 1 and counts 0; four enforcing pods.  Pod 0 sees A 0, B 0: every node is eligible, the
+ * cheapest is n0 (A 1, B 0).  Pod 1: a pod in A would make the skew 2, only n2 is eligible (A 1, B 1).  Pod 2: as pod
+ * 0, n0 (A 2, B 1).  Pod 3: n2.  out_idx = {0, 2, 0, 2}, out_feasible = {3, 1, 3, 1}, final counts A 2, B 2.
+ * ksched_schedule on the same input gives {0, 0, 0, 0}. */
+#define KSCHED_SPREAD_MAX_DOMAINS 1024
+#define KSCHED_SPREAD_MAX_GROUPS  64
+#define KSCHED_SPREAD_MAX_CELLS   4096      /* n_groups * n_domains: the per-workgroup LDS table, 16 KiB */
+int ksched_load_spread(ksched_ctx *ctx, int32_t n_domains, const int32_t *node_domain /* n_local */,
+                       int32_t n_groups, const int32_t *max_skew /* n_groups */,
+                       const int32_t *counts /* n_groups * n_domains, NULL = zeros */);
+int ksched_read_spread(ksched_ctx *ctx, int32_t *out_counts /* n_groups * n_domains */);
+int ksched_schedule_spread(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,
+                           const int64_t *req_pods, const uint64_t *selector, const int32_t *spread_group /* p */,
+                           const uint8_t *spread_enforce /* p, NULL = all 1 */, int32_t *out_idx, double *out_score,
+                           int32_t *out_feasible);
+
 /* Same, in two halves, with the pods staged in HBM: upload once, run many times (bench). */
 int ksched_upload_pods(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,
                        const int64_t *req_pods, const uint64_t *selector);

@@ -8,6 +8,7 @@
 #include "ksched_ctx.h"
 #include "ksched_preempt.h"
 #include "ksched_rank.h"
+#include "ksched_spread.h"
 
 using namespace ksched;
 
@@ -88,6 +89,7 @@ int ksched_load_nodes(ksched_ctx *c, int64_t n, const int64_t *ac, const int64_t
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->perm_n = -1;  // first: whatever happens below, d->perm no longer describes the loaded nodes
     c->bound_valid = false;  // ... and neither does the bound-pod table (ksched_load_bound)
+    c->spread_D = c->spread_S = 0;  // ... nor the spread table (ksched_load_spread)
     HIPCHK(c, c->d->nodes.reserve((size_t)n * sizeof(NodeRec)));
     c->d->snap.release();
     // in the stream of the kernels that read it (a legacy hipMemcpy from pageable memory may return before its DMA
@@ -504,6 +506,47 @@ int ksched_load_bound(ksched_ctx *c, int64_t nb, const int32_t *node_idx, const 
     HIPCHK(c, up(d.bseg, h.seg.data(), n * 4));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go away with this call
     c->bound_valid = true;
+    return KSCHED_OK;
+}
+
+// The spread table of ksched_schedule_spread: checked on the host (ksched_spread.h) before anything is allocated or
+// staged, then uploaded in the stream of the kernel that reads it.  Touches no node row; the context holds the new
+// table only once the last copy has landed, and the earlier one until the checks have passed.
+int ksched_load_spread(ksched_ctx *c, int32_t n_domains, const int32_t *node_domain, int32_t n_groups,
+                       const int32_t *max_skew, const int32_t *counts) {
+    if (!c) return KSCHED_E_INVALID;
+    static_assert(KSCHED_SPREAD_MAX_DOMAINS == kSpreadMaxDomains && KSCHED_SPREAD_MAX_GROUPS == kSpreadMaxGroups &&
+                  KSCHED_SPREAD_MAX_CELLS == kSpreadMaxCells, "spread constants");
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_spread before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "load_spread: spread scheduling is single-GPU (the exact kernel)");
+    try {
+        if (const char *why = spread_check_table(c->n_local, n_domains, node_domain, n_groups, max_skew, counts))
+            return fail(c, KSCHED_E_INVALID, std::string("load_spread: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "load_spread: host allocation failed");
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->spread_D = c->spread_S = 0;
+    ksched_bufs &d = *c->d;
+    const size_t n = (size_t)c->n_local, cells = (size_t)n_domains * (size_t)n_groups;
+    HIPCHK(c, d.sdom.reserve(n * 4)); HIPCHK(c, d.scnt.reserve(cells * 4)); HIPCHK(c, d.sskew.reserve((size_t)n_groups * 4));
+    if (n > 0) HIPCHK(c, hipMemcpyAsync(d.sdom, node_domain, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d.sskew, max_skew, (size_t)n_groups * 4, hipMemcpyHostToDevice, c->stream));
+    if (counts) HIPCHK(c, hipMemcpyAsync(d.scnt, counts, cells * 4, hipMemcpyHostToDevice, c->stream));
+    else HIPCHK(c, hipMemsetAsync(d.scnt, 0, cells * 4, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's arrays are free again
+    c->spread_D = n_domains; c->spread_S = n_groups;
+    return KSCHED_OK;
+}
+
+int ksched_read_spread(ksched_ctx *c, int32_t *out_counts) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->spread_S == 0) return fail(c, KSCHED_E_STATE, "read_spread: no spread table (ksched_load_spread after every ksched_load_nodes)");
+    if (!out_counts) return fail(c, KSCHED_E_INVALID, "read_spread: out_counts is NULL");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out_counts, c->d->scnt, (size_t)c->spread_D * (size_t)c->spread_S * 4, hipMemcpyDeviceToHost));
     return KSCHED_OK;
 }
 

@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "ksched_ctx.h"
+#include "ksched_spread.h"
 
 using namespace ksched;
 
@@ -463,8 +464,11 @@ int enqueue_persistent(ksched_ctx *c) {
 }
 
 // gang: the run of ksched_schedule_gangs (the staged gangs in d->gend) -- always k_exact<GANG>, the
-// multi-slot kernel, under the same geometry and launch rule as a plain exact run
-int enqueue_exact(ksched_ctx *c, bool gang) {
+// multi-slot kernel, under the same geometry and launch rule as a plain exact run; spread: the run of
+// ksched_schedule_spread (the staged words in d->sword, the context's table) -- always k_exact<SPREAD>, likewise
+enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2 };
+int enqueue_exact(ksched_ctx *c, ExactRun run) {
+    const bool gang = run == kRunGang, spread = run == kRunSpread;
     if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "exact mode is single-GPU; use batched mode across ranks");
     const int64_t n = c->n_local;
     // the whole node set in ONE workgroup's registers (k_exact1): no cross-workgroup exchange per pod
@@ -475,7 +479,7 @@ int enqueue_exact(ksched_ctx *c, bool gang) {
     a.pods = PodArgs{c->d->rc, c->d->rm, c->d->rp, c->d->sel, c->p};
     a.out = OutArgs{c->d->oidx, c->d->osc, c->d->ofeas};
     a.err = c->d->err;
-    if (!gang && c->o.exact_wgs <= 1 && n > 0 && n <= (int64_t)kExact1Block * max1 && (!price || c->perm_n == n)) {
+    if (!gang && !spread && c->o.exact_wgs <= 1 && n > 0 && n <= (int64_t)kExact1Block * max1 && (!price || c->perm_n == n)) {
         int bs = kExact1Block;
         if (price && c->diag.exact1_bs == 512 && n <= 5120) bs = 512;
         if (price && c->diag.exact1_bs == 256 && n <= 5120) bs = 256;
@@ -519,6 +523,11 @@ int enqueue_exact(ksched_ctx *c, bool gang) {
         a.gang_end = c->d->gend; a.gang_placed = c->d->gplaced;
         HIPCHK(c, launch_exact_gang(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
                                     G > 1 && !c->diag.plain_launch, c->stream));
+    } else if (spread) {
+        a.sp_dom = c->d->sdom; a.sp_counts = c->d->scnt; a.sp_skew = c->d->sskew;
+        a.sp_D = c->spread_D; a.sp_S = c->spread_S; a.sp_word = c->d->sword;
+        HIPCHK(c, launch_exact_spread(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
+                                      G > 1 && !c->diag.plain_launch, c->stream));
     } else {
         HIPCHK(c, launch_exact(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
                                G > 1 && !c->diag.plain_launch, c->stream));
@@ -625,8 +634,10 @@ int ksched_destroy(ksched_ctx *c) {
 
 const char *ksched_last_error(const ksched_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
-// ksched_run, or (gang) the run of ksched_schedule_gangs: the exact kernel over the staged gangs whatever opts.mode
-static int run_impl(ksched_ctx *c, bool gang) {
+// ksched_run, or the run of ksched_schedule_gangs / ksched_schedule_spread: the exact kernel over the staged gangs /
+// spread words whatever opts.mode
+static int run_impl(ksched_ctx *c, ExactRun run) {
+    const bool gang = run == kRunGang;
     if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "run before load_nodes");
     if (c->o.nranks > 1 && !c->comm && !c->group && !c->xchg_ready)
         return fail(c, KSCHED_E_STATE, "run: multi-rank context without ksched_set_comm / ksched_set_group / "
@@ -639,7 +650,7 @@ static int run_impl(ksched_ctx *c, bool gang) {
     c->st.pods = c->p;
     int mode = c->o.mode;
     if (mode == KSCHED_MODE_AUTO) mode = c->o.nranks > 1 ? KSCHED_MODE_BATCHED : KSCHED_MODE_EXACT;
-    if (gang) mode = KSCHED_MODE_EXACT;
+    if (run != kRunPlain) mode = KSCHED_MODE_EXACT;
     c->xchg_run = c->xchg_ready && mode == KSCHED_MODE_BATCHED && c->p > 0;
     // a multi-rank batched call needs a transport: the device exchange, an RCCL communicator or a rank group
     // (never a rank committing from its own shard alone)
@@ -651,7 +662,7 @@ static int run_impl(ksched_ctx *c, bool gang) {
     if (c->p > 0) {
         c->persist_stats = false;
         if (mode == KSCHED_MODE_EXACT) {
-            r = enqueue_exact(c, gang);
+            r = enqueue_exact(c, run);
             c->st.pipeline = KSCHED_PIPE_EXACT;
         } else {
             r = enqueue_persistent(c);
@@ -673,13 +684,14 @@ static int run_impl(ksched_ctx *c, bool gang) {
     // FAST53 bound true of the state the NEXT call starts from
     if (r == KSCHED_OK) c->max_abs_alloc = sat_add(c->max_abs_alloc, c->sum_abs_req);
     // (a rolled-back gang leaves no final placements for ksched_explain_batch to rebuild a pod's state from)
-    c->explain_valid = r == KSCHED_OK && !gang;
+    // (and the explain calls know no spread reason)
+    c->explain_valid = r == KSCHED_OK && !gang && run != kRunSpread;
     return r;
 }
 
 int ksched_run(ksched_ctx *c) {
     if (!c) return KSCHED_E_INVALID;
-    return run_impl(c, false);
+    return run_impl(c, kRunPlain);
 }
 
 static int sync_impl(ksched_ctx *c) {
@@ -806,7 +818,7 @@ int ksched_schedule_gangs(ksched_ctx *c, int64_t p, const int64_t *rc, const int
     // in the stream of the kernel that reads it, finished before `gend` goes (ksched_upload_pods)
     if (p > 0) HIPCHK(c, hipMemcpyAsync(c->d->gend, gend.data(), (size_t)p * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((r = run_impl(c, true)) != KSCHED_OK) { ksched_sync(c); return r; }
+    if ((r = run_impl(c, kRunGang)) != KSCHED_OK) { ksched_sync(c); return r; }
     if ((r = ksched_sync(c)) != KSCHED_OK) return r;
     if ((r = ksched_download_results(c, p, oi, os, of)) != KSCHED_OK) return r;
     std::vector<int32_t> gp(ng);
@@ -815,6 +827,33 @@ int ksched_schedule_gangs(ksched_ctx *c, int64_t p, const int64_t *rc, const int
     for (int32_t v : gp) c->st.placed += v;
     if (out_gang_placed && ng > 0) std::memcpy(out_gang_placed, gp.data(), ng * 4);
     return KSCHED_OK;
+}
+
+int ksched_schedule_spread(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                           const uint64_t *sel, const int32_t *spread_group, const uint8_t *spread_enforce, int32_t *oi,
+                           double *os, int32_t *of) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_spread before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_spread is single-GPU (the exact kernel)");
+    if (c->spread_S == 0)
+        return fail(c, KSCHED_E_STATE, "schedule_spread: no spread table (ksched_load_spread after every ksched_load_nodes)");
+    // every group is checked, and the per-pod words are packed, before anything is written or allocated
+    std::vector<int32_t> words;
+    try {
+        if (const char *why = spread_pack_words(p, c->spread_S, spread_group, spread_enforce, &words))
+            return fail(c, KSCHED_E_INVALID, std::string("schedule_spread: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "schedule_spread: host staging buffer");
+    }
+    int r = ksched_upload_pods(c, p, rc, rm, rp, sel);
+    if (r != KSCHED_OK) return r;
+    HIPCHK(c, c->d->sword.reserve((size_t)p * 4));
+    // in the stream of the kernel that reads it, finished before `words` goes (ksched_upload_pods)
+    if (p > 0) HIPCHK(c, hipMemcpyAsync(c->d->sword, words.data(), (size_t)p * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((r = run_impl(c, kRunSpread)) != KSCHED_OK) { ksched_sync(c); return r; }
+    if ((r = ksched_sync(c)) != KSCHED_OK) return r;
+    return ksched_download_results(c, p, oi, os, of);
 }
 
 }  // extern "C"

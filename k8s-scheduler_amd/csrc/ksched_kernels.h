@@ -200,9 +200,18 @@ struct ExactArgs {
     // them); the kernel reads it with the pod's request
     const int32_t *gang_end;
     int32_t *gang_placed;     // out: members bound per gang, 0 for a rejected one (may be null)
+    // k_exact<SPREAD> (ksched_schedule_spread): the context's spread table and the per-pod word
+    const int32_t *sp_dom;    // [n] node -> topology domain in [0, sp_D), or -1: the node does not carry the key
+    int32_t *sp_counts;       // [sp_S][sp_D] matching pods bound per (group, domain): read at entry, written at exit
+    const int32_t *sp_skew;   // [sp_S] the groups' maximum skew
+    int32_t sp_D, sp_S;       // sp_S * sp_D <= kSpreadMaxCells
+    const int32_t *sp_word;   // per pod: -1 (no group), or group << 1 | enforce; the kernel reads it with the request
 };
 constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
 constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
+constexpr int kSpreadMaxDomains = 1024; // KSCHED_SPREAD_MAX_DOMAINS
+constexpr int kSpreadMaxGroups = 64;    // KSCHED_SPREAD_MAX_GROUPS
+constexpr int kSpreadMaxCells = 4096;   // KSCHED_SPREAD_MAX_CELLS: the LDS table of every workgroup, 16 KiB
 
 struct ScoreArgs {
     NodeRec *nodes;    // read; the rows of `patch` are written back by their chunk's wave
@@ -424,6 +433,9 @@ hipError_t launch_exact(int npt, int prio, int dom, bool lab, bool fast53, const
 // the same launch of k_exact<GANG>: a.gang_end set (a.gang_placed may be null)
 hipError_t launch_exact_gang(int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
                              bool cooperative, hipStream_t s);
+// the same launch of k_exact<SPREAD>: a.sp_* set (never k_exact1: the one-workgroup kernel knows no spread table)
+hipError_t launch_exact_spread(int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
+                               bool cooperative, hipStream_t s);
 hipError_t launch_score_topk(int KC, int prio, int dom, bool lab, bool fast53, const ScoreArgs &a, int pod_groups,
                              hipStream_t s);
 // one workgroup per pod: the score kernel's workgroup lists -> the pod's K-entry Rec list (C_in <= 256)

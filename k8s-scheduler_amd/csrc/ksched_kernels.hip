@@ -44,6 +44,22 @@ __device__ __forceinline__ int32_t *gang_log() {
     }
 }
 
+// k_exact<SPREAD>: a workgroup's copy of the spread table -- the S x D counts row-major, and per group the row's
+// minimum, the number of domains at it, and the maximum skew
+struct SpreadTable {
+    int32_t cnt[kSpreadMaxCells];
+    int32_t mn[kSpreadMaxGroups], nmin[kSpreadMaxGroups], skew[kSpreadMaxGroups];
+};
+template <bool SPREAD>
+__device__ __forceinline__ SpreadTable *spread_table() {
+    if constexpr (SPREAD) {
+        __shared__ SpreadTable s_spread;
+        return &s_spread;
+    } else {
+        return nullptr;
+    }
+}
+
 // (re)derive af / y of every node row from its int64 allocatable
 __global__ void k_prep_nodes(NodeRec *nodes, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -72,9 +88,21 @@ __global__ void k_prep_nodes(NodeRec *nodes, int64_t n) {
 //   the commit's inverse; f / y re-derived once per touched slot), and workgroup 0 rewrites the placed members'
 //   results.  Register-only and workgroup-local: no exchange, no wait.  The next gang's first log entry is
 //   written behind the next pod's barrier, after every thread has left the walk.
+// SPREAD (ksched_schedule_spread): one topology spread constraint per pod joins the
+//   predicate.  Every thread keeps its slots' domains in registers; every workgroup keeps the whole S x D count
+//   table in LDS (SpreadTable, loaded at entry, written back by workgroup 0 at exit) with each row's minimum and
+//   the number of domains at it.  An enforcing pod's slot is eligible when it fits and counts[s][dom] <= skew[s] +
+//   min[s] - 1: one LDS gather per slot and two broadcast reads per pod.  Every workgroup derives the same winner,
+//   reads its domain from the global array (a uniform load) and thread 0 applies the same increment to its own
+//   copy -- no exchange, no wait, the tag and parity sequence unchanged.  A row's minimum rises only when its last
+//   domain at the minimum is incremented; thread 0 then recounts the row (D reads, at most once per D placements
+//   of the group).  The increment is written after the pod's last barrier and the next pod's gathers come before
+//   its first, so a pod that moved the table ends with one more barrier; a pod that did not (no group, not placed,
+//   a node without the key) pays none.
 // ------------------------------------------------------------------------------------------------
-template <int NPT, int PRIO, int DOM, bool LAB, bool F53, bool GANG = false>
+template <int NPT, int PRIO, int DOM, bool LAB, bool F53, bool GANG = false, bool SPREAD = false>
 __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
+    static_assert(!(GANG && SPREAD), "one extension per instantiation");
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -102,6 +130,26 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
             lab[k] = 0; pr[k] = 0.f; id[k] = kNoIdx;
         }
     }
+    [[maybe_unused]] int32_t dom[SPREAD ? NPT : 1];  // SPREAD: the slots' topology domains (-1: the node lacks the key)
+    [[maybe_unused]] SpreadTable *const sp = spread_table<SPREAD>();
+    if constexpr (SPREAD) {
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) dom[k] = id[k] != kNoIdx ? A.sp_dom[id[k]] : -1;
+        const int cells = A.sp_S * A.sp_D;
+        for (int c = tid; c < cells; c += kExactBlock) sp->cnt[c] = A.sp_counts[c];
+        __syncthreads();
+        if (tid < A.sp_S) {  // one thread per group: the row's minimum and how many domains hold it
+            const int32_t *row = sp->cnt + tid * A.sp_D;
+            int32_t m = row[0], nm = 1;
+            for (int d = 1; d < A.sp_D; ++d) {
+                const int32_t v = row[d];
+                nm = v < m ? 1 : nm + (v == m);
+                m = v < m ? v : m;
+            }
+            sp->mn[tid] = m; sp->nmin[tid] = nm; sp->skew[tid] = A.sp_skew[tid];
+        }
+        __syncthreads();
+    }
 
     __shared__ double s_key[2][kExactBlock / 64];
     __shared__ int32_t s_idx[2][kExactBlock / 64];
@@ -120,6 +168,19 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
         const uint64_t sel = LAB ? A.pods.sel[i] : 0;
         // GANG: 0, or at a gang's last member its size | minimum << 16 -- loaded with the request, not after the pod
         const int32_t gend = GANG ? A.gang_end[i] : 0;
+        // SPREAD: -1 (no group), or group << 1 | enforce -- loaded with the request too
+        [[maybe_unused]] const int32_t sword = SPREAD ? A.sp_word[i] : -1;
+        [[maybe_unused]] bool enf = false;   // the pod enforces its group's constraint:
+        [[maybe_unused]] int32_t srow = 0;   // ... the group's row of the table,
+        [[maybe_unused]] int64_t slim = 0;   // ... the largest count an eligible domain may hold
+        if constexpr (SPREAD) {
+            if (sword >= 0 && (sword & 1)) {
+                const int32_t s = sword >> 1;
+                enf = true;
+                srow = s * A.sp_D;
+                slim = (int64_t)sp->skew[s] + sp->mn[s] - 1;
+            }
+        }
         const double rcf = (double)rc, rmf = (double)rm, rpf = (double)rp;
         double bk = -__builtin_inf();
         int32_t bi = kNoIdx;
@@ -127,7 +188,10 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
 #pragma unroll
         for (int k = 0; k < NPT; ++k) {
             if (id[k] != kNoIdx) {
-                const bool f = fits(rc, rm, rp, sel, a0[k], a1[k], a2[k], lab[k], LAB);
+                bool f = fits(rc, rm, rp, sel, a0[k], a1[k], a2[k], lab[k], LAB);
+                if constexpr (SPREAD) {
+                    if (enf) f = f && dom[k] >= 0 && (int64_t)sp->cnt[srow + (dom[k] < 0 ? 0 : dom[k])] <= slim;
+                }
                 cnt += f;
                 double key;
                 if (pair_key_fast<PRIO, DOM, F53>(f, rc, rm, rp, rcf, rmf, rpf, a0[k], a1[k], a2[k], f0[k], f1[k],
@@ -221,6 +285,26 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
             A.out.score[i] = osc;
             A.out.feas[i] = (int32_t)gc;
         }
+        if constexpr (SPREAD) {
+            if (sword >= 0 && oidx >= 0) {  // (the same in every thread of every workgroup)
+                const int32_t wd = A.sp_dom[__builtin_amdgcn_readfirstlane(oidx)];
+                if (wd >= 0) {
+                    if (tid == 0) {
+                        const int32_t s = sword >> 1;
+                        int32_t *row = sp->cnt + s * A.sp_D;
+                        const int32_t old = row[wd];
+                        row[wd] = old + 1;
+                        if (old == sp->mn[s] && --sp->nmin[s] == 0) {
+                            // the row's last domain at the minimum: every domain now holds at least old + 1
+                            int32_t nm = 0;
+                            for (int d = 0; d < A.sp_D; ++d) nm += row[d] == old + 1;
+                            sp->mn[s] = old + 1; sp->nmin[s] = nm;
+                        }
+                    }
+                    __syncthreads();  // the next pod's gathers come before its first barrier
+                }
+            }
+        }
         if constexpr (GANG) {
             if (tid == 0) s_log[gs.gm] = oidx;
             gs.placed += oidx >= 0;
@@ -263,6 +347,13 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
 #pragma unroll
     for (int k = 0; k < NPT; ++k)
         if (id[k] != kNoIdx) set_node(A.nodes + id[k], a0[k], a1[k], a2[k]);
+    if constexpr (SPREAD) {
+        // (every pod that moved the table ended with a barrier: the copy is complete in every thread's view)
+        if (g == 0) {
+            const int cells = A.sp_S * A.sp_D;
+            for (int c = tid; c < cells; c += kExactBlock) A.sp_counts[c] = sp->cnt[c];
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1096,9 +1187,9 @@ __global__ void k_selftest_div(int64_t n, const double *a, const double *b, doub
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-template <int NPT, int PRIO, int DOM, bool LAB, bool F53, bool GANG>
+template <int NPT, int PRIO, int DOM, bool LAB, bool F53, bool GANG, bool SPREAD = false>
 hipError_t exact_one(const ExactArgs &a, int block, bool coop, hipStream_t s) {
-    auto fn = k_exact<NPT, PRIO, DOM, LAB, F53, GANG>;
+    auto fn = k_exact<NPT, PRIO, DOM, LAB, F53, GANG, SPREAD>;
     if (coop && a.G > 1) {
         ExactArgs copy = a;
         void *args[] = {&copy};
@@ -1108,13 +1199,13 @@ hipError_t exact_one(const ExactArgs &a, int block, bool coop, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <int PRIO, int DOM, bool LAB, bool F53, bool GANG>
+template <int PRIO, int DOM, bool LAB, bool F53, bool GANG, bool SPREAD = false>
 hipError_t exact_npt(int npt, const ExactArgs &a, int block, bool coop, hipStream_t s) {
     switch (npt) {
-        case 1: return exact_one<1, PRIO, DOM, LAB, F53, GANG>(a, block, coop, s);
-        case 2: return exact_one<2, PRIO, DOM, LAB, F53, GANG>(a, block, coop, s);
-        case 4: return exact_one<4, PRIO, DOM, LAB, F53, GANG>(a, block, coop, s);
-        case 8: return exact_one<8, PRIO, DOM, LAB, F53, GANG>(a, block, coop, s);
+        case 1: return exact_one<1, PRIO, DOM, LAB, F53, GANG, SPREAD>(a, block, coop, s);
+        case 2: return exact_one<2, PRIO, DOM, LAB, F53, GANG, SPREAD>(a, block, coop, s);
+        case 4: return exact_one<4, PRIO, DOM, LAB, F53, GANG, SPREAD>(a, block, coop, s);
+        case 8: return exact_one<8, PRIO, DOM, LAB, F53, GANG, SPREAD>(a, block, coop, s);
         default: return hipErrorInvalidValue;
     }
 }
@@ -1278,6 +1369,14 @@ hipError_t launch_exact_gang(int npt, int prio, int dom, bool lab, bool f53, con
                              hipStream_t s) {
     if (!a.gang_end) return hipErrorInvalidValue;
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, true>(npt, a, block, coop, s)));
+}
+
+hipError_t launch_exact_spread(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
+                               hipStream_t s) {
+    if (!a.sp_dom || !a.sp_counts || !a.sp_skew || !a.sp_word || a.sp_D < 1 || a.sp_S < 1 ||
+        (int64_t)a.sp_D * a.sp_S > kSpreadMaxCells || a.sp_S > kSpreadMaxGroups)
+        return hipErrorInvalidValue;
+    KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, false, true>(npt, a, block, coop, s)));
 }
 
 hipError_t launch_exact1(int npt, int bs, int prio, int dom, bool lab, bool f53, const ExactArgs &a, hipStream_t s) {

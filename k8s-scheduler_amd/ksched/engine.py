@@ -320,6 +320,54 @@ class Engine:
         self.p = p
         return oi, os_, of, gp
 
+    def load_spread(self, node_domain, max_skew, counts=None, n_domains=None):
+        """The spread table of schedule_spread() (ksched_load_spread): node j lies in topology domain node_domain[j]
+        (-1: it does not carry the key; the ids must be compact -- every id below the largest is carried by a node),
+        group s allows max_skew[s], counts[s, d] (None: zeros) matching pods are already bound in domain d.  The
+        counts then live in the engine and move with every schedule_spread(); load_nodes() invalidates the table,
+        apply_delta() and restore_state() leave it alone.  n_domains: the number of domains where neither the counts
+        nor the largest id says it."""
+        nd = np.ascontiguousarray(node_domain, dtype=np.int32)
+        sk = np.ascontiguousarray(max_skew, dtype=np.int32)
+        assert nd.ndim == 1 and sk.ndim == 1 and nd.shape[0] == max(self.n, 0)
+        S = sk.shape[0]
+        if counts is None:
+            D, cn = (int(nd.max()) + 1 if nd.size else 0) if n_domains is None else int(n_domains), None
+        else:
+            cn = np.ascontiguousarray(counts, dtype=np.int32)
+            assert cn.ndim == 2 and cn.shape[0] == S and n_domains in (None, cn.shape[1])
+            D = cn.shape[1]
+        self._chk(L.lib().ksched_load_spread(self._ctx, D, L.ptr(nd, C.c_int32), S, L.ptr(sk, C.c_int32),
+                                             L.ptr(cn, C.c_int32)), "load_spread")
+        self._spread_shape = (S, D)
+
+    def read_spread(self):
+        """The spread table's counts, int32[S, D], as the last schedule_spread() (or load_spread()) left them."""
+        S, D = getattr(self, "_spread_shape", (0, 0))
+        out = np.empty((max(S, 1), max(D, 1)), np.int32)  # (never a null pointer: an engine without a table answers E_STATE)
+        self._chk(L.lib().ksched_read_spread(self._ctx, L.ptr(out, C.c_int32)), "read_spread")
+        return out[:S, :D]
+
+    def schedule_spread(self, req_cpu, req_mem, req_pods, selector, group, enforce=None):
+        """schedule() under one topology spread constraint per pod (ksched_schedule_spread): pod i belongs to group
+        group[i] of the load_spread() table (-1: none) and, where enforce[i] (None: every pod), may only land in a
+        domain whose count stays within the group's max_skew of the emptiest domain; every placed pod of a group is
+        counted.  One launch of the exact kernel, whatever the engine's mode.  Returns (idx, score, feasible)."""
+        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
+        p = rc.shape[0]
+        assert rm.shape[0] == p and rp.shape[0] == p
+        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
+        gr = np.ascontiguousarray(group, dtype=np.int32)
+        en = None if enforce is None else np.ascontiguousarray(np.asarray(enforce) != 0, dtype=np.uint8)
+        assert gr.shape[0] == p and (en is None or en.shape[0] == p)
+        oi = np.empty(p, np.int32); os_ = np.empty(p, np.float64); of = np.empty(p, np.int32)
+        self._chk(L.lib().ksched_schedule_spread(self._ctx, p, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64),
+                                                 L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64), L.ptr(gr, C.c_int32),
+                                                 L.ptr(en, C.c_uint8), L.ptr(oi, C.c_int32), L.ptr(os_, C.c_double),
+                                                 L.ptr(of, C.c_int32)), "schedule_spread")
+        self.p = p
+        return oi, os_, of
+
 
 def engine_for(cl, mode: Optional[int] = None, **kw) -> Engine:
     """Engine configured for a ksched.cluster.Cluster and loaded with its nodes."""

@@ -45,6 +45,17 @@ class Container:
     requests: Dict[str, str] = dataclasses.field(default_factory=dict)
 
 
+@dataclasses.dataclass(frozen=True)
+class SpreadConstraint:
+    """One topologySpreadConstraints entry with whenUnsatisfiable: DoNotSchedule (build extension)."""
+    max_skew: int
+    topology_key: str
+    match_labels: tuple  # labelSelector.matchLabels as sorted (key, value) pairs
+
+    def matches(self, labels: Dict[str, str]) -> bool:
+        return all(labels.get(k) == v for k, v in self.match_labels)
+
+
 @dataclasses.dataclass
 class Pod:
     name: str
@@ -54,6 +65,8 @@ class Pod:
     uid: str = ""
     node_selector: Dict[str, str] = dataclasses.field(default_factory=dict)
     priority: int = 0  # spec.priority (preemption; build extension, the reference knows no priorities)
+    labels: Dict[str, str] = dataclasses.field(default_factory=dict)  # metadata.labels (topology spread groups)
+    spread: Optional[SpreadConstraint] = None  # the first DoNotSchedule entry of spec.topologySpreadConstraints
 
 
 @dataclasses.dataclass
@@ -119,14 +132,24 @@ def node_from_kube(obj: dict) -> Node:
 
 def pod_from_kube(obj: dict) -> Pod:
     """One PodList item / watch event object (anchor/types.go:57-80): containers' resources.requests
-    (limits are ignored, anchor/predicate.go:73-77) and spec.nodeName; spec.priority (absent: 0) for preemption."""
+    (limits are ignored, anchor/predicate.go:73-77) and spec.nodeName; spec.priority (absent: 0) for preemption;
+    metadata.labels and the first DoNotSchedule entry of spec.topologySpreadConstraints (maxSkew, topologyKey,
+    labelSelector.matchLabels) for topology spread -- ScheduleAnyway entries and any further ones are ignored."""
     md = obj.get("metadata") or {}
     sp = obj.get("spec") or {}
+    spread = None
+    for tc in (sp.get("topologySpreadConstraints") or []):
+        if tc.get("whenUnsatisfiable", "DoNotSchedule") == "DoNotSchedule":
+            ml = (tc.get("labelSelector") or {}).get("matchLabels") or {}
+            spread = SpreadConstraint(max_skew=int(tc.get("maxSkew", 1)), topology_key=tc.get("topologyKey", ""),
+                                      match_labels=tuple(sorted(ml.items())))
+            break
     conts = [Container(name=c.get("name", ""), requests=dict((c.get("resources") or {}).get("requests") or {}))
              for c in (sp.get("containers") or [])]
     return Pod(name=md.get("name", ""), containers=conts, node_name=sp.get("nodeName") or "",
                annotations=dict(md.get("annotations") or {}), uid=md.get("uid", ""),
-               node_selector=dict(sp.get("nodeSelector") or {}), priority=int(sp.get("priority") or 0))
+               node_selector=dict(sp.get("nodeSelector") or {}), priority=int(sp.get("priority") or 0),
+               labels=dict(md.get("labels") or {}), spread=spread)
 
 
 def _strv(items):
@@ -220,6 +243,55 @@ def group_gangs(pods: List[Pod]):
         mins.append(need)
     return ([m for members in gangs for m in members], np.asarray(off, dtype=np.int64),
             np.asarray(mins, dtype=np.int32))
+
+
+def spread_tables(nodes: List[Node], bound: List[Pod], pending: List[Pod]):
+    """The inputs of ksched_load_spread / ksched_schedule_spread from Kubernetes objects.  The pending pods' constraints
+    must share one topology key (ValueError on a second); domain ids are compacted over the values the nodes carry
+    for it, in node order (a node without the label: -1); one group per distinct (selector, maxSkew), in the pending
+    pods' order; a group's counts are the bound pods whose labels match its selector, per domain of their node.  A
+    pending pod with a constraint enforces its group; one without a constraint whose labels match a group's selector
+    only counts in (the first such) group.  Returns (node_domain int32[n], max_skew int32[S], counts int32[S, D],
+    group int32[p], enforce uint8[p]); without any constraint, one domain and one empty group."""
+    keys = []
+    for pod in pending:
+        if pod.spread is not None and pod.spread.topology_key not in keys:
+            keys.append(pod.spread.topology_key)
+    if len(keys) > 1:
+        raise ValueError(f"topology spread: one topology key per call, the pending pods name {keys}")
+    p = len(pending)
+    if not keys:
+        return (np.zeros(len(nodes), np.int32), np.ones(1, np.int32), np.zeros((1, 1), np.int32),
+                np.full(p, -1, np.int32), np.zeros(p, np.uint8))
+    ids: Dict[str, int] = {}
+    node_domain = np.full(len(nodes), -1, np.int32)
+    for j, nd in enumerate(nodes):
+        v = nd.label_map.get(keys[0])
+        if v is not None:
+            node_domain[j] = ids.setdefault(v, len(ids))
+    if not ids:
+        raise ValueError(f"topology spread: no node carries the topology key {keys[0]!r}")
+    groups: Dict[tuple, int] = {}
+    for pod in pending:
+        if pod.spread is not None:
+            groups.setdefault((pod.spread.match_labels, pod.spread.max_skew), len(groups))
+    cons = [SpreadConstraint(max_skew=sk, topology_key=keys[0], match_labels=ml) for ml, sk in groups]
+    counts = np.zeros((len(cons), len(ids)), np.int32)
+    by_name = {nd.name: j for j, nd in enumerate(nodes)}
+    for pod in bound:
+        d = node_domain[by_name[pod.node_name]] if pod.node_name in by_name else -1
+        if d >= 0:
+            for s, c in enumerate(cons):
+                counts[s, d] += c.matches(pod.labels)
+    group = np.full(p, -1, np.int32)
+    enforce = np.zeros(p, np.uint8)
+    for i, pod in enumerate(pending):
+        if pod.spread is not None:
+            group[i] = groups[(pod.spread.match_labels, pod.spread.max_skew)]
+            enforce[i] = 1
+        else:
+            group[i] = next((s for s, c in enumerate(cons) if c.matches(pod.labels)), -1)
+    return node_domain, np.asarray([c.max_skew for c in cons], np.int32), counts, group, enforce
 
 
 def parse_price(s: str) -> float:
@@ -452,6 +524,33 @@ class FakeCluster:
                     node = self.nodes[int(i)]
                     self.bind(pod, node)
                     out.append((pod, node))
+        return out
+
+    def schedule_spread(self, pending: Optional[List[Pod]] = None):
+        """schedule_pods under the pending pods' topology spread constraints (spread_tables;
+        ksched_schedule_spread): the spread table is reloaded from self.pods' bound pods on every call, then one
+        engine call resolves every pending pod in order and the binds follow.  Returns (pod, node | Exception); a
+        pod that fits nowhere its constraint allows gets the usual FailedScheduling event (without per-node lines:
+        the explain calls know no spread reason)."""
+        pending = self.unscheduled_pods() if pending is None else pending
+        node_domain, skew, counts, group, enforce = spread_tables(self.nodes, [p for p in self.pods if p.node_name],
+                                                                  pending)
+        self.engine.load_spread(node_domain, skew, counts)
+        rc, rm, rp = pack_pods(pending)
+        sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
+        idx, _, _ = self.engine.schedule_spread(rc, rm, rp, sel, group, enforce)
+        out = []
+        for pod, i in zip(pending, idx):
+            if i == L.NO_FIT:
+                self.events.append(dict(reason="FailedScheduling", message=f"pod ({pod.name}) failed to fit in any node",
+                                        type="Warning", involved=pod.name))
+                out.append((pod, FitError(f"Unable to schedule pod ({pod.name}) failed to fit in any node")))
+            elif i == L.NO_POSITIVE_SCORE:
+                out.append((pod, NilNodeError(pod.name)))
+            else:
+                node = self.nodes[int(i)]
+                self.bind(pod, node)
+                out.append((pod, node))
         return out
 
     def schedule_pod(self, pod: Pod, selector: Optional[int] = None):
