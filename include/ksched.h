@@ -398,6 +398,58 @@ int ksched_schedule_spread(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, c
                            const uint8_t *spread_enforce /* p, NULL = all 1 */, int32_t *out_idx, double *out_score,
                            int32_t *out_feasible);
 
+/* ---- extended resources (added within ABI 6: probe with dlsym(lib, "ksched_schedule_ext"); the version number did not move) ----
+ * The scalar-resource half of kube-scheduler's NodeResourcesFit: up to KSCHED_EXT_MAX further resource columns beside
+ * cpu, memory and pod slots (amd.com/gpu, nvidia.com/gpu, hugepages-2Mi, an RDMA NIC, a pre-scaled ephemeral-storage),
+ * resolved by ONE launch of the exact kernel whatever opts.mode says (stats.pipeline == KSCHED_PIPE_EXACT,
+ * stats.pair_evals == p * n).  A build extension: the reference knows cpu, memory and pods only.
+ *
+ * The table (ksched_load_ext, after ksched_load_nodes): node_ext[r * n_local + j] is node j's allocatable amount of
+ * resource r -- capacity minus what bound pods already hold.  Any int64 is accepted.
+ * Pods: req_ext[r * p + i] >= 0 is pod i's request for resource r (NULL: every request is zero).  A zero request is not
+ * checked at all, as in kube-scheduler's fitsRequest: a node whose column is 0 or negative still takes pods that do
+ * not ask for it.
+ *
+ * Per pod i, in order:
+ *   eligible(i, j) = fits(i, j) && for every r < n_ext: req_ext[r][i] == 0 || req_ext[r][i] <= ext[r][j]
+ * fits is the scheduler's predicate, with the label check under opts.use_labels.  Everything else is ksched_schedule
+ * in exact mode with eligible in the place of fits: out_feasible counts eligible nodes, zero eligible nodes is
+ * KSCHED_NO_FIT, the key, the tie-break and the commit alloc -= (req_cpu, req_mem, 1) are unchanged.  Scores do not
+ * see the extended columns: kube-scheduler's default resource scoring covers cpu and memory only, and so does the
+ * reference's.  The constraint joins the predicate exactly as labels and spread do: under KSCHED_DOMAIN_ALL an
+ * ineligible node can still win the argmax; callers who want enforcement use KSCHED_DOMAIN_FEASIBLE, or best-price.
+ * A pod placed on w does ext[r][w] -= req_ext[r][i] for every r; the subtraction wraps, like the commit's, so under
+ * KSCHED_DOMAIN_ALL a column can go negative.
+ *
+ * State: the table lives in the context and carries over from call to call; ksched_read_ext returns it.
+ * ksched_load_nodes invalidates it (ksched_schedule_ext and ksched_read_ext return KSCHED_E_STATE until it is loaded
+ * again); ksched_apply_delta and ksched_save_state / ksched_restore_state leave it alone -- keeping it in step is the
+ * caller's business (FakeCluster.schedule_ext reloads the table on every call).  ksched_schedule,
+ * ksched_schedule_gangs, ksched_schedule_spread, ksched_rank, ksched_explain* and ksched_preempt neither read nor
+ * move it.  After ksched_schedule_ext, ksched_explain_batch / ksched_explain_pod return KSCHED_E_STATE: they know no
+ * extended-resource reason (KSCHED_NUM_REASONS did not change).
+ *
+ * KSCHED_E_INVALID (nothing changed; a table loaded earlier survives): n_ext outside [1, KSCHED_EXT_MAX], a null
+ * node_ext, a negative request, p outside [0, 2^30), opts.nranks > 1.
+ *
+ * Out of scope: extended columns in rank, preempt, explain, gangs and spread; the batched pipeline and multi-rank;
+ * the one-workgroup exact kernel (an ext run always takes the multi-slot one); an apply_delta for the table; init
+ * containers and pod overhead; quantity suffixes (amounts are whole numbers, pre-scaled by the caller); scoring on
+ * extended resources.
+ *
+ * Worked example (best-price, feasible domain, one resource "gpu", ample cpu and memory): nodes n0 (price 0.1, gpu 1),
+ * n1 (0.2, gpu 0), n2 (0.5, gpu 2); the pods ask for gpu 1, 0, 2, 1.  Pod 0: {n0, n2} are eligible, the cheapest is n0
+ * (gpu 0, 0, 2).  Pod 1 asks for nothing, so nothing is checked: all three are eligible, n0 again.  Pod 2: only n2
+ * (gpu 0, 0, 0).  Pod 3: no node, KSCHED_NO_FIT.  out_idx = {0, 0, 2, -1}, out_feasible = {2, 3, 1, 0}, final gpu column
+ * {0, 0, 0}.  ksched_schedule on the same input gives {0, 0, 0, 0}. */
+#define KSCHED_EXT_MAX 4                     /* the exact kernel's per-workgroup LDS table: 4 * 2048 slots * 8 B = 64 KiB */
+int ksched_load_ext(ksched_ctx *ctx, int32_t n_ext, const int64_t *node_ext /* n_ext * n_local, node_ext[r * n_local + j] */);
+int ksched_read_ext(ksched_ctx *ctx, int64_t *out_ext /* n_ext * n_local */);
+int ksched_schedule_ext(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,
+                        const int64_t *req_pods, const uint64_t *selector,
+                        const int64_t *req_ext /* n_ext * p, req_ext[r * p + i]; NULL = all zero */,
+                        int32_t *out_idx, double *out_score, int32_t *out_feasible);
+
 /* Same, in two halves, with the pods staged in HBM: upload once, run many times (bench). */
 int ksched_upload_pods(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,
                        const int64_t *req_pods, const uint64_t *selector);

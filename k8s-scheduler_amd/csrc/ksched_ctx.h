@@ -104,6 +104,8 @@ struct ksched_bufs {
     DevBuf<int32_t> gend, gplaced;        // ksched_schedule_gangs: ExactArgs::gang_end per pod, members bound per gang
     DevBuf<int32_t> sdom, scnt, sskew;    // ksched_load_spread: node -> domain, the S x D counts, the groups' skews
     DevBuf<int32_t> sword;                // ksched_schedule_spread: ExactArgs::sp_word per pod
+    DevBuf<int64_t> etab, ereq;           // ksched_load_ext: the R x n table; ksched_schedule_ext: ExactArgs::ext_req
+    DevBuf<int32_t> eword;                // ksched_schedule_ext: ExactArgs::ext_word per pod
     DevBuf<void> xws, xbuf;               // explain: workspace; counts + NO_FIT pod list, or one pod's state + counts
     DevBuf<void> rws;                     // ksched_rank: one chunk's pods, span lists and outputs (rank_geometry's bound)
     DevBuf<int64_t> bcpu, bmem, boff;     // ksched_load_bound: the bound-pod table (BoundTable, ksched_preempt.h)
@@ -192,6 +194,7 @@ struct ksched_ctx {
     int64_t perm_n = -1;         // the node count d->perm was built for (-1: none; k_exact1 needs perm_n == n_local)
     bool bound_valid = false;    // ksched_load_bound's table describes the loaded nodes (every load_nodes clears it)
     int32_t spread_D = 0, spread_S = 0;  // ksched_load_spread's table; 0: none (every load_nodes clears it)
+    int32_t ext_R = 0;           // ksched_load_ext's table: its resource columns; 0: none (every load_nodes clears it)
     // pods
     int64_t p = 0;
     // batched workspace

@@ -6,6 +6,7 @@
 #include <new>
 
 #include "ksched_ctx.h"
+#include "ksched_ext.h"
 #include "ksched_preempt.h"
 #include "ksched_rank.h"
 #include "ksched_spread.h"
@@ -90,6 +91,7 @@ int ksched_load_nodes(ksched_ctx *c, int64_t n, const int64_t *ac, const int64_t
     c->perm_n = -1;  // first: whatever happens below, d->perm no longer describes the loaded nodes
     c->bound_valid = false;  // ... and neither does the bound-pod table (ksched_load_bound)
     c->spread_D = c->spread_S = 0;  // ... nor the spread table (ksched_load_spread)
+    c->ext_R = 0;  // ... nor the extended-resource table (ksched_load_ext)
     HIPCHK(c, c->d->nodes.reserve((size_t)n * sizeof(NodeRec)));
     c->d->snap.release();
     // in the stream of the kernels that read it (a legacy hipMemcpy from pageable memory may return before its DMA
@@ -547,6 +549,37 @@ int ksched_read_spread(ksched_ctx *c, int32_t *out_counts) {
     HIPCHK(c, hipSetDevice(c->dev));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(out_counts, c->d->scnt, (size_t)c->spread_D * (size_t)c->spread_S * 4, hipMemcpyDeviceToHost));
+    return KSCHED_OK;
+}
+
+// The extended-resource table of ksched_schedule_ext: checked on the host (ksched_ext.h) before anything is allocated,
+// then uploaded in the stream of the kernel that reads it.  Touches no node row; the context holds the new table only
+// once the copy has landed, and the earlier one until the checks have passed.
+int ksched_load_ext(ksched_ctx *c, int32_t n_ext, const int64_t *node_ext) {
+    if (!c) return KSCHED_E_INVALID;
+    static_assert(KSCHED_EXT_MAX == kExtMax, "ext constants");
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_ext before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "load_ext: extended resources are single-GPU (the exact kernel)");
+    if (const char *why = ext_check_table(n_ext, node_ext)) return fail(c, KSCHED_E_INVALID, std::string("load_ext: ") + why);
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ext_R = 0;
+    const size_t bytes = (size_t)n_ext * (size_t)c->n_local * 8;
+    HIPCHK(c, c->d->etab.reserve(bytes));
+    if (bytes > 0) HIPCHK(c, hipMemcpyAsync(c->d->etab, node_ext, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's array is free again
+    c->ext_R = n_ext;
+    return KSCHED_OK;
+}
+
+int ksched_read_ext(ksched_ctx *c, int64_t *out_ext) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->ext_R == 0) return fail(c, KSCHED_E_STATE, "read_ext: no extended-resource table (ksched_load_ext after every ksched_load_nodes)");
+    if (!out_ext) return fail(c, KSCHED_E_INVALID, "read_ext: out_ext is NULL");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = (size_t)c->ext_R * (size_t)c->n_local * 8;
+    if (bytes > 0) HIPCHK(c, hipMemcpy(out_ext, c->d->etab, bytes, hipMemcpyDeviceToHost));
     return KSCHED_OK;
 }
 

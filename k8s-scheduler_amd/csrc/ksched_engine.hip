@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "ksched_ctx.h"
+#include "ksched_ext.h"
 #include "ksched_spread.h"
 
 using namespace ksched;
@@ -465,10 +466,12 @@ int enqueue_persistent(ksched_ctx *c) {
 
 // gang: the run of ksched_schedule_gangs (the staged gangs in d->gend) -- always k_exact<GANG>, the
 // multi-slot kernel, under the same geometry and launch rule as a plain exact run; spread: the run of
-// ksched_schedule_spread (the staged words in d->sword, the context's table) -- always k_exact<SPREAD>, likewise
-enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2 };
+// ksched_schedule_spread (the staged words in d->sword, the context's table) -- always k_exact<SPREAD>, likewise;
+// ext: the run of ksched_schedule_ext (the staged requests in d->ereq / d->eword, the context's table) -- always
+// k_exact<EXT>, likewise
+enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3 };
 int enqueue_exact(ksched_ctx *c, ExactRun run) {
-    const bool gang = run == kRunGang, spread = run == kRunSpread;
+    const bool gang = run == kRunGang, spread = run == kRunSpread, ext = run == kRunExt;
     if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "exact mode is single-GPU; use batched mode across ranks");
     const int64_t n = c->n_local;
     // the whole node set in ONE workgroup's registers (k_exact1): no cross-workgroup exchange per pod
@@ -479,7 +482,7 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
     a.pods = PodArgs{c->d->rc, c->d->rm, c->d->rp, c->d->sel, c->p};
     a.out = OutArgs{c->d->oidx, c->d->osc, c->d->ofeas};
     a.err = c->d->err;
-    if (!gang && !spread && c->o.exact_wgs <= 1 && n > 0 && n <= (int64_t)kExact1Block * max1 && (!price || c->perm_n == n)) {
+    if (!gang && !spread && !ext && c->o.exact_wgs <= 1 && n > 0 && n <= (int64_t)kExact1Block * max1 && (!price || c->perm_n == n)) {
         int bs = kExact1Block;
         if (price && c->diag.exact1_bs == 512 && n <= 5120) bs = 512;
         if (price && c->diag.exact1_bs == 256 && n <= 5120) bs = 256;
@@ -528,6 +531,10 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
         a.sp_D = c->spread_D; a.sp_S = c->spread_S; a.sp_word = c->d->sword;
         HIPCHK(c, launch_exact_spread(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
                                       G > 1 && !c->diag.plain_launch, c->stream));
+    } else if (ext) {
+        a.ext = c->d->etab; a.ext_req = c->d->ereq; a.ext_word = c->d->eword; a.n_ext = c->ext_R;
+        HIPCHK(c, launch_exact_ext(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
+                                   G > 1 && !c->diag.plain_launch, c->stream));
     } else {
         HIPCHK(c, launch_exact(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
                                G > 1 && !c->diag.plain_launch, c->stream));
@@ -634,10 +641,9 @@ int ksched_destroy(ksched_ctx *c) {
 
 const char *ksched_last_error(const ksched_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
-// ksched_run, or the run of ksched_schedule_gangs / ksched_schedule_spread: the exact kernel over the staged gangs /
-// spread words whatever opts.mode
+// ksched_run, or the run of ksched_schedule_gangs / ksched_schedule_spread / ksched_schedule_ext: the exact kernel over
+// the staged gangs / spread words / extended requests whatever opts.mode
 static int run_impl(ksched_ctx *c, ExactRun run) {
-    const bool gang = run == kRunGang;
     if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "run before load_nodes");
     if (c->o.nranks > 1 && !c->comm && !c->group && !c->xchg_ready)
         return fail(c, KSCHED_E_STATE, "run: multi-rank context without ksched_set_comm / ksched_set_group / "
@@ -684,8 +690,8 @@ static int run_impl(ksched_ctx *c, ExactRun run) {
     // FAST53 bound true of the state the NEXT call starts from
     if (r == KSCHED_OK) c->max_abs_alloc = sat_add(c->max_abs_alloc, c->sum_abs_req);
     // (a rolled-back gang leaves no final placements for ksched_explain_batch to rebuild a pod's state from)
-    // (and the explain calls know no spread reason)
-    c->explain_valid = r == KSCHED_OK && !gang && run != kRunSpread;
+    // (and the explain calls know no spread or extended-resource reason)
+    c->explain_valid = r == KSCHED_OK && run == kRunPlain;
     return r;
 }
 
@@ -852,6 +858,37 @@ int ksched_schedule_spread(ksched_ctx *c, int64_t p, const int64_t *rc, const in
     if (p > 0) HIPCHK(c, hipMemcpyAsync(c->d->sword, words.data(), (size_t)p * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((r = run_impl(c, kRunSpread)) != KSCHED_OK) { ksched_sync(c); return r; }
+    if ((r = ksched_sync(c)) != KSCHED_OK) return r;
+    return ksched_download_results(c, p, oi, os, of);
+}
+
+int ksched_schedule_ext(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                        const uint64_t *sel, const int64_t *req_ext, int32_t *oi, double *os, int32_t *of) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_ext before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_ext is single-GPU (the exact kernel)");
+    if (c->ext_R == 0)
+        return fail(c, KSCHED_E_STATE, "schedule_ext: no extended-resource table (ksched_load_ext after every ksched_load_nodes)");
+    // every request is checked, and the per-pod words are packed, before anything is written or allocated
+    std::vector<int64_t> reqs;
+    std::vector<int32_t> words;
+    try {
+        if (const char *why = ext_pack_pods(p, c->ext_R, req_ext, &reqs, &words))
+            return fail(c, KSCHED_E_INVALID, std::string("schedule_ext: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "schedule_ext: host staging buffer");
+    }
+    int r = ksched_upload_pods(c, p, rc, rm, rp, sel);
+    if (r != KSCHED_OK) return r;
+    HIPCHK(c, c->d->ereq.reserve(reqs.size() * 8));
+    HIPCHK(c, c->d->eword.reserve((size_t)p * 4));
+    // in the stream of the kernel that reads them, finished before the vectors go (ksched_upload_pods)
+    if (p > 0) {
+        HIPCHK(c, hipMemcpyAsync(c->d->ereq, reqs.data(), reqs.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d->eword, words.data(), (size_t)p * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((r = run_impl(c, kRunExt)) != KSCHED_OK) { ksched_sync(c); return r; }
     if ((r = ksched_sync(c)) != KSCHED_OK) return r;
     return ksched_download_results(c, p, oi, os, of);
 }

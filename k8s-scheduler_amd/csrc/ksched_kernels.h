@@ -206,12 +206,18 @@ struct ExactArgs {
     const int32_t *sp_skew;   // [sp_S] the groups' maximum skew
     int32_t sp_D, sp_S;       // sp_S * sp_D <= kSpreadMaxCells
     const int32_t *sp_word;   // per pod: -1 (no group), or group << 1 | enforce; the kernel reads it with the request
+    // k_exact<EXT> (ksched_schedule_ext): the context's extended-resource table and the staged requests
+    int64_t *ext;             // [n_ext][n] allocatable per (resource, node): read at entry, written at exit
+    const int64_t *ext_req;   // [p][kExtMax] requests, pod-major (columns at and beyond n_ext: 0)
+    const int32_t *ext_word;  // per pod: bit r set where ext_req[i][r] != 0; the kernel reads it with the request
+    int32_t n_ext;            // 1..kExtMax
 };
 constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
 constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
 constexpr int kSpreadMaxDomains = 1024; // KSCHED_SPREAD_MAX_DOMAINS
 constexpr int kSpreadMaxGroups = 64;    // KSCHED_SPREAD_MAX_GROUPS
 constexpr int kSpreadMaxCells = 4096;   // KSCHED_SPREAD_MAX_CELLS: the LDS table of every workgroup, 16 KiB
+constexpr int kExtMax = 4;              // KSCHED_EXT_MAX: columns of the dynamic LDS table, kExtMax * 256 * 8 slots * 8 B = 64 KiB
 
 struct ScoreArgs {
     NodeRec *nodes;    // read; the rows of `patch` are written back by their chunk's wave
@@ -436,6 +442,9 @@ hipError_t launch_exact_gang(int npt, int prio, int dom, bool lab, bool fast53, 
 // the same launch of k_exact<SPREAD>: a.sp_* set (never k_exact1: the one-workgroup kernel knows no spread table)
 hipError_t launch_exact_spread(int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
                                bool cooperative, hipStream_t s);
+// the same launch of k_exact<EXT>: a.ext* set, dynamic LDS of a.n_ext * block * npt * 8 bytes (never k_exact1)
+hipError_t launch_exact_ext(int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
+                            bool cooperative, hipStream_t s);
 hipError_t launch_score_topk(int KC, int prio, int dom, bool lab, bool fast53, const ScoreArgs &a, int pod_groups,
                              hipStream_t s);
 // one workgroup per pod: the score kernel's workgroup lists -> the pod's K-entry Rec list (C_in <= 256)

@@ -60,6 +60,18 @@ __device__ __forceinline__ SpreadTable *spread_table() {
     }
 }
 
+// k_exact<EXT>: a workgroup's slots of the extended-resource table, in dynamic LDS: column r of slot s at
+// [r * kExactBlock * NPT + s].  (Declared 16-byte aligned: the dynamic region follows the kernel's statics.)
+template <bool EXT>
+__device__ __forceinline__ int64_t *ext_table() {
+    if constexpr (EXT) {
+        extern __shared__ __attribute__((aligned(16))) int64_t s_ext[];
+        return s_ext;
+    } else {
+        return nullptr;
+    }
+}
+
 // (re)derive af / y of every node row from its int64 allocatable
 __global__ void k_prep_nodes(NodeRec *nodes, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -99,10 +111,18 @@ __global__ void k_prep_nodes(NodeRec *nodes, int64_t n) {
 //   of the group).  The increment is written after the pod's last barrier and the next pod's gathers come before
 //   its first, so a pod that moved the table ends with one more barrier; a pod that did not (no group, not placed,
 //   a node without the key) pays none.
+// EXT (ksched_schedule_ext): up to kExtMax further resource columns join the predicate.  The
+//   registers are full (section 4.7), so the columns of a workgroup's slots live in dynamic LDS, ext[r][slot] with
+//   slot = tid + k * kExactBlock: consecutive lanes read consecutive 8-byte words.  Loaded from the device table at
+//   entry (node ids below n only), written back by every workgroup for its own slots at exit.  The pod's requests
+//   come pod-major with a word of non-zero-column bits, all uniform loads: a column the pod does not ask for is a
+//   uniform skip, so a pod that asks for nothing reads no LDS.  The owner lane of the winning slot subtracts the
+//   non-zero requests from its own slot's words.  Only the owning thread ever reads or writes a slot's words: no
+//   new barrier, exchange or wait; the tag and parity sequence unchanged.
 // ------------------------------------------------------------------------------------------------
-template <int NPT, int PRIO, int DOM, bool LAB, bool F53, bool GANG = false, bool SPREAD = false>
+template <int NPT, int PRIO, int DOM, bool LAB, bool F53, bool GANG = false, bool SPREAD = false, bool EXT = false>
 __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
-    static_assert(!(GANG && SPREAD), "one extension per instantiation");
+    static_assert((int)GANG + (int)SPREAD + (int)EXT <= 1, "one extension per instantiation");
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -150,6 +170,16 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
         }
         __syncthreads();
     }
+    // EXT: this thread's words of column r, slot k at ext[r * kExtCol + k * kExactBlock] (no other thread touches them)
+    [[maybe_unused]] constexpr int kExtCol = kExactBlock * NPT;
+    [[maybe_unused]] int64_t *const ext = EXT ? ext_table<EXT>() + tid : nullptr;
+    if constexpr (EXT) {
+        for (int r = 0; r < A.n_ext; ++r) {
+#pragma unroll
+            for (int k = 0; k < NPT; ++k)
+                ext[r * kExtCol + k * kExactBlock] = id[k] != kNoIdx ? A.ext[(int64_t)r * A.n + id[k]] : 0;
+        }
+    }
 
     __shared__ double s_key[2][kExactBlock / 64];
     __shared__ int32_t s_idx[2][kExactBlock / 64];
@@ -181,6 +211,18 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                 slim = (int64_t)sp->skew[s] + sp->mn[s] - 1;
             }
         }
+        // EXT: the non-zero-column bits -- loaded with the request too -- and, only where there are any, the requests
+        // (pod-major: one uniform load; loading them for every pod cost 4 % per pod on pods that ask for nothing)
+        [[maybe_unused]] const int32_t eword = EXT ? A.ext_word[i] : 0;
+        [[maybe_unused]] int64_t er[EXT ? kExtMax : 1];
+        if constexpr (EXT) {
+#pragma unroll
+            for (int r = 0; r < kExtMax; ++r) er[r] = 0;
+            if (eword != 0) {
+#pragma unroll
+                for (int r = 0; r < kExtMax; ++r) er[r] = A.ext_req[i * kExtMax + r];
+            }
+        }
         const double rcf = (double)rc, rmf = (double)rm, rpf = (double)rp;
         double bk = -__builtin_inf();
         int32_t bi = kNoIdx;
@@ -191,6 +233,13 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                 bool f = fits(rc, rm, rp, sel, a0[k], a1[k], a2[k], lab[k], LAB);
                 if constexpr (SPREAD) {
                     if (enf) f = f && dom[k] >= 0 && (int64_t)sp->cnt[srow + (dom[k] < 0 ? 0 : dom[k])] <= slim;
+                }
+                if constexpr (EXT) {
+                    if (eword != 0) {  // (uniform: a pod that asks for no column reads no LDS)
+#pragma unroll
+                        for (int r = 0; r < kExtMax; ++r)
+                            if (eword >> r & 1) f = f && er[r] <= ext[r * kExtCol + k * kExactBlock];
+                    }
                 }
                 cnt += f;
                 double key;
@@ -277,6 +326,16 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                     f0[k] = (double)a0[k]; f1[k] = (double)a1[k]; f2[k] = (double)a2[k];
                     y0[k] = recip_or_zero(a0[k], f0[k]); y1[k] = recip_or_zero(a1[k], f1[k]);
                     y2[k] = recip_or_zero(a2[k], f2[k]);
+                    if constexpr (EXT) {
+                        if (eword != 0) {  // the owner lane: its own slot's words, the non-zero columns only
+#pragma unroll
+                            for (int r = 0; r < kExtMax; ++r)
+                                if (eword >> r & 1) {
+                                    int64_t *w = ext + r * kExtCol + k * kExactBlock;
+                                    *w = wsub(*w, er[r]);
+                                }
+                        }
+                    }
                 }
             }
         }
@@ -347,6 +406,13 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
 #pragma unroll
     for (int k = 0; k < NPT; ++k)
         if (id[k] != kNoIdx) set_node(A.nodes + id[k], a0[k], a1[k], a2[k]);
+    if constexpr (EXT) {
+        for (int r = 0; r < A.n_ext; ++r) {
+#pragma unroll
+            for (int k = 0; k < NPT; ++k)
+                if (id[k] != kNoIdx) A.ext[(int64_t)r * A.n + id[k]] = ext[r * kExtCol + k * kExactBlock];
+        }
+    }
     if constexpr (SPREAD) {
         // (every pod that moved the table ended with a barrier: the copy is complete in every thread's view)
         if (g == 0) {
@@ -1187,25 +1253,28 @@ __global__ void k_selftest_div(int64_t n, const double *a, const double *b, doub
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-template <int NPT, int PRIO, int DOM, bool LAB, bool F53, bool GANG, bool SPREAD = false>
+template <int NPT, int PRIO, int DOM, bool LAB, bool F53, bool GANG, bool SPREAD = false, bool EXT = false>
 hipError_t exact_one(const ExactArgs &a, int block, bool coop, hipStream_t s) {
-    auto fn = k_exact<NPT, PRIO, DOM, LAB, F53, GANG, SPREAD>;
+    auto fn = k_exact<NPT, PRIO, DOM, LAB, F53, GANG, SPREAD, EXT>;
+    // EXT: the workgroup's slots of every column (ext_table), at most kExtMax * 256 * 8 * 8 B = 64 KiB
+    const size_t lds = EXT ? (size_t)a.n_ext * kExactBlock * NPT * sizeof(int64_t) : 0;
+    if (EXT && block != kExactBlock) return hipErrorInvalidValue;
     if (coop && a.G > 1) {
         ExactArgs copy = a;
         void *args[] = {&copy};
-        return hipLaunchCooperativeKernel((const void *)fn, dim3(a.G), dim3(block), args, 0, s);
+        return hipLaunchCooperativeKernel((const void *)fn, dim3(a.G), dim3(block), args, lds, s);
     }
-    hipLaunchKernelGGL(fn, dim3(a.G), dim3(block), 0, s, a);
+    hipLaunchKernelGGL(fn, dim3(a.G), dim3(block), lds, s, a);
     return hipGetLastError();
 }
 
-template <int PRIO, int DOM, bool LAB, bool F53, bool GANG, bool SPREAD = false>
+template <int PRIO, int DOM, bool LAB, bool F53, bool GANG, bool SPREAD = false, bool EXT = false>
 hipError_t exact_npt(int npt, const ExactArgs &a, int block, bool coop, hipStream_t s) {
     switch (npt) {
-        case 1: return exact_one<1, PRIO, DOM, LAB, F53, GANG, SPREAD>(a, block, coop, s);
-        case 2: return exact_one<2, PRIO, DOM, LAB, F53, GANG, SPREAD>(a, block, coop, s);
-        case 4: return exact_one<4, PRIO, DOM, LAB, F53, GANG, SPREAD>(a, block, coop, s);
-        case 8: return exact_one<8, PRIO, DOM, LAB, F53, GANG, SPREAD>(a, block, coop, s);
+        case 1: return exact_one<1, PRIO, DOM, LAB, F53, GANG, SPREAD, EXT>(a, block, coop, s);
+        case 2: return exact_one<2, PRIO, DOM, LAB, F53, GANG, SPREAD, EXT>(a, block, coop, s);
+        case 4: return exact_one<4, PRIO, DOM, LAB, F53, GANG, SPREAD, EXT>(a, block, coop, s);
+        case 8: return exact_one<8, PRIO, DOM, LAB, F53, GANG, SPREAD, EXT>(a, block, coop, s);
         default: return hipErrorInvalidValue;
     }
 }
@@ -1377,6 +1446,12 @@ hipError_t launch_exact_spread(int npt, int prio, int dom, bool lab, bool f53, c
         (int64_t)a.sp_D * a.sp_S > kSpreadMaxCells || a.sp_S > kSpreadMaxGroups)
         return hipErrorInvalidValue;
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, false, true>(npt, a, block, coop, s)));
+}
+
+hipError_t launch_exact_ext(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
+                            hipStream_t s) {
+    if (!a.ext || !a.ext_req || !a.ext_word || a.n_ext < 1 || a.n_ext > kExtMax) return hipErrorInvalidValue;
+    KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, false, false, true>(npt, a, block, coop, s)));
 }
 
 hipError_t launch_exact1(int npt, int bs, int prio, int dom, bool lab, bool f53, const ExactArgs &a, hipStream_t s) {

@@ -36,6 +36,7 @@ RANK_MAX = 64  # KSCHED_RANK_MAX: entries ksched_rank keeps per pod
 GANG_MAX = 1024  # KSCHED_GANG_MAX: members of one gang
 # ksched_load_spread's caps: domains, groups, and groups * domains (the exact kernel's per-workgroup LDS table)
 SPREAD_MAX_DOMAINS, SPREAD_MAX_GROUPS, SPREAD_MAX_CELLS = 1024, 64, 4096
+EXT_MAX = 4  # KSCHED_EXT_MAX: extended-resource columns of ksched_load_ext's table
 BOUND_MAX_PER_NODE = 1024  # KSCHED_BOUND_MAX_PER_NODE: bound pods of one node in ksched_load_bound's table
 PREEMPT_NO_VICTIM_PRIO = -(1 << 31)  # KSCHED_PREEMPT_NO_VICTIM_PRIO: the key's max priority without a victim
 XCHG_HANDLE_BYTES = 128
@@ -119,6 +120,9 @@ SIGNATURES = [
     ("ksched_load_spread", C.c_int, [CTX, C.c_int32, I32P, C.c_int32, I32P, I32P]),
     ("ksched_read_spread", C.c_int, [CTX, I32P]),
     ("ksched_schedule_spread", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, I32P, U8P, I32P, F64P, I32P]),
+    ("ksched_load_ext", C.c_int, [CTX, C.c_int32, I64P]),
+    ("ksched_read_ext", C.c_int, [CTX, I64P]),
+    ("ksched_schedule_ext", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, I64P, I32P, F64P, I32P]),
     ("ksched_upload_pods", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P]),
     ("ksched_run", C.c_int, [CTX]),
     ("ksched_sync", C.c_int, [CTX]),

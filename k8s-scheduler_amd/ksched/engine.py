@@ -368,6 +368,42 @@ class Engine:
         self.p = p
         return oi, os_, of
 
+    def load_ext(self, node_ext):
+        """The extended-resource table of schedule_ext() (ksched_load_ext): node_ext[r, j], int64 [R, n] with R in
+        1..EXT_MAX, is node j's allocatable amount of resource r -- capacity minus what bound pods hold; any int64.  The
+        table then lives in the engine and moves with every schedule_ext(); load_nodes() invalidates it,
+        apply_delta() and restore_state() leave it alone."""
+        ne = np.ascontiguousarray(node_ext, dtype=np.int64)
+        assert ne.ndim == 2 and ne.shape[1] == max(self.n, 0)
+        self._chk(L.lib().ksched_load_ext(self._ctx, ne.shape[0], L.ptr(ne, C.c_int64)), "load_ext")
+        self._ext_shape = ne.shape
+
+    def read_ext(self):
+        """The extended-resource table, int64[R, n], as the last schedule_ext() (or load_ext()) left it."""
+        R, n = getattr(self, "_ext_shape", (0, 0))
+        out = np.empty(max(R * n, 1), np.int64)  # (never a null pointer: an engine without a table answers E_STATE)
+        self._chk(L.lib().ksched_read_ext(self._ctx, L.ptr(out, C.c_int64)), "read_ext")
+        return out[:R * n].reshape(R, n)
+
+    def schedule_ext(self, req_cpu, req_mem, req_pods, selector, req_ext=None):
+        """schedule() with the load_ext() table's columns in the fit predicate (ksched_schedule_ext): req_ext[r, i] >= 0,
+        int64 [R, p] (None: zeros), is pod i's request for resource r; a zero request is not checked, any other must
+        not exceed the node's column, and the placed pod's requests are subtracted from its node's columns.  One
+        launch of the exact kernel, whatever the engine's mode.  Returns (idx, score, feasible)."""
+        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
+        p = rc.shape[0]
+        assert rm.shape[0] == p and rp.shape[0] == p
+        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
+        re_ = None if req_ext is None else np.ascontiguousarray(req_ext, dtype=np.int64)
+        assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], p))
+        oi = np.empty(p, np.int32); os_ = np.empty(p, np.float64); of = np.empty(p, np.int32)
+        self._chk(L.lib().ksched_schedule_ext(self._ctx, p, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64),
+                                              L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64), L.ptr(re_, C.c_int64),
+                                              L.ptr(oi, C.c_int32), L.ptr(os_, C.c_double), L.ptr(of, C.c_int32)),
+                  "schedule_ext")
+        self.p = p
+        return oi, os_, of
+
 
 def engine_for(cl, mode: Optional[int] = None, **kw) -> Engine:
     """Engine configured for a ksched.cluster.Cluster and loaded with its nodes."""

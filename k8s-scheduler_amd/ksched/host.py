@@ -294,6 +294,48 @@ def spread_tables(nodes: List[Node], bound: List[Pod], pending: List[Pod]):
     return node_domain, np.asarray([c.max_skew for c in cons], np.int32), counts, group, enforce
 
 
+CORE_RESOURCES = ("cpu", "memory", "pods")
+
+
+def _whole(q, what) -> int:
+    """An extended-resource quantity: a plain decimal integer (Kubernetes admits only whole numbers for them)."""
+    s = str(q)
+    if not (s.isascii() and s.isdigit()):
+        raise ValueError(f"extended resource quantity {q!r} ({what}) is not a plain decimal integer")
+    return int(s)
+
+
+def ext_tables(nodes: List[Node], bound: List[Pod], pending: List[Pod], names: Optional[List[str]] = None):
+    """The inputs of ksched_load_ext / ksched_schedule_ext from Kubernetes objects.  names: the extended resources, by
+    default the sorted names that the pending pods' containers request other than cpu, memory and pods; more than
+    EXT_MAX is a ValueError.  A quantity is a plain decimal integer string (ValueError otherwise: no suffixes, no
+    fractions).  A node's amount is capacity[name] (absent: 0) minus the requests of the bound pods on it; a pod's
+    request is the sum over its containers.  Returns (names, node_ext int64[R, n], req_ext int64[R, p]); without any
+    name, one column "" of zeros (the table needs at least one)."""
+    if names is None:
+        names = sorted({k for pod in pending for c in pod.containers for k in c.requests if k not in CORE_RESOURCES})
+    names = list(names)
+    if len(names) > L.EXT_MAX:
+        raise ValueError(f"extended resources: at most {L.EXT_MAX} per call, got {names}")
+    R = max(len(names), 1)
+    node_ext = np.zeros((R, len(nodes)), np.int64)
+    req_ext = np.zeros((R, len(pending)), np.int64)
+    by_name = {nd.name: j for j, nd in enumerate(nodes)}
+    for r, name in enumerate(names):
+        for j, nd in enumerate(nodes):
+            if name in nd.capacity:
+                node_ext[r, j] = _whole(nd.capacity[name], f"node {nd.name}, {name}")
+        for pod in bound:
+            j = by_name.get(pod.node_name)
+            if j is not None:
+                node_ext[r, j] -= sum(_whole(c.requests[name], f"pod {pod.name}, {name}")
+                                      for c in pod.containers if name in c.requests)
+        for i, pod in enumerate(pending):
+            req_ext[r, i] = sum(_whole(c.requests[name], f"pod {pod.name}, {name}")
+                                for c in pod.containers if name in c.requests)
+    return names, node_ext, req_ext
+
+
 def parse_price(s: str) -> float:
     out = C.c_float(0)
     r = L.lib().ksched_parse_price(s.encode(), C.byref(out))
@@ -539,6 +581,31 @@ class FakeCluster:
         rc, rm, rp = pack_pods(pending)
         sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
         idx, _, _ = self.engine.schedule_spread(rc, rm, rp, sel, group, enforce)
+        out = []
+        for pod, i in zip(pending, idx):
+            if i == L.NO_FIT:
+                self.events.append(dict(reason="FailedScheduling", message=f"pod ({pod.name}) failed to fit in any node",
+                                        type="Warning", involved=pod.name))
+                out.append((pod, FitError(f"Unable to schedule pod ({pod.name}) failed to fit in any node")))
+            elif i == L.NO_POSITIVE_SCORE:
+                out.append((pod, NilNodeError(pod.name)))
+            else:
+                node = self.nodes[int(i)]
+                self.bind(pod, node)
+                out.append((pod, node))
+        return out
+
+    def schedule_ext(self, pending: Optional[List[Pod]] = None):
+        """schedule_pods with the pending pods' extended resources (ext_tables; ksched_schedule_ext) in the fit
+        predicate: the table is reloaded from self.pods' bound pods on every call, then one engine call resolves every
+        pending pod in order and the binds follow.  Returns (pod, node | Exception); a pod that fits nowhere gets the
+        usual FailedScheduling event (without per-node lines: the explain calls know no extended-resource reason)."""
+        pending = self.unscheduled_pods() if pending is None else pending
+        _, node_ext, req_ext = ext_tables(self.nodes, [p for p in self.pods if p.node_name], pending)
+        self.engine.load_ext(node_ext)
+        rc, rm, rp = pack_pods(pending)
+        sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
+        idx, _, _ = self.engine.schedule_ext(rc, rm, rp, sel, req_ext)
         out = []
         for pod, i in zip(pending, idx):
             if i == L.NO_FIT:
