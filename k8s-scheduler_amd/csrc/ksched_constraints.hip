@@ -1,0 +1,213 @@
+// ksched_constraints.hip -- libksched: the three extensions of exact mode above the kernel.  The schedule calls
+// (ksched_schedule_gangs / _spread / _ext) check and pack on the host, stage what they packed and run k_exact with their
+// extension (ExactRun, ksched_exact.h); the table calls load and read the context's spread and extended-resource tables.
+#include <cstring>
+
+#include <new>
+
+#include "ksched_ctx.h"
+#include "ksched_ext.h"
+#include "ksched_spread.h"
+
+using namespace ksched;
+
+namespace {
+
+// One array an extension's call stages for the kernel: the context's buffer, the packed host array (null: an output
+// of the kernel, reserved only) and its bytes.
+template <class T>
+struct Staged {
+    DevBuf<T> &buf;
+    const T *host;
+    size_t bytes;
+};
+
+// What the three schedule calls share once their checks have passed and their arrays are packed: the pods go up, the
+// staged arrays are reserved and copied in the stream of the kernel that reads them -- finished before the host arrays
+// go (ksched_upload_pods) -- then the run over them, the sync on both outcomes, and the results.
+template <class... S>
+int schedule_staged(ksched_ctx *c, ExactRun run, const char *name, int64_t p, const int64_t *rc, const int64_t *rm,
+                    const int64_t *rp, const uint64_t *sel, int32_t *oi, double *os, int32_t *of, const S &...staged) {
+    int r = ksched_upload_pods(c, p, rc, rm, rp, sel);
+    if (r != KSCHED_OK) return r;
+    hipError_t e = hipSuccess;
+    auto reserve = [&](const auto &st) { if (e == hipSuccess) e = st.buf.reserve(st.bytes); };
+    auto copy = [&](const auto &st) {
+        if (e == hipSuccess && st.host && st.bytes > 0)
+            e = hipMemcpyAsync(st.buf, st.host, st.bytes, hipMemcpyHostToDevice, c->stream);
+    };
+    (reserve(staged), ...);  // every array reserved before the first is copied; a step runs only if the last succeeded
+    (copy(staged), ...);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, KSCHED_E_DEVICE, std::string(name) + ": staging: " + hipGetErrorString(e));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((r = run_impl(c, run)) != KSCHED_OK) { ksched_sync(c); return r; }
+    if ((r = ksched_sync(c)) != KSCHED_OK) return r;
+    return ksched_download_results(c, p, oi, os, of);
+}
+
+}  // namespace
+
+extern "C" {
+
+// The spread table of ksched_schedule_spread: checked on the host (ksched_spread.h) before anything is allocated or
+// staged, then uploaded in the stream of the kernel that reads it.  Touches no node row; the context holds the new
+// table only once the last copy has landed, and the earlier one until the checks have passed.
+int ksched_load_spread(ksched_ctx *c, int32_t n_domains, const int32_t *node_domain, int32_t n_groups,
+                       const int32_t *max_skew, const int32_t *counts) {
+    if (!c) return KSCHED_E_INVALID;
+    static_assert(KSCHED_SPREAD_MAX_DOMAINS == kSpreadMaxDomains && KSCHED_SPREAD_MAX_GROUPS == kSpreadMaxGroups &&
+                  KSCHED_SPREAD_MAX_CELLS == kSpreadMaxCells, "spread constants");
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_spread before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "load_spread: spread scheduling is single-GPU (the exact kernel)");
+    try {
+        if (const char *why = spread_check_table(c->n_local, n_domains, node_domain, n_groups, max_skew, counts))
+            return fail(c, KSCHED_E_INVALID, std::string("load_spread: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "load_spread: host allocation failed");
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->spread_D = c->spread_S = 0;
+    ksched_bufs &d = *c->d;
+    const size_t n = (size_t)c->n_local, cells = (size_t)n_domains * (size_t)n_groups;
+    HIPCHK(c, d.sdom.reserve(n * 4)); HIPCHK(c, d.scnt.reserve(cells * 4)); HIPCHK(c, d.sskew.reserve((size_t)n_groups * 4));
+    if (n > 0) HIPCHK(c, hipMemcpyAsync(d.sdom, node_domain, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d.sskew, max_skew, (size_t)n_groups * 4, hipMemcpyHostToDevice, c->stream));
+    if (counts) HIPCHK(c, hipMemcpyAsync(d.scnt, counts, cells * 4, hipMemcpyHostToDevice, c->stream));
+    else HIPCHK(c, hipMemsetAsync(d.scnt, 0, cells * 4, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's arrays are free again
+    c->spread_D = n_domains; c->spread_S = n_groups;
+    return KSCHED_OK;
+}
+
+int ksched_read_spread(ksched_ctx *c, int32_t *out_counts) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->spread_S == 0) return fail(c, KSCHED_E_STATE, "read_spread: no spread table (ksched_load_spread after every ksched_load_nodes)");
+    if (!out_counts) return fail(c, KSCHED_E_INVALID, "read_spread: out_counts is NULL");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(out_counts, c->d->scnt, (size_t)c->spread_D * (size_t)c->spread_S * 4, hipMemcpyDeviceToHost));
+    return KSCHED_OK;
+}
+
+// The extended-resource table of ksched_schedule_ext: checked on the host (ksched_ext.h) before anything is allocated,
+// then uploaded in the stream of the kernel that reads it.  Touches no node row; the context holds the new table only
+// once the copy has landed, and the earlier one until the checks have passed.
+int ksched_load_ext(ksched_ctx *c, int32_t n_ext, const int64_t *node_ext) {
+    if (!c) return KSCHED_E_INVALID;
+    static_assert(KSCHED_EXT_MAX == kExtMax, "ext constants");
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_ext before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "load_ext: extended resources are single-GPU (the exact kernel)");
+    if (const char *why = ext_check_table(n_ext, node_ext)) return fail(c, KSCHED_E_INVALID, std::string("load_ext: ") + why);
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->ext_R = 0;
+    const size_t bytes = (size_t)n_ext * (size_t)c->n_local * 8;
+    HIPCHK(c, c->d->etab.reserve(bytes));
+    if (bytes > 0) HIPCHK(c, hipMemcpyAsync(c->d->etab, node_ext, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's array is free again
+    c->ext_R = n_ext;
+    return KSCHED_OK;
+}
+
+int ksched_read_ext(ksched_ctx *c, int64_t *out_ext) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->ext_R == 0) return fail(c, KSCHED_E_STATE, "read_ext: no extended-resource table (ksched_load_ext after every ksched_load_nodes)");
+    if (!out_ext) return fail(c, KSCHED_E_INVALID, "read_ext: out_ext is NULL");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = (size_t)c->ext_R * (size_t)c->n_local * 8;
+    if (bytes > 0) HIPCHK(c, hipMemcpy(out_ext, c->d->etab, bytes, hipMemcpyDeviceToHost));
+    return KSCHED_OK;
+}
+
+int ksched_schedule_gangs(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                          const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
+                          int32_t *oi, double *os, int32_t *of, int32_t *out_gang_placed) {
+    if (!c) return KSCHED_E_INVALID;
+    static_assert(KSCHED_GANG_MAX == kGangMax && KSCHED_GANG_REJECTED == kGangRejected, "gang constants");
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_gangs before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_gangs is single-GPU (the exact kernel)");
+    if (p < 0 || n_gangs < 0 || n_gangs > p || !gang_off || gang_off[0] != 0 || gang_off[n_gangs] != p)
+        return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_off must run from 0 to p over n_gangs <= p gangs");
+    // every offset and minimum is checked before anything is written or allocated: each offset above its
+    // predecessor and at most p (so every gang's pods lie in [0, p)), each gang within the cap
+    for (int64_t g = 0; g < n_gangs; ++g) {
+        if (gang_off[g + 1] <= gang_off[g] || gang_off[g + 1] > p)
+            return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_off must be strictly increasing and end at p");
+        const int64_t size = gang_off[g + 1] - gang_off[g];
+        if (size > KSCHED_GANG_MAX) return fail(c, KSCHED_E_INVALID, "schedule_gangs: a gang has more than KSCHED_GANG_MAX members");
+        if (gang_min && (gang_min[g] < 1 || gang_min[g] > size))
+            return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_min must be in 1..size");
+    }
+    // staged per pod, so the kernel reads a gang's end with its last member's request: 0, or size | minimum << 16
+    static_assert(KSCHED_GANG_MAX < (1 << 15), "ExactArgs::gang_end packs size and minimum into 16 bits each");
+    std::vector<int32_t> gend;
+    try {
+        gend.assign((size_t)p, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "schedule_gangs: host staging buffer");
+    }
+    for (int64_t g = 0; g < n_gangs; ++g) {
+        const int32_t size = (int32_t)(gang_off[g + 1] - gang_off[g]);
+        gend[(size_t)gang_off[g + 1] - 1] = size | (gang_min ? gang_min[g] : size) << 16;
+    }
+    const size_t ng = (size_t)n_gangs;
+    const int r = schedule_staged(c, kRunGang, "schedule_gangs", p, rc, rm, rp, sel, oi, os, of,
+                                  Staged<int32_t>{c->d->gend, gend.data(), (size_t)p * 4},
+                                  Staged<int32_t>{c->d->gplaced, nullptr, ng * 4});
+    if (r != KSCHED_OK) return r;
+    std::vector<int32_t> gp(ng);
+    if (ng > 0) HIPCHK(c, hipMemcpy(gp.data(), c->d->gplaced, ng * 4, hipMemcpyDeviceToHost));
+    c->st.placed = 0;
+    for (int32_t v : gp) c->st.placed += v;
+    if (out_gang_placed && ng > 0) std::memcpy(out_gang_placed, gp.data(), ng * 4);
+    return KSCHED_OK;
+}
+
+int ksched_schedule_spread(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                           const uint64_t *sel, const int32_t *spread_group, const uint8_t *spread_enforce, int32_t *oi,
+                           double *os, int32_t *of) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_spread before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_spread is single-GPU (the exact kernel)");
+    if (c->spread_S == 0)
+        return fail(c, KSCHED_E_STATE, "schedule_spread: no spread table (ksched_load_spread after every ksched_load_nodes)");
+    // every group is checked, and the per-pod words are packed, before anything is written or allocated
+    std::vector<int32_t> words;
+    try {
+        if (const char *why = spread_pack_words(p, c->spread_S, spread_group, spread_enforce, &words))
+            return fail(c, KSCHED_E_INVALID, std::string("schedule_spread: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "schedule_spread: host staging buffer");
+    }
+    return schedule_staged(c, kRunSpread, "schedule_spread", p, rc, rm, rp, sel, oi, os, of,
+                           Staged<int32_t>{c->d->sword, words.data(), (size_t)p * 4});
+}
+
+int ksched_schedule_ext(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                        const uint64_t *sel, const int64_t *req_ext, int32_t *oi, double *os, int32_t *of) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_ext before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_ext is single-GPU (the exact kernel)");
+    if (c->ext_R == 0)
+        return fail(c, KSCHED_E_STATE, "schedule_ext: no extended-resource table (ksched_load_ext after every ksched_load_nodes)");
+    // every request is checked, and the per-pod words are packed, before anything is written or allocated
+    std::vector<int64_t> reqs;
+    std::vector<int32_t> words;
+    try {
+        if (const char *why = ext_pack_pods(p, c->ext_R, req_ext, &reqs, &words))
+            return fail(c, KSCHED_E_INVALID, std::string("schedule_ext: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "schedule_ext: host staging buffer");
+    }
+    return schedule_staged(c, kRunExt, "schedule_ext", p, rc, rm, rp, sel, oi, os, of,
+                           Staged<int64_t>{c->d->ereq, reqs.data(), reqs.size() * 8},
+                           Staged<int32_t>{c->d->eword, words.data(), (size_t)p * 4});
+}
+
+}  // extern "C"
+

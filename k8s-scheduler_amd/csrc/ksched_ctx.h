@@ -1,6 +1,7 @@
 // ksched_ctx.h -- the context behind the C-ABI (include/ksched.h) and what the host units share: ksched_engine.hip
-// (lifecycle, run / sync, the enqueue paths), ksched_data.hip (node / pod data calls), ksched_xchg.hip (ranks meeting)
-// and ksched_diag.hip (environment, traces, dumps, device error decoding).  Internal: not part of the ABI.
+// (lifecycle, run / sync, the enqueue paths), ksched_data.hip (node / pod data calls), ksched_constraints.hip (the
+// gang / spread / extended-resource calls of exact mode), ksched_xchg.hip (ranks meeting) and ksched_diag.hip
+// (environment, traces, dumps, device error decoding).  Internal: not part of the ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 #include <vector>
 
 #include "ksched.h"
+#include "ksched_exact.h"
 #include "ksched_kernels.h"
 
 // In-process rank group (include/ksched.h).  The all-gather is host-coordinated and synchronous:
@@ -286,6 +288,9 @@ bool lg_meet(ksched_lgroup *g, Mine mine, Last last) {
     }
     return true;
 }
+
+// ksched_engine.hip
+int run_impl(ksched_ctx *c, ExactRun run);  // ksched_run (kRunPlain), or the exact kernel over what an extension's call staged
 
 // ksched_xchg.hip
 bool group_min(ksched_group *g, int v, int *out);  // all ranks meet; the minimum of their values (false: a rank never arrived)

@@ -6,10 +6,8 @@
 #include <new>
 
 #include "ksched_ctx.h"
-#include "ksched_ext.h"
 #include "ksched_preempt.h"
 #include "ksched_rank.h"
-#include "ksched_spread.h"
 
 using namespace ksched;
 
@@ -508,78 +506,6 @@ int ksched_load_bound(ksched_ctx *c, int64_t nb, const int32_t *node_idx, const 
     HIPCHK(c, up(d.bseg, h.seg.data(), n * 4));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go away with this call
     c->bound_valid = true;
-    return KSCHED_OK;
-}
-
-// The spread table of ksched_schedule_spread: checked on the host (ksched_spread.h) before anything is allocated or
-// staged, then uploaded in the stream of the kernel that reads it.  Touches no node row; the context holds the new
-// table only once the last copy has landed, and the earlier one until the checks have passed.
-int ksched_load_spread(ksched_ctx *c, int32_t n_domains, const int32_t *node_domain, int32_t n_groups,
-                       const int32_t *max_skew, const int32_t *counts) {
-    if (!c) return KSCHED_E_INVALID;
-    static_assert(KSCHED_SPREAD_MAX_DOMAINS == kSpreadMaxDomains && KSCHED_SPREAD_MAX_GROUPS == kSpreadMaxGroups &&
-                  KSCHED_SPREAD_MAX_CELLS == kSpreadMaxCells, "spread constants");
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_spread before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "load_spread: spread scheduling is single-GPU (the exact kernel)");
-    try {
-        if (const char *why = spread_check_table(c->n_local, n_domains, node_domain, n_groups, max_skew, counts))
-            return fail(c, KSCHED_E_INVALID, std::string("load_spread: ") + why);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "load_spread: host allocation failed");
-    }
-    HIPCHK(c, hipSetDevice(c->dev));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->spread_D = c->spread_S = 0;
-    ksched_bufs &d = *c->d;
-    const size_t n = (size_t)c->n_local, cells = (size_t)n_domains * (size_t)n_groups;
-    HIPCHK(c, d.sdom.reserve(n * 4)); HIPCHK(c, d.scnt.reserve(cells * 4)); HIPCHK(c, d.sskew.reserve((size_t)n_groups * 4));
-    if (n > 0) HIPCHK(c, hipMemcpyAsync(d.sdom, node_domain, n * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d.sskew, max_skew, (size_t)n_groups * 4, hipMemcpyHostToDevice, c->stream));
-    if (counts) HIPCHK(c, hipMemcpyAsync(d.scnt, counts, cells * 4, hipMemcpyHostToDevice, c->stream));
-    else HIPCHK(c, hipMemsetAsync(d.scnt, 0, cells * 4, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's arrays are free again
-    c->spread_D = n_domains; c->spread_S = n_groups;
-    return KSCHED_OK;
-}
-
-int ksched_read_spread(ksched_ctx *c, int32_t *out_counts) {
-    if (!c) return KSCHED_E_INVALID;
-    if (c->spread_S == 0) return fail(c, KSCHED_E_STATE, "read_spread: no spread table (ksched_load_spread after every ksched_load_nodes)");
-    if (!out_counts) return fail(c, KSCHED_E_INVALID, "read_spread: out_counts is NULL");
-    HIPCHK(c, hipSetDevice(c->dev));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(out_counts, c->d->scnt, (size_t)c->spread_D * (size_t)c->spread_S * 4, hipMemcpyDeviceToHost));
-    return KSCHED_OK;
-}
-
-// The extended-resource table of ksched_schedule_ext: checked on the host (ksched_ext.h) before anything is allocated,
-// then uploaded in the stream of the kernel that reads it.  Touches no node row; the context holds the new table only
-// once the copy has landed, and the earlier one until the checks have passed.
-int ksched_load_ext(ksched_ctx *c, int32_t n_ext, const int64_t *node_ext) {
-    if (!c) return KSCHED_E_INVALID;
-    static_assert(KSCHED_EXT_MAX == kExtMax, "ext constants");
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_ext before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "load_ext: extended resources are single-GPU (the exact kernel)");
-    if (const char *why = ext_check_table(n_ext, node_ext)) return fail(c, KSCHED_E_INVALID, std::string("load_ext: ") + why);
-    HIPCHK(c, hipSetDevice(c->dev));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->ext_R = 0;
-    const size_t bytes = (size_t)n_ext * (size_t)c->n_local * 8;
-    HIPCHK(c, c->d->etab.reserve(bytes));
-    if (bytes > 0) HIPCHK(c, hipMemcpyAsync(c->d->etab, node_ext, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's array is free again
-    c->ext_R = n_ext;
-    return KSCHED_OK;
-}
-
-int ksched_read_ext(ksched_ctx *c, int64_t *out_ext) {
-    if (!c) return KSCHED_E_INVALID;
-    if (c->ext_R == 0) return fail(c, KSCHED_E_STATE, "read_ext: no extended-resource table (ksched_load_ext after every ksched_load_nodes)");
-    if (!out_ext) return fail(c, KSCHED_E_INVALID, "read_ext: out_ext is NULL");
-    HIPCHK(c, hipSetDevice(c->dev));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const size_t bytes = (size_t)c->ext_R * (size_t)c->n_local * 8;
-    if (bytes > 0) HIPCHK(c, hipMemcpy(out_ext, c->d->etab, bytes, hipMemcpyDeviceToHost));
     return KSCHED_OK;
 }
 

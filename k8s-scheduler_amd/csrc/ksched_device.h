@@ -97,6 +97,19 @@ struct alignas(8) Rec {
 };
 static_assert(sizeof(Rec) == 56, "Rec layout");
 
+// The pending pods (SoA) and the per-pod results, as every scheduling kernel's arguments carry them.
+struct PodArgs {
+    const int64_t *rc, *rm, *rp;
+    const uint64_t *sel;
+    int64_t p;
+};
+
+struct OutArgs {
+    int32_t *idx;
+    double *score;
+    int32_t *feas;
+};
+
 // Rec loads / stores, plain or coherent (COH: 8-byte sc1 accesses, Rec words w0..w6).
 template <bool COH>
 __device__ __forceinline__ Rec load_rec(const Rec *p) {
@@ -244,6 +257,14 @@ __device__ __forceinline__ bool pair_key_fast(bool feas, int64_t rc, int64_t rm,
 }
 
 __device__ __forceinline__ double recip_or_zero(int64_t a, double af) { return a == 0 ? 0.0 : recip(af); }
+
+// a node row's allocatable with its af / y kept in sync (every device-side writer of a row goes through here)
+__device__ __forceinline__ void set_node(NodeRec *nd, int64_t a0, int64_t a1, int64_t a2) {
+    nd->a[0] = a0; nd->a[1] = a1; nd->a[2] = a2;
+    const double f0 = (double)a0, f1 = (double)a1, f2 = (double)a2;
+    nd->af[0] = f0; nd->af[1] = f1; nd->af[2] = f2;
+    nd->y[0] = recip_or_zero(a0, f0); nd->y[1] = recip_or_zero(a1, f1); nd->y[2] = recip_or_zero(a2, f2);
+}
 
 // ---- f32 screen of the resource score (the persistent pipeline's screened scan) ----
 // With fractions f_k = r_k / a_k (0 < a_k < 2^52, 0 <= r_k < 2^52) the reference score (anchor/priorities.go:

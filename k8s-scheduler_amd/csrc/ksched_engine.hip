@@ -10,8 +10,6 @@
 #include <cstring>
 
 #include "ksched_ctx.h"
-#include "ksched_ext.h"
-#include "ksched_spread.h"
 
 using namespace ksched;
 
@@ -464,14 +462,9 @@ int enqueue_persistent(ksched_ctx *c) {
     return KSCHED_OK;
 }
 
-// gang: the run of ksched_schedule_gangs (the staged gangs in d->gend) -- always k_exact<GANG>, the
-// multi-slot kernel, under the same geometry and launch rule as a plain exact run; spread: the run of
-// ksched_schedule_spread (the staged words in d->sword, the context's table) -- always k_exact<SPREAD>, likewise;
-// ext: the run of ksched_schedule_ext (the staged requests in d->ereq / d->eword, the context's table) -- always
-// k_exact<EXT>, likewise
-enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3 };
+// run (ExactRun, ksched_exact.h): a plain exact run, or the run of ksched_schedule_gangs / _spread / _ext over what
+// that call staged -- always k_exact, the multi-slot kernel, under the same geometry and launch rule as a plain run
 int enqueue_exact(ksched_ctx *c, ExactRun run) {
-    const bool gang = run == kRunGang, spread = run == kRunSpread, ext = run == kRunExt;
     if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "exact mode is single-GPU; use batched mode across ranks");
     const int64_t n = c->n_local;
     // the whole node set in ONE workgroup's registers (k_exact1): no cross-workgroup exchange per pod
@@ -482,7 +475,7 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
     a.pods = PodArgs{c->d->rc, c->d->rm, c->d->rp, c->d->sel, c->p};
     a.out = OutArgs{c->d->oidx, c->d->osc, c->d->ofeas};
     a.err = c->d->err;
-    if (!gang && !spread && !ext && c->o.exact_wgs <= 1 && n > 0 && n <= (int64_t)kExact1Block * max1 && (!price || c->perm_n == n)) {
+    if (run == kRunPlain && c->o.exact_wgs <= 1 && n > 0 && n <= (int64_t)kExact1Block * max1 && (!price || c->perm_n == n)) {
         int bs = kExact1Block;
         if (price && c->diag.exact1_bs == 512 && n <= 5120) bs = 512;
         if (price && c->diag.exact1_bs == 256 && n <= 5120) bs = 256;
@@ -522,29 +515,81 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
     a.timeout_ticks = c->diag.exchange_timeout_ms * 100000;  // 100 MHz wall clock
     int e0 = -1;
     HIPCHK(c, ev_begin(c, c->o.timing != 0, &e0, c->stream));
-    if (gang) {
-        a.gang_end = c->d->gend; a.gang_placed = c->d->gplaced;
-        HIPCHK(c, launch_exact_gang(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
-                                    G > 1 && !c->diag.plain_launch, c->stream));
-    } else if (spread) {
-        a.sp_dom = c->d->sdom; a.sp_counts = c->d->scnt; a.sp_skew = c->d->sskew;
-        a.sp_D = c->spread_D; a.sp_S = c->spread_S; a.sp_word = c->d->sword;
-        HIPCHK(c, launch_exact_spread(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
-                                      G > 1 && !c->diag.plain_launch, c->stream));
-    } else if (ext) {
-        a.ext = c->d->etab; a.ext_req = c->d->ereq; a.ext_word = c->d->eword; a.n_ext = c->ext_R;
-        HIPCHK(c, launch_exact_ext(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
-                                   G > 1 && !c->diag.plain_launch, c->stream));
-    } else {
-        HIPCHK(c, launch_exact(npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
-                               G > 1 && !c->diag.plain_launch, c->stream));
+    switch (run) {  // the extension's fields: what its call staged, and the context's table
+        case kRunPlain: break;
+        case kRunGang:
+            a.gang_end = c->d->gend; a.gang_placed = c->d->gplaced;
+            break;
+        case kRunSpread:
+            a.sp_dom = c->d->sdom; a.sp_counts = c->d->scnt; a.sp_skew = c->d->sskew;
+            a.sp_D = c->spread_D; a.sp_S = c->spread_S; a.sp_word = c->d->sword;
+            break;
+        case kRunExt:
+            a.ext = c->d->etab; a.ext_req = c->d->ereq; a.ext_word = c->d->eword; a.n_ext = c->ext_R;
+            break;
     }
+    HIPCHK(c, launch_exact(run, npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
+                           G > 1 && !c->diag.plain_launch, c->stream));
     HIPCHK(c, ev_end(c, c->o.timing != 0, 0, e0, c->p * n, c->stream));
     c->st.pair_evals = c->p * n;
     return KSCHED_OK;
 }
 
 }  // namespace
+
+// ksched_run, or the run of ksched_schedule_gangs / ksched_schedule_spread / ksched_schedule_ext: the exact kernel over
+// the staged gangs / spread words / extended requests whatever opts.mode
+int ksched::run_impl(ksched_ctx *c, ExactRun run) {
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "run before load_nodes");
+    if (c->o.nranks > 1 && !c->comm && !c->group && !c->xchg_ready)
+        return fail(c, KSCHED_E_STATE, "run: multi-rank context without ksched_set_comm / ksched_set_group / "
+                                       "ksched_xchg_import");
+    HIPCHK(c, hipSetDevice(c->dev));
+    c->err.clear();
+    c->st = ksched_stats{};
+    c->timed.clear();
+    c->ev_used = 0;
+    c->st.pods = c->p;
+    int mode = c->o.mode;
+    if (mode == KSCHED_MODE_AUTO) mode = c->o.nranks > 1 ? KSCHED_MODE_BATCHED : KSCHED_MODE_EXACT;
+    if (run != kRunPlain) mode = KSCHED_MODE_EXACT;
+    c->xchg_run = c->xchg_ready && mode == KSCHED_MODE_BATCHED && c->p > 0;
+    // a multi-rank batched call needs a transport: the device exchange, an RCCL communicator or a rank group
+    // (never a rank committing from its own shard alone)
+    if (c->o.nranks > 1 && mode == KSCHED_MODE_BATCHED && c->p > 0 && !c->xchg_run && !c->comm && !c->group)
+        return fail(c, KSCHED_E_STATE, "run: multi-rank context without an exchange transport");
+    if (int rr = decide_fast53(c)) return rr;
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    int r = KSCHED_OK;
+    if (c->p > 0) {
+        c->persist_stats = false;
+        if (mode == KSCHED_MODE_EXACT) {
+            r = enqueue_exact(c, run);
+            c->st.pipeline = KSCHED_PIPE_EXACT;
+        } else {
+            r = enqueue_persistent(c);
+            c->st.pipeline = KSCHED_PIPE_PERSISTENT;
+            if (r == 1 && c->xchg_run && !c->comm)
+                r = fail(c, KSCHED_E_INVALID, "node-sharded exchange: the persistent pipeline does not fit this "
+                                              "configuration and no RCCL communicator is set");
+            if (r == 1) {  // not eligible: the stream pipeline
+                c->xchg_run = false;
+                r = enqueue_batched(c);
+                c->st.pipeline = c->B > 64 || c->o.commit_impl == KSCHED_COMMIT_SEQUENTIAL ? KSCHED_PIPE_STREAM_SEQ
+                                                                                          : KSCHED_PIPE_STREAM;
+            }
+        }
+    }
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    c->running = r == KSCHED_OK;
+    // the call's commits move every allocatable by at most the sum of the staged requests: keep the
+    // FAST53 bound true of the state the NEXT call starts from
+    if (r == KSCHED_OK) c->max_abs_alloc = sat_add(c->max_abs_alloc, c->sum_abs_req);
+    // (a rolled-back gang leaves no final placements for ksched_explain_batch to rebuild a pod's state from)
+    // (and the explain calls know no spread or extended-resource reason)
+    c->explain_valid = r == KSCHED_OK && run == kRunPlain;
+    return r;
+}
 
 extern "C" {
 
@@ -641,60 +686,6 @@ int ksched_destroy(ksched_ctx *c) {
 
 const char *ksched_last_error(const ksched_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
-// ksched_run, or the run of ksched_schedule_gangs / ksched_schedule_spread / ksched_schedule_ext: the exact kernel over
-// the staged gangs / spread words / extended requests whatever opts.mode
-static int run_impl(ksched_ctx *c, ExactRun run) {
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "run before load_nodes");
-    if (c->o.nranks > 1 && !c->comm && !c->group && !c->xchg_ready)
-        return fail(c, KSCHED_E_STATE, "run: multi-rank context without ksched_set_comm / ksched_set_group / "
-                                       "ksched_xchg_import");
-    HIPCHK(c, hipSetDevice(c->dev));
-    c->err.clear();
-    c->st = ksched_stats{};
-    c->timed.clear();
-    c->ev_used = 0;
-    c->st.pods = c->p;
-    int mode = c->o.mode;
-    if (mode == KSCHED_MODE_AUTO) mode = c->o.nranks > 1 ? KSCHED_MODE_BATCHED : KSCHED_MODE_EXACT;
-    if (run != kRunPlain) mode = KSCHED_MODE_EXACT;
-    c->xchg_run = c->xchg_ready && mode == KSCHED_MODE_BATCHED && c->p > 0;
-    // a multi-rank batched call needs a transport: the device exchange, an RCCL communicator or a rank group
-    // (never a rank committing from its own shard alone)
-    if (c->o.nranks > 1 && mode == KSCHED_MODE_BATCHED && c->p > 0 && !c->xchg_run && !c->comm && !c->group)
-        return fail(c, KSCHED_E_STATE, "run: multi-rank context without an exchange transport");
-    if (int rr = decide_fast53(c)) return rr;
-    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    int r = KSCHED_OK;
-    if (c->p > 0) {
-        c->persist_stats = false;
-        if (mode == KSCHED_MODE_EXACT) {
-            r = enqueue_exact(c, run);
-            c->st.pipeline = KSCHED_PIPE_EXACT;
-        } else {
-            r = enqueue_persistent(c);
-            c->st.pipeline = KSCHED_PIPE_PERSISTENT;
-            if (r == 1 && c->xchg_run && !c->comm)
-                r = fail(c, KSCHED_E_INVALID, "node-sharded exchange: the persistent pipeline does not fit this "
-                                              "configuration and no RCCL communicator is set");
-            if (r == 1) {  // not eligible: the stream pipeline
-                c->xchg_run = false;
-                r = enqueue_batched(c);
-                c->st.pipeline = c->B > 64 || c->o.commit_impl == KSCHED_COMMIT_SEQUENTIAL ? KSCHED_PIPE_STREAM_SEQ
-                                                                                          : KSCHED_PIPE_STREAM;
-            }
-        }
-    }
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    c->running = r == KSCHED_OK;
-    // the call's commits move every allocatable by at most the sum of the staged requests: keep the
-    // FAST53 bound true of the state the NEXT call starts from
-    if (r == KSCHED_OK) c->max_abs_alloc = sat_add(c->max_abs_alloc, c->sum_abs_req);
-    // (a rolled-back gang leaves no final placements for ksched_explain_batch to rebuild a pod's state from)
-    // (and the explain calls know no spread or extended-resource reason)
-    c->explain_valid = r == KSCHED_OK && run == kRunPlain;
-    return r;
-}
-
 int ksched_run(ksched_ctx *c) {
     if (!c) return KSCHED_E_INVALID;
     return run_impl(c, kRunPlain);
@@ -782,113 +773,6 @@ int ksched_schedule(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *
     int r = ksched_upload_pods(c, p, rc, rm, rp, sel);
     if (r != KSCHED_OK) return r;
     if ((r = ksched_run(c)) != KSCHED_OK) { ksched_sync(c); return r; }
-    if ((r = ksched_sync(c)) != KSCHED_OK) return r;
-    return ksched_download_results(c, p, oi, os, of);
-}
-
-int ksched_schedule_gangs(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
-                          const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
-                          int32_t *oi, double *os, int32_t *of, int32_t *out_gang_placed) {
-    if (!c) return KSCHED_E_INVALID;
-    static_assert(KSCHED_GANG_MAX == kGangMax && KSCHED_GANG_REJECTED == kGangRejected, "gang constants");
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_gangs before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_gangs is single-GPU (the exact kernel)");
-    if (p < 0 || n_gangs < 0 || n_gangs > p || !gang_off || gang_off[0] != 0 || gang_off[n_gangs] != p)
-        return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_off must run from 0 to p over n_gangs <= p gangs");
-    // every offset and minimum is checked before anything is written or allocated: each offset above its
-    // predecessor and at most p (so every gang's pods lie in [0, p)), each gang within the cap
-    for (int64_t g = 0; g < n_gangs; ++g) {
-        if (gang_off[g + 1] <= gang_off[g] || gang_off[g + 1] > p)
-            return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_off must be strictly increasing and end at p");
-        const int64_t size = gang_off[g + 1] - gang_off[g];
-        if (size > KSCHED_GANG_MAX) return fail(c, KSCHED_E_INVALID, "schedule_gangs: a gang has more than KSCHED_GANG_MAX members");
-        if (gang_min && (gang_min[g] < 1 || gang_min[g] > size))
-            return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_min must be in 1..size");
-    }
-    // staged per pod, so the kernel reads a gang's end with its last member's request: 0, or size | minimum << 16
-    static_assert(KSCHED_GANG_MAX < (1 << 15), "ExactArgs::gang_end packs size and minimum into 16 bits each");
-    std::vector<int32_t> gend;
-    try {
-        gend.assign((size_t)p, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "schedule_gangs: host staging buffer");
-    }
-    for (int64_t g = 0; g < n_gangs; ++g) {
-        const int32_t size = (int32_t)(gang_off[g + 1] - gang_off[g]);
-        gend[(size_t)gang_off[g + 1] - 1] = size | (gang_min ? gang_min[g] : size) << 16;
-    }
-    int r = ksched_upload_pods(c, p, rc, rm, rp, sel);
-    if (r != KSCHED_OK) return r;
-    const size_t ng = (size_t)n_gangs;
-    HIPCHK(c, c->d->gend.reserve((size_t)p * 4)); HIPCHK(c, c->d->gplaced.reserve(ng * 4));
-    // in the stream of the kernel that reads it, finished before `gend` goes (ksched_upload_pods)
-    if (p > 0) HIPCHK(c, hipMemcpyAsync(c->d->gend, gend.data(), (size_t)p * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((r = run_impl(c, kRunGang)) != KSCHED_OK) { ksched_sync(c); return r; }
-    if ((r = ksched_sync(c)) != KSCHED_OK) return r;
-    if ((r = ksched_download_results(c, p, oi, os, of)) != KSCHED_OK) return r;
-    std::vector<int32_t> gp(ng);
-    if (ng > 0) HIPCHK(c, hipMemcpy(gp.data(), c->d->gplaced, ng * 4, hipMemcpyDeviceToHost));
-    c->st.placed = 0;
-    for (int32_t v : gp) c->st.placed += v;
-    if (out_gang_placed && ng > 0) std::memcpy(out_gang_placed, gp.data(), ng * 4);
-    return KSCHED_OK;
-}
-
-int ksched_schedule_spread(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
-                           const uint64_t *sel, const int32_t *spread_group, const uint8_t *spread_enforce, int32_t *oi,
-                           double *os, int32_t *of) {
-    if (!c) return KSCHED_E_INVALID;
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_spread before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_spread is single-GPU (the exact kernel)");
-    if (c->spread_S == 0)
-        return fail(c, KSCHED_E_STATE, "schedule_spread: no spread table (ksched_load_spread after every ksched_load_nodes)");
-    // every group is checked, and the per-pod words are packed, before anything is written or allocated
-    std::vector<int32_t> words;
-    try {
-        if (const char *why = spread_pack_words(p, c->spread_S, spread_group, spread_enforce, &words))
-            return fail(c, KSCHED_E_INVALID, std::string("schedule_spread: ") + why);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "schedule_spread: host staging buffer");
-    }
-    int r = ksched_upload_pods(c, p, rc, rm, rp, sel);
-    if (r != KSCHED_OK) return r;
-    HIPCHK(c, c->d->sword.reserve((size_t)p * 4));
-    // in the stream of the kernel that reads it, finished before `words` goes (ksched_upload_pods)
-    if (p > 0) HIPCHK(c, hipMemcpyAsync(c->d->sword, words.data(), (size_t)p * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((r = run_impl(c, kRunSpread)) != KSCHED_OK) { ksched_sync(c); return r; }
-    if ((r = ksched_sync(c)) != KSCHED_OK) return r;
-    return ksched_download_results(c, p, oi, os, of);
-}
-
-int ksched_schedule_ext(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
-                        const uint64_t *sel, const int64_t *req_ext, int32_t *oi, double *os, int32_t *of) {
-    if (!c) return KSCHED_E_INVALID;
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_ext before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_ext is single-GPU (the exact kernel)");
-    if (c->ext_R == 0)
-        return fail(c, KSCHED_E_STATE, "schedule_ext: no extended-resource table (ksched_load_ext after every ksched_load_nodes)");
-    // every request is checked, and the per-pod words are packed, before anything is written or allocated
-    std::vector<int64_t> reqs;
-    std::vector<int32_t> words;
-    try {
-        if (const char *why = ext_pack_pods(p, c->ext_R, req_ext, &reqs, &words))
-            return fail(c, KSCHED_E_INVALID, std::string("schedule_ext: ") + why);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "schedule_ext: host staging buffer");
-    }
-    int r = ksched_upload_pods(c, p, rc, rm, rp, sel);
-    if (r != KSCHED_OK) return r;
-    HIPCHK(c, c->d->ereq.reserve(reqs.size() * 8));
-    HIPCHK(c, c->d->eword.reserve((size_t)p * 4));
-    // in the stream of the kernel that reads them, finished before the vectors go (ksched_upload_pods)
-    if (p > 0) {
-        HIPCHK(c, hipMemcpyAsync(c->d->ereq, reqs.data(), reqs.size() * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d->eword, words.data(), (size_t)p * 4, hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((r = run_impl(c, kRunExt)) != KSCHED_OK) { ksched_sync(c); return r; }
     if ((r = ksched_sync(c)) != KSCHED_OK) return r;
     return ksched_download_results(c, p, oi, os, of);
 }

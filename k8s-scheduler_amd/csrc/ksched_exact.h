@@ -1,0 +1,66 @@
+// ksched_exact.h -- exact mode (ksched_exact.hip): the arguments of k_exact / k_exact1, the constants of the three
+// extensions of k_exact (gangs, topology spread, extended resources) and the launchers.  ksched_ctx.h includes it
+// beside ksched_kernels.h, so the host units keep one include and no other device unit depends on it.
+#pragma once
+
+#include "ksched_device.h"
+
+namespace ksched {
+
+// Which extension of k_exact a launch runs (at most one): the value travels from the C entry point
+// (ksched_schedule_gangs / _spread / _ext, ksched_constraints.hip) through run_impl and enqueue_exact to the kernel's
+// template parameter.  kRunGang: the staged gangs in d->gend; kRunSpread: the staged words in d->sword and the context's
+// table; kRunExt: the staged requests in d->ereq / d->eword and the context's table.  Every run but kRunPlain is the
+// multi-slot kernel k_exact whatever opts.mode, under the same geometry and launch rule as a plain exact run.
+enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3 };
+
+struct ExactArgs {
+    NodeRec *nodes;
+    int64_t n;
+    int32_t G;        // workgroups (all co-resident)
+    int32_t per_wg;   // nodes per workgroup
+    PodArgs pods;
+    OutArgs out;
+    uint64_t *slots;  // [2][G][4] granules {epoch:32 | value:32}; zeroed before every launch
+    int32_t *err;     // device error word (kErrExactExchange)
+    int64_t timeout_ticks;
+    const int32_t *perm;  // k_exact1: slot -> node (best-price: nodes by price asc, index asc); null: slot = node
+    // k_exact<GANG> (ksched_schedule_gangs): per pod, 0 or -- at the last member of its gang -- the gang's size
+    // (<= kGangMax) | the members it needs << 16 (both fit 15 bits: kGangMax < 2^15, asserted where the host packs
+    // them); the kernel reads it with the pod's request
+    const int32_t *gang_end;
+    int32_t *gang_placed;     // out: members bound per gang, 0 for a rejected one (may be null)
+    // k_exact<SPREAD> (ksched_schedule_spread): the context's spread table and the per-pod word
+    const int32_t *sp_dom;    // [n] node -> topology domain in [0, sp_D), or -1: the node does not carry the key
+    int32_t *sp_counts;       // [sp_S][sp_D] matching pods bound per (group, domain): read at entry, written at exit
+    const int32_t *sp_skew;   // [sp_S] the groups' maximum skew
+    int32_t sp_D, sp_S;       // sp_S * sp_D <= kSpreadMaxCells
+    const int32_t *sp_word;   // per pod: -1 (no group), or group << 1 | enforce; the kernel reads it with the request
+    // k_exact<EXT> (ksched_schedule_ext): the context's extended-resource table and the staged requests
+    int64_t *ext;             // [n_ext][n] allocatable per (resource, node): read at entry, written at exit
+    const int64_t *ext_req;   // [p][kExtMax] requests, pod-major (columns at and beyond n_ext: 0)
+    const int32_t *ext_word;  // per pod: bit r set where ext_req[i][r] != 0; the kernel reads it with the request
+    int32_t n_ext;            // 1..kExtMax
+};
+constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
+constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
+constexpr int kSpreadMaxDomains = 1024; // KSCHED_SPREAD_MAX_DOMAINS
+constexpr int kSpreadMaxGroups = 64;    // KSCHED_SPREAD_MAX_GROUPS
+constexpr int kSpreadMaxCells = 4096;   // KSCHED_SPREAD_MAX_CELLS: the LDS table of every workgroup, 16 KiB
+constexpr int kExtMax = 4;              // KSCHED_EXT_MAX: columns of the dynamic LDS table, kExtMax * 256 * 8 slots * 8 B = 64 KiB
+
+constexpr int kExactBlock = 256;
+constexpr int kExact1Block = 1024;  // k_exact1: the whole node set in one workgroup
+
+// host-side launchers (ksched_exact.hip).  fast53: every allocatable and request magnitude stays
+// below 2^52 for the whole call (host-checked), enabling (double)(a-r) == (double)a - (double)r.
+// One launch of k_exact<run>.  kRunGang: a.gang_end set (a.gang_placed may be null); kRunSpread: a.sp_* set; kRunExt:
+// a.ext* set, dynamic LDS of a.n_ext * block * npt * 8 bytes.  (An extension never runs k_exact1: the one-workgroup
+// kernel knows no gang log, spread table or extended-resource table.)
+hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
+                        bool cooperative, hipStream_t s);
+// exact mode on one workgroup of bs threads, npt node slots each: bs 1024 with npt 1-4 (resource) or 1-6, 8, 12, 16
+// (best-price); best-price also (512, 10) and (256, 20)
+hipError_t launch_exact1(int npt, int bs, int prio, int dom, bool lab, bool f53, const ExactArgs &a, hipStream_t s);
+
+}  // namespace ksched

@@ -2,6 +2,7 @@
 //
 // Exact mode  : k_exact        persistent, node-per-lane, node state in registers, one grid-wide
 //                              arg-best per pod through tagged 8-byte granules (no host round trip).
+//                              A unit of its own: ksched_exact.h / ksched_exact.hip (not included here).
 // Batched mode: k_score_topk   pod-per-lane fused predicate + score + per-lane top-K over a node
 //                              chunk (node rows are wave-uniform -> scalar loads);
 //               k_merge        sorted-list merge of the ranks' lists, one wave per pod, DPP/shuffle arg-best;
@@ -171,53 +172,6 @@ struct alignas(16) RescueReq {
 };
 constexpr size_t kRescueResOff = (sizeof(RescueReq) + 127) / 128 * 128;
 constexpr size_t rescue_bytes(int B) { return kRescueResOff + (size_t)B * sizeof(Rec); }
-
-struct PodArgs {
-    const int64_t *rc, *rm, *rp;
-    const uint64_t *sel;
-    int64_t p;
-};
-
-struct OutArgs {
-    int32_t *idx;
-    double *score;
-    int32_t *feas;
-};
-
-struct ExactArgs {
-    NodeRec *nodes;
-    int64_t n;
-    int32_t G;        // workgroups (all co-resident)
-    int32_t per_wg;   // nodes per workgroup
-    PodArgs pods;
-    OutArgs out;
-    uint64_t *slots;  // [2][G][4] granules {epoch:32 | value:32}; zeroed before every launch
-    int32_t *err;     // device error word (kErrExactExchange)
-    int64_t timeout_ticks;
-    const int32_t *perm;  // k_exact1: slot -> node (best-price: nodes by price asc, index asc); null: slot = node
-    // k_exact<GANG> (ksched_schedule_gangs): per pod, 0 or -- at the last member of its gang -- the gang's size
-    // (<= kGangMax) | the members it needs << 16 (both fit 15 bits: kGangMax < 2^15, asserted where the host packs
-    // them); the kernel reads it with the pod's request
-    const int32_t *gang_end;
-    int32_t *gang_placed;     // out: members bound per gang, 0 for a rejected one (may be null)
-    // k_exact<SPREAD> (ksched_schedule_spread): the context's spread table and the per-pod word
-    const int32_t *sp_dom;    // [n] node -> topology domain in [0, sp_D), or -1: the node does not carry the key
-    int32_t *sp_counts;       // [sp_S][sp_D] matching pods bound per (group, domain): read at entry, written at exit
-    const int32_t *sp_skew;   // [sp_S] the groups' maximum skew
-    int32_t sp_D, sp_S;       // sp_S * sp_D <= kSpreadMaxCells
-    const int32_t *sp_word;   // per pod: -1 (no group), or group << 1 | enforce; the kernel reads it with the request
-    // k_exact<EXT> (ksched_schedule_ext): the context's extended-resource table and the staged requests
-    int64_t *ext;             // [n_ext][n] allocatable per (resource, node): read at entry, written at exit
-    const int64_t *ext_req;   // [p][kExtMax] requests, pod-major (columns at and beyond n_ext: 0)
-    const int32_t *ext_word;  // per pod: bit r set where ext_req[i][r] != 0; the kernel reads it with the request
-    int32_t n_ext;            // 1..kExtMax
-};
-constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
-constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
-constexpr int kSpreadMaxDomains = 1024; // KSCHED_SPREAD_MAX_DOMAINS
-constexpr int kSpreadMaxGroups = 64;    // KSCHED_SPREAD_MAX_GROUPS
-constexpr int kSpreadMaxCells = 4096;   // KSCHED_SPREAD_MAX_CELLS: the LDS table of every workgroup, 16 KiB
-constexpr int kExtMax = 4;              // KSCHED_EXT_MAX: columns of the dynamic LDS table, kExtMax * 256 * 8 slots * 8 B = 64 KiB
 
 struct ScoreArgs {
     NodeRec *nodes;    // read; the rows of `patch` are written back by their chunk's wave
@@ -431,20 +385,9 @@ hipError_t explain_batch(const ExplainArgs &a, void **ws, size_t *ws_bytes, unsi
 hipError_t explain_pod_at(const ExplainArgs &a, int64_t pod, int64_t *state, uint8_t *reason,
                           unsigned long long *counts, hipStream_t s);
 
-// host-side launchers (ksched_kernels.hip).  fast53: every allocatable and request magnitude stays
-// below 2^52 for the whole call (host-checked), enabling (double)(a-r) == (double)a - (double)r.
+// host-side launchers (ksched_kernels.hip; exact mode's: ksched_exact.h).  fast53: every allocatable and request
+// magnitude stays below 2^52 for the whole call (host-checked), enabling (double)(a-r) == (double)a - (double)r.
 hipError_t launch_prep_nodes(NodeRec *nodes, int64_t n, hipStream_t s);
-hipError_t launch_exact(int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
-                        bool cooperative, hipStream_t s);
-// the same launch of k_exact<GANG>: a.gang_end set (a.gang_placed may be null)
-hipError_t launch_exact_gang(int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
-                             bool cooperative, hipStream_t s);
-// the same launch of k_exact<SPREAD>: a.sp_* set (never k_exact1: the one-workgroup kernel knows no spread table)
-hipError_t launch_exact_spread(int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
-                               bool cooperative, hipStream_t s);
-// the same launch of k_exact<EXT>: a.ext* set, dynamic LDS of a.n_ext * block * npt * 8 bytes (never k_exact1)
-hipError_t launch_exact_ext(int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
-                            bool cooperative, hipStream_t s);
 hipError_t launch_score_topk(int KC, int prio, int dom, bool lab, bool fast53, const ScoreArgs &a, int pod_groups,
                              hipStream_t s);
 // one workgroup per pod: the score kernel's workgroup lists -> the pod's K-entry Rec list (C_in <= 256)
@@ -697,12 +640,6 @@ hipError_t launch_apply_batch(const XBuf *x, NodeRec *nodes, int64_t node_lo, in
 // diagnostics: qdiv(a, b, recip(b)) against the native a / b, bit for bit
 hipError_t launch_selftest_div(int64_t n, const double *a, const double *b, double *native, double *fast,
                                hipStream_t s);
-
-constexpr int kExactBlock = 256;
-constexpr int kExact1Block = 1024;  // k_exact1: the whole node set in one workgroup
-// exact mode on one workgroup of bs threads, npt node slots each: bs 1024 with npt 1-4 (resource) or 1-6, 8, 12, 16
-// (best-price); best-price also (512, 10) and (256, 20)
-hipError_t launch_exact1(int npt, int bs, int prio, int dom, bool lab, bool f53, const ExactArgs &a, hipStream_t s);
 
 // score kernel geometry: 4 waves per workgroup, 2 workgroups per CU at the default grid
 constexpr int kScoreWaves = 8;

@@ -1,76 +1,14 @@
-// ksched_kernels.hip -- CDNA4 (gfx950) kernels of the scheduling core.  Compiled with
+// ksched_kernels.hip -- CDNA4 (gfx950) kernels of the scheduling core: the stream pipeline's kernels and the small
+// utility kernels (exact mode's are in ksched_exact.hip).  Compiled with
 // -ffp-contract=off: every double op rounds individually, exactly like the Go reference.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <type_traits>
 
 #include "ksched_kernels.h"
 #include "ksched_merge.h"
 
 namespace ksched {
-
-namespace {
-
-__device__ __forceinline__ uint64_t ld_granule(const uint64_t *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_granule(uint64_t *p, uint64_t v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void set_node(NodeRec *nd, int64_t a0, int64_t a1, int64_t a2) {
-    nd->a[0] = a0; nd->a[1] = a1; nd->a[2] = a2;
-    const double f0 = (double)a0, f1 = (double)a1, f2 = (double)a2;
-    nd->af[0] = f0; nd->af[1] = f1; nd->af[2] = f2;
-    nd->y[0] = recip_or_zero(a0, f0); nd->y[1] = recip_or_zero(a1, f1); nd->y[2] = recip_or_zero(a2, f2);
-}
-
-}  // namespace
-
-// k_exact<GANG>: what a workgroup keeps across the pods of the current gang, and its LDS log of their outcomes
-struct GangNone {};
-struct GangState {
-    int64_t gang = 0;             // the current gang,
-    int32_t gm = 0, placed = 0;   // ... the current member, the members placed so far
-};
-template <bool GANG>
-__device__ __forceinline__ int32_t *gang_log() {
-    if constexpr (GANG) {
-        __shared__ int32_t s_log[kGangMax];  // member by member: the node, or the member's failure code
-        return s_log;
-    } else {
-        return nullptr;
-    }
-}
-
-// k_exact<SPREAD>: a workgroup's copy of the spread table -- the S x D counts row-major, and per group the row's
-// minimum, the number of domains at it, and the maximum skew
-struct SpreadTable {
-    int32_t cnt[kSpreadMaxCells];
-    int32_t mn[kSpreadMaxGroups], nmin[kSpreadMaxGroups], skew[kSpreadMaxGroups];
-};
-template <bool SPREAD>
-__device__ __forceinline__ SpreadTable *spread_table() {
-    if constexpr (SPREAD) {
-        __shared__ SpreadTable s_spread;
-        return &s_spread;
-    } else {
-        return nullptr;
-    }
-}
-
-// k_exact<EXT>: a workgroup's slots of the extended-resource table, in dynamic LDS: column r of slot s at
-// [r * kExactBlock * NPT + s].  (Declared 16-byte aligned: the dynamic region follows the kernel's statics.)
-template <bool EXT>
-__device__ __forceinline__ int64_t *ext_table() {
-    if constexpr (EXT) {
-        extern __shared__ __attribute__((aligned(16))) int64_t s_ext[];
-        return s_ext;
-    } else {
-        return nullptr;
-    }
-}
 
 // (re)derive af / y of every node row from its int64 allocatable
 __global__ void k_prep_nodes(NodeRec *nodes, int64_t n) {
@@ -78,491 +16,6 @@ __global__ void k_prep_nodes(NodeRec *nodes, int64_t n) {
     if (i >= n) return;
     NodeRec *nd = nodes + i;
     set_node(nd, nd->a[0], nd->a[1], nd->a[2]);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Exact mode: one persistent launch schedules every pod in order.
-//   - workgroup g owns nodes [g*per_wg, (g+1)*per_wg); thread t holds nodes g*per_wg + t + k*256
-//     (k < NPT) in registers for the whole launch, with their (double) values and reciprocals;
-//   - per pod: each lane scores its nodes (predicate.go:127-150 + priorities.go:45-50), wave
-//     butterfly arg-best + count, 4-wave combine through LDS;
-//   - G > 1: wave 0 publishes the workgroup's (key, idx, count) as four tagged 8-byte granules
-//     (write-through sc1 stores, epoch = pod + 1) and sweeps all G records until every tag matches
-//     (MI355X_MICROARCH "handoff-1to1"/"allgather" R2 granules: no fences needed); every workgroup
-//     then folds the same G records into the same decision;
-//   - the owner lane of the winning node commits it in registers; nodes are written back at exit.
-// GANG (ksched_schedule_gangs): the pods come in groups that are bound all-or-nothing.
-//   Every member is evaluated and committed exactly as above -- never skipped, so the granule tag and the parity
-//   advance by one per pod -- and every workgroup logs the member's outcome in LDS (s_log, thread 0: the decision
-//   is the same in every thread of every workgroup).  At the gang's last member every workgroup compares the
-//   same count of placed members with the gang's minimum.  Rejected: one workgroup barrier (the log's last
-//   entry), then every thread walks the log and adds the members' requests back to the slots it owns (wrapping,
-//   the commit's inverse; f / y re-derived once per touched slot), and workgroup 0 rewrites the placed members'
-//   results.  Register-only and workgroup-local: no exchange, no wait.  The next gang's first log entry is
-//   written behind the next pod's barrier, after every thread has left the walk.
-// SPREAD (ksched_schedule_spread): one topology spread constraint per pod joins the
-//   predicate.  Every thread keeps its slots' domains in registers; every workgroup keeps the whole S x D count
-//   table in LDS (SpreadTable, loaded at entry, written back by workgroup 0 at exit) with each row's minimum and
-//   the number of domains at it.  An enforcing pod's slot is eligible when it fits and counts[s][dom] <= skew[s] +
-//   min[s] - 1: one LDS gather per slot and two broadcast reads per pod.  Every workgroup derives the same winner,
-//   reads its domain from the global array (a uniform load) and thread 0 applies the same increment to its own
-//   copy -- no exchange, no wait, the tag and parity sequence unchanged.  A row's minimum rises only when its last
-//   domain at the minimum is incremented; thread 0 then recounts the row (D reads, at most once per D placements
-//   of the group).  The increment is written after the pod's last barrier and the next pod's gathers come before
-//   its first, so a pod that moved the table ends with one more barrier; a pod that did not (no group, not placed,
-//   a node without the key) pays none.
-// EXT (ksched_schedule_ext): up to kExtMax further resource columns join the predicate.  The
-//   registers are full (section 4.7), so the columns of a workgroup's slots live in dynamic LDS, ext[r][slot] with
-//   slot = tid + k * kExactBlock: consecutive lanes read consecutive 8-byte words.  Loaded from the device table at
-//   entry (node ids below n only), written back by every workgroup for its own slots at exit.  The pod's requests
-//   come pod-major with a word of non-zero-column bits, all uniform loads: a column the pod does not ask for is a
-//   uniform skip, so a pod that asks for nothing reads no LDS.  The owner lane of the winning slot subtracts the
-//   non-zero requests from its own slot's words.  Only the owning thread ever reads or writes a slot's words: no
-//   new barrier, exchange or wait; the tag and parity sequence unchanged.
-// ------------------------------------------------------------------------------------------------
-template <int NPT, int PRIO, int DOM, bool LAB, bool F53, bool GANG = false, bool SPREAD = false, bool EXT = false>
-__global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
-    static_assert((int)GANG + (int)SPREAD + (int)EXT <= 1, "one extension per instantiation");
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int g = blockIdx.x;
-    const int64_t lo = (int64_t)g * A.per_wg;
-    const int64_t hi = (lo + A.per_wg < A.n) ? lo + A.per_wg : A.n;
-    const double y3 = recip(3.0);
-
-    int64_t a0[NPT], a1[NPT], a2[NPT];
-    double f0[NPT], f1[NPT], f2[NPT], y0[NPT], y1[NPT], y2[NPT];
-    uint64_t lab[NPT];
-    float pr[NPT];
-    int32_t id[NPT];
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        const int64_t j = lo + tid + (int64_t)k * kExactBlock;
-        if (j < hi) {
-            const NodeRec &nd = A.nodes[j];
-            a0[k] = nd.a[0]; a1[k] = nd.a[1]; a2[k] = nd.a[2];
-            f0[k] = nd.af[0]; f1[k] = nd.af[1]; f2[k] = nd.af[2];
-            y0[k] = nd.y[0]; y1[k] = nd.y[1]; y2[k] = nd.y[2];
-            lab[k] = nd.labels; pr[k] = nd.price; id[k] = (int32_t)j;
-        } else {
-            a0[k] = a1[k] = a2[k] = 0; f0[k] = f1[k] = f2[k] = 0.0; y0[k] = y1[k] = y2[k] = 0.0;
-            lab[k] = 0; pr[k] = 0.f; id[k] = kNoIdx;
-        }
-    }
-    [[maybe_unused]] int32_t dom[SPREAD ? NPT : 1];  // SPREAD: the slots' topology domains (-1: the node lacks the key)
-    [[maybe_unused]] SpreadTable *const sp = spread_table<SPREAD>();
-    if constexpr (SPREAD) {
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) dom[k] = id[k] != kNoIdx ? A.sp_dom[id[k]] : -1;
-        const int cells = A.sp_S * A.sp_D;
-        for (int c = tid; c < cells; c += kExactBlock) sp->cnt[c] = A.sp_counts[c];
-        __syncthreads();
-        if (tid < A.sp_S) {  // one thread per group: the row's minimum and how many domains hold it
-            const int32_t *row = sp->cnt + tid * A.sp_D;
-            int32_t m = row[0], nm = 1;
-            for (int d = 1; d < A.sp_D; ++d) {
-                const int32_t v = row[d];
-                nm = v < m ? 1 : nm + (v == m);
-                m = v < m ? v : m;
-            }
-            sp->mn[tid] = m; sp->nmin[tid] = nm; sp->skew[tid] = A.sp_skew[tid];
-        }
-        __syncthreads();
-    }
-    // EXT: this thread's words of column r, slot k at ext[r * kExtCol + k * kExactBlock] (no other thread touches them)
-    [[maybe_unused]] constexpr int kExtCol = kExactBlock * NPT;
-    [[maybe_unused]] int64_t *const ext = EXT ? ext_table<EXT>() + tid : nullptr;
-    if constexpr (EXT) {
-        for (int r = 0; r < A.n_ext; ++r) {
-#pragma unroll
-            for (int k = 0; k < NPT; ++k)
-                ext[r * kExtCol + k * kExactBlock] = id[k] != kNoIdx ? A.ext[(int64_t)r * A.n + id[k]] : 0;
-        }
-    }
-
-    __shared__ double s_key[2][kExactBlock / 64];
-    __shared__ int32_t s_idx[2][kExactBlock / 64];
-    __shared__ int64_t s_cnt[2][kExactBlock / 64];
-    __shared__ double s_rkey[2];
-    __shared__ int32_t s_ridx[2];
-    __shared__ int64_t s_rcnt[2];
-    __shared__ int32_t s_abort;
-    if (tid == 0) s_abort = 0;
-    [[maybe_unused]] std::conditional_t<GANG, GangState, GangNone> gs;  // (nothing in the plain kernels)
-    [[maybe_unused]] int32_t *const s_log = gang_log<GANG>();
-
-    for (int64_t i = 0; i < A.pods.p; ++i) {
-        const int par = (int)(i & 1);
-        const int64_t rc = A.pods.rc[i], rm = A.pods.rm[i], rp = A.pods.rp[i];
-        const uint64_t sel = LAB ? A.pods.sel[i] : 0;
-        // GANG: 0, or at a gang's last member its size | minimum << 16 -- loaded with the request, not after the pod
-        const int32_t gend = GANG ? A.gang_end[i] : 0;
-        // SPREAD: -1 (no group), or group << 1 | enforce -- loaded with the request too
-        [[maybe_unused]] const int32_t sword = SPREAD ? A.sp_word[i] : -1;
-        [[maybe_unused]] bool enf = false;   // the pod enforces its group's constraint:
-        [[maybe_unused]] int32_t srow = 0;   // ... the group's row of the table,
-        [[maybe_unused]] int64_t slim = 0;   // ... the largest count an eligible domain may hold
-        if constexpr (SPREAD) {
-            if (sword >= 0 && (sword & 1)) {
-                const int32_t s = sword >> 1;
-                enf = true;
-                srow = s * A.sp_D;
-                slim = (int64_t)sp->skew[s] + sp->mn[s] - 1;
-            }
-        }
-        // EXT: the non-zero-column bits -- loaded with the request too -- and, only where there are any, the requests
-        // (pod-major: one uniform load; loading them for every pod cost 4 % per pod on pods that ask for nothing)
-        [[maybe_unused]] const int32_t eword = EXT ? A.ext_word[i] : 0;
-        [[maybe_unused]] int64_t er[EXT ? kExtMax : 1];
-        if constexpr (EXT) {
-#pragma unroll
-            for (int r = 0; r < kExtMax; ++r) er[r] = 0;
-            if (eword != 0) {
-#pragma unroll
-                for (int r = 0; r < kExtMax; ++r) er[r] = A.ext_req[i * kExtMax + r];
-            }
-        }
-        const double rcf = (double)rc, rmf = (double)rm, rpf = (double)rp;
-        double bk = -__builtin_inf();
-        int32_t bi = kNoIdx;
-        int64_t cnt = 0;
-#pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            if (id[k] != kNoIdx) {
-                bool f = fits(rc, rm, rp, sel, a0[k], a1[k], a2[k], lab[k], LAB);
-                if constexpr (SPREAD) {
-                    if (enf) f = f && dom[k] >= 0 && (int64_t)sp->cnt[srow + (dom[k] < 0 ? 0 : dom[k])] <= slim;
-                }
-                if constexpr (EXT) {
-                    if (eword != 0) {  // (uniform: a pod that asks for no column reads no LDS)
-#pragma unroll
-                        for (int r = 0; r < kExtMax; ++r)
-                            if (eword >> r & 1) f = f && er[r] <= ext[r * kExtCol + k * kExactBlock];
-                    }
-                }
-                cnt += f;
-                double key;
-                if (pair_key_fast<PRIO, DOM, F53>(f, rc, rm, rp, rcf, rmf, rpf, a0[k], a1[k], a2[k], f0[k], f1[k],
-                                                  f2[k], y0[k], y1[k], y2[k], y3, pr[k], &key) &&
-                    better(key, id[k], bk, bi)) {
-                    bk = key;
-                    bi = id[k];
-                }
-            }
-        }
-        int32_t aux = 0;
-        wave_argbest(bk, bi, aux);
-        cnt = wave_sum_i64(cnt);
-        if (lane == 0) { s_key[par][wave] = bk; s_idx[par][wave] = bi; s_cnt[par][wave] = cnt; }
-        __syncthreads();
-        double gk = s_key[par][0];
-        int32_t gi = s_idx[par][0];
-        int64_t gc = s_cnt[par][0];
-#pragma unroll
-        for (int w = 1; w < kExactBlock / 64; ++w) {
-            gc += s_cnt[par][w];
-            if (better(s_key[par][w], s_idx[par][w], gk, gi)) { gk = s_key[par][w]; gi = s_idx[par][w]; }
-        }
-        if (A.G > 1) {
-            if (wave == 0) {
-                const uint64_t ep = (uint64_t)(uint32_t)(i + 1) << 32;
-                uint64_t *mine = A.slots + ((size_t)par * A.G + g) * 4;
-                const uint64_t kb = (uint64_t)__double_as_longlong(gk);
-                if (lane < 4) {
-                    const uint32_t v = lane == 0 ? (uint32_t)(kb >> 32)
-                                     : lane == 1 ? (uint32_t)kb
-                                     : lane == 2 ? (uint32_t)gi
-                                                 : (uint32_t)gc;
-                    st_granule(mine + lane, ep | v);
-                }
-                const int64_t t0 = wall_clock64();
-                double fk;
-                int32_t fi;
-                int64_t fc;
-                for (;;) {
-                    bool ok = true;
-                    fk = -__builtin_inf(); fi = kNoIdx; fc = 0;
-                    for (int g2 = lane; g2 < A.G; g2 += 64) {
-                        const uint64_t *sl = A.slots + ((size_t)par * A.G + g2) * 4;
-                        const uint64_t x0 = ld_granule(sl), x1 = ld_granule(sl + 1);
-                        const uint64_t x2 = ld_granule(sl + 2), x3 = ld_granule(sl + 3);
-                        ok &= ((x0 & 0xffffffff00000000ull) == ep) & ((x1 & 0xffffffff00000000ull) == ep) &
-                              ((x2 & 0xffffffff00000000ull) == ep) & ((x3 & 0xffffffff00000000ull) == ep);
-                        const double k2 = __longlong_as_double((long long)((x0 << 32) | (x1 & 0xffffffffull)));
-                        const int32_t i2 = (int32_t)(uint32_t)x2;
-                        fc += (int64_t)(uint32_t)x3;
-                        if (better(k2, i2, fk, fi)) { fk = k2; fi = i2; }
-                    }
-                    if (__all(ok)) break;
-                    if (wall_clock64() - t0 > A.timeout_ticks) {
-                        if (lane == 0) { atomicExch(A.err, kErrExactExchange); s_abort = 1; }
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                int32_t aux2 = 0;
-                wave_argbest(fk, fi, aux2);
-                fc = wave_sum_i64(fc);
-                if (lane == 0) { s_rkey[par] = fk; s_ridx[par] = fi; s_rcnt[par] = fc; }
-            }
-            __syncthreads();
-            if (s_abort) break;
-            gk = s_rkey[par]; gi = s_ridx[par]; gc = s_rcnt[par];
-        }
-        int32_t oidx;
-        double osc = 0.0;
-        if (gc == 0) {
-            oidx = -1;  // NO_FIT (anchor/schedule.go:74-76)
-        } else if (gi == kNoIdx) {
-            oidx = -2;  // NO_POSITIVE_SCORE (reference: nil node, anchor/priorities.go:55-62)
-        } else {
-            oidx = gi;
-            osc = PRIO == kPrioPrice ? 0.0 - gk : gk;
-#pragma unroll
-            for (int k = 0; k < NPT; ++k) {
-                if (id[k] == gi) {  // commit: used += request, ONE pod (anchor/predicate.go:99-102)
-                    a0[k] = wsub(a0[k], rc); a1[k] = wsub(a1[k], rm); a2[k] = wsub(a2[k], 1);
-                    f0[k] = (double)a0[k]; f1[k] = (double)a1[k]; f2[k] = (double)a2[k];
-                    y0[k] = recip_or_zero(a0[k], f0[k]); y1[k] = recip_or_zero(a1[k], f1[k]);
-                    y2[k] = recip_or_zero(a2[k], f2[k]);
-                    if constexpr (EXT) {
-                        if (eword != 0) {  // the owner lane: its own slot's words, the non-zero columns only
-#pragma unroll
-                            for (int r = 0; r < kExtMax; ++r)
-                                if (eword >> r & 1) {
-                                    int64_t *w = ext + r * kExtCol + k * kExactBlock;
-                                    *w = wsub(*w, er[r]);
-                                }
-                        }
-                    }
-                }
-            }
-        }
-        if (g == 0 && tid == 0) {
-            A.out.idx[i] = oidx;
-            A.out.score[i] = osc;
-            A.out.feas[i] = (int32_t)gc;
-        }
-        if constexpr (SPREAD) {
-            if (sword >= 0 && oidx >= 0) {  // (the same in every thread of every workgroup)
-                const int32_t wd = A.sp_dom[__builtin_amdgcn_readfirstlane(oidx)];
-                if (wd >= 0) {
-                    if (tid == 0) {
-                        const int32_t s = sword >> 1;
-                        int32_t *row = sp->cnt + s * A.sp_D;
-                        const int32_t old = row[wd];
-                        row[wd] = old + 1;
-                        if (old == sp->mn[s] && --sp->nmin[s] == 0) {
-                            // the row's last domain at the minimum: every domain now holds at least old + 1
-                            int32_t nm = 0;
-                            for (int d = 0; d < A.sp_D; ++d) nm += row[d] == old + 1;
-                            sp->mn[s] = old + 1; sp->nmin[s] = nm;
-                        }
-                    }
-                    __syncthreads();  // the next pod's gathers come before its first barrier
-                }
-            }
-        }
-        if constexpr (GANG) {
-            if (tid == 0) s_log[gs.gm] = oidx;
-            gs.placed += oidx >= 0;
-            ++gs.gm;
-            if (gend != 0) {  // the gang's last member: accept or roll back (the same answer in every workgroup)
-                const int32_t gsize = gend & 0xffff;
-                const bool reject = gs.placed < (gend >> 16);
-                if (reject && gs.placed > 0) {
-                    __syncthreads();  // the log's last entry
-                    const int64_t first = i + 1 - gsize;
-                    uint32_t dirty = 0;
-#pragma nounroll
-                    for (int32_t m = 0; m < gsize; ++m) {
-                        const int32_t li = s_log[m];
-                        if (li < 0) continue;  // a member that failed keeps its own code
-                        if (g == 0 && tid == 0) { A.out.idx[first + m] = kGangRejected; A.out.score[first + m] = 0.0; }
-                        const int64_t urc = A.pods.rc[first + m], urm = A.pods.rm[first + m];
-#pragma unroll
-                        for (int k = 0; k < NPT; ++k) {
-                            if (id[k] == li) {  // the commit's inverse: a wrapping add undoes the wrapping subtract
-                                a0[k] = wadd(a0[k], urc); a1[k] = wadd(a1[k], urm); a2[k] = wadd(a2[k], 1);
-                                dirty |= 1u << k;
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < NPT; ++k) {
-                        if (dirty >> k & 1) {
-                            f0[k] = (double)a0[k]; f1[k] = (double)a1[k]; f2[k] = (double)a2[k];
-                            y0[k] = recip_or_zero(a0[k], f0[k]); y1[k] = recip_or_zero(a1[k], f1[k]);
-                            y2[k] = recip_or_zero(a2[k], f2[k]);
-                        }
-                    }
-                }
-                if (g == 0 && tid == 0 && A.gang_placed) A.gang_placed[gs.gang] = reject ? 0 : gs.placed;
-                ++gs.gang; gs.gm = 0; gs.placed = 0;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NPT; ++k)
-        if (id[k] != kNoIdx) set_node(A.nodes + id[k], a0[k], a1[k], a2[k]);
-    if constexpr (EXT) {
-        for (int r = 0; r < A.n_ext; ++r) {
-#pragma unroll
-            for (int k = 0; k < NPT; ++k)
-                if (id[k] != kNoIdx) A.ext[(int64_t)r * A.n + id[k]] = ext[r * kExtCol + k * kExactBlock];
-        }
-    }
-    if constexpr (SPREAD) {
-        // (every pod that moved the table ended with a barrier: the copy is complete in every thread's view)
-        if (g == 0) {
-            const int cells = A.sp_S * A.sp_D;
-            for (int c = tid; c < cells; c += kExactBlock) A.sp_counts[c] = sp->cnt[c];
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Exact mode on ONE workgroup (kExact1Block threads; n <= kExact1Block * NPT): every node lives in a register
-// slot of this workgroup, so a pod is decided with one workgroup barrier and no cross-workgroup exchange (k_exact
-// with G > 1 pays a round of tagged granules through L2 per pod, ~2.7 us on c2).  Thread t holds slots
-// s = t + k * kExact1Block.
-//   best-price: slot s is the node of rank s in (price asc, node index asc) -- the order of the reference's
-//     argmax over -price with the lowest index on ties (README.md:37-64; price_key) -- so a pod's node is the
-//     FIRST feasible slot: per wave one ballot per k (its lowest set bit), the minimum over the waves; the feasible
-//     count is the sum of the ballots' popcounts.  No key is compared at all.
-//   resource: slot s is node s; per pod every lane keys its slots, wave arg-best, the waves' bests through LDS.
-// Restated by the same oracle as k_exact (oracle/cpu_ref.c or_schedule); results bit-identical.
-// ------------------------------------------------------------------------------------------------
-template <int NPT, int BS, int PRIO, int DOM, bool LAB, bool F53>
-__global__ __launch_bounds__(BS) void k_exact1(ExactArgs A) {
-    constexpr int kExact1Block = BS;
-    constexpr int W = kExact1Block / 64;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const double y3 = recip(3.0);
-    constexpr bool kRes = PRIO != kPrioPrice;
-    int64_t a0[NPT], a1[NPT], a2[NPT];
-    double f0[kRes ? NPT : 1], f1[kRes ? NPT : 1], f2[kRes ? NPT : 1];
-    double yy0[kRes ? NPT : 1], yy1[kRes ? NPT : 1], yy2[kRes ? NPT : 1];
-    uint64_t lab[NPT];
-    float pr[NPT];
-    int32_t id[NPT];
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        const int64_t sl = tid + (int64_t)k * kExact1Block;
-        id[k] = kNoIdx;
-        a0[k] = a1[k] = a2[k] = 0; lab[k] = 0; pr[k] = 0.f;
-        if constexpr (kRes) { f0[k] = f1[k] = f2[k] = 0.0; yy0[k] = yy1[k] = yy2[k] = 0.0; }
-        if (sl < A.n) {
-            const int32_t j = A.perm ? A.perm[sl] : (int32_t)sl;
-            const NodeRec &nd = A.nodes[j];
-            a0[k] = nd.a[0]; a1[k] = nd.a[1]; a2[k] = nd.a[2];
-            lab[k] = nd.labels; pr[k] = nd.price; id[k] = j;
-            if constexpr (kRes) {
-                f0[k] = nd.af[0]; f1[k] = nd.af[1]; f2[k] = nd.af[2];
-                yy0[k] = nd.y[0]; yy1[k] = nd.y[1]; yy2[k] = nd.y[2];
-            }
-        }
-    }
-    __shared__ int32_t s_cnt[2][W];
-    __shared__ int32_t s_slot[2][W];  // best-price: the wave's first feasible slot (INT32_MAX: none)
-    __shared__ double s_key[2][W];    // resource: the wave's best (key, node)
-    __shared__ int32_t s_idx[2][W];
-    // the next pod's request is loaded one pod ahead: its latency hides behind the current pod
-    int64_t nrc = 0, nrm = 0, nrp = 0;
-    uint64_t nsel = 0;
-    if (A.pods.p > 0) { nrc = A.pods.rc[0]; nrm = A.pods.rm[0]; nrp = A.pods.rp[0]; nsel = LAB ? A.pods.sel[0] : 0; }
-    for (int64_t i = 0; i < A.pods.p; ++i) {
-        const int par = (int)(i & 1);
-        const int64_t rc = nrc, rm = nrm, rp = nrp;
-        const uint64_t sel = nsel;
-        if (i + 1 < A.pods.p) {
-            nrc = A.pods.rc[i + 1]; nrm = A.pods.rm[i + 1]; nrp = A.pods.rp[i + 1];
-            nsel = LAB ? A.pods.sel[i + 1] : 0;
-        }
-        int32_t cnt = 0;
-        int32_t oidx = -1;
-        double osc = 0.0;
-        if constexpr (!kRes) {
-            int32_t first = 0x7fffffff;
-#pragma unroll
-            for (int k = 0; k < NPT; ++k) {
-                const bool f = id[k] != kNoIdx && fits(rc, rm, rp, sel, a0[k], a1[k], a2[k], lab[k], LAB);
-                const uint64_t m = __ballot(f);
-                cnt += __popcll(m);
-                if (first == 0x7fffffff && m) first = k * kExact1Block + wave * 64 + (int)__builtin_ctzll(m);
-            }
-            if (lane == 0) { s_slot[par][wave] = first; s_cnt[par][wave] = cnt; }
-            __syncthreads();
-            int32_t gs = s_slot[par][0], gc = s_cnt[par][0];
-#pragma unroll
-            for (int w = 1; w < W; ++w) { gs = s_slot[par][w] < gs ? s_slot[par][w] : gs; gc += s_cnt[par][w]; }
-            // the first feasible slot's owner commits it and writes the pod's results; no feasible node: thread 0
-            if (gc == 0) {
-                if (tid == 0) { A.out.idx[i] = -1; A.out.score[i] = 0.0; A.out.feas[i] = 0; }  // NO_FIT
-            } else if ((gs & (kExact1Block - 1)) == tid) {
-#pragma unroll
-                for (int k = 0; k < NPT; ++k) {
-                    if (gs == k * kExact1Block + tid) {  // commit: used += request, ONE pod (anchor/predicate.go:99-102)
-                        A.out.idx[i] = id[k];
-                        A.out.score[i] = 0.0 - price_key(pr[k]);
-                        A.out.feas[i] = gc;
-                        a0[k] = wsub(a0[k], rc); a1[k] = wsub(a1[k], rm); a2[k] = wsub(a2[k], 1);
-                    }
-                }
-            }
-            (void)oidx; (void)osc;
-        } else {
-            const double rcf = (double)rc, rmf = (double)rm, rpf = (double)rp;
-            double bk = -__builtin_inf();
-            int32_t bi = kNoIdx;
-#pragma unroll
-            for (int k = 0; k < NPT; ++k) {
-                if (id[k] != kNoIdx) {
-                    const bool f = fits(rc, rm, rp, sel, a0[k], a1[k], a2[k], lab[k], LAB);
-                    cnt += f;
-                    double key;
-                    if (pair_key_fast<PRIO, DOM, F53>(f, rc, rm, rp, rcf, rmf, rpf, a0[k], a1[k], a2[k], f0[k], f1[k],
-                                                      f2[k], yy0[k], yy1[k], yy2[k], y3, pr[k], &key) &&
-                        better(key, id[k], bk, bi)) {
-                        bk = key;
-                        bi = id[k];
-                    }
-                }
-            }
-            int32_t aux = 0;
-            wave_argbest(bk, bi, aux);
-            cnt = (int32_t)wave_sum_i64(cnt);
-            if (lane == 0) { s_key[par][wave] = bk; s_idx[par][wave] = bi; s_cnt[par][wave] = cnt; }
-            __syncthreads();
-            double gk = s_key[par][0];
-            int32_t gi = s_idx[par][0], gc = s_cnt[par][0];
-#pragma unroll
-            for (int w = 1; w < W; ++w) {
-                gc += s_cnt[par][w];
-                if (better(s_key[par][w], s_idx[par][w], gk, gi)) { gk = s_key[par][w]; gi = s_idx[par][w]; }
-            }
-            oidx = gc == 0 ? -1 : (gi == kNoIdx ? -2 : gi);  // NO_FIT / NO_POSITIVE_SCORE (anchor/schedule.go:74-76)
-            osc = oidx >= 0 ? gk : 0.0;
-            if (oidx >= 0) {
-#pragma unroll
-                for (int k = 0; k < NPT; ++k) {
-                    if (id[k] == gi) {
-                        a0[k] = wsub(a0[k], rc); a1[k] = wsub(a1[k], rm); a2[k] = wsub(a2[k], 1);
-                        f0[k] = (double)a0[k]; f1[k] = (double)a1[k]; f2[k] = (double)a2[k];
-                        yy0[k] = recip_or_zero(a0[k], f0[k]); yy1[k] = recip_or_zero(a1[k], f1[k]);
-                        yy2[k] = recip_or_zero(a2[k], f2[k]);
-                    }
-                }
-            }
-            if (tid == 0) { A.out.idx[i] = oidx; A.out.score[i] = osc; A.out.feas[i] = gc; }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NPT; ++k)
-        if (id[k] != kNoIdx) set_node(A.nodes + id[k], a0[k], a1[k], a2[k]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1253,67 +706,6 @@ __global__ void k_selftest_div(int64_t n, const double *a, const double *b, doub
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-template <int NPT, int PRIO, int DOM, bool LAB, bool F53, bool GANG, bool SPREAD = false, bool EXT = false>
-hipError_t exact_one(const ExactArgs &a, int block, bool coop, hipStream_t s) {
-    auto fn = k_exact<NPT, PRIO, DOM, LAB, F53, GANG, SPREAD, EXT>;
-    // EXT: the workgroup's slots of every column (ext_table), at most kExtMax * 256 * 8 * 8 B = 64 KiB
-    const size_t lds = EXT ? (size_t)a.n_ext * kExactBlock * NPT * sizeof(int64_t) : 0;
-    if (EXT && block != kExactBlock) return hipErrorInvalidValue;
-    if (coop && a.G > 1) {
-        ExactArgs copy = a;
-        void *args[] = {&copy};
-        return hipLaunchCooperativeKernel((const void *)fn, dim3(a.G), dim3(block), args, lds, s);
-    }
-    hipLaunchKernelGGL(fn, dim3(a.G), dim3(block), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int PRIO, int DOM, bool LAB, bool F53, bool GANG, bool SPREAD = false, bool EXT = false>
-hipError_t exact_npt(int npt, const ExactArgs &a, int block, bool coop, hipStream_t s) {
-    switch (npt) {
-        case 1: return exact_one<1, PRIO, DOM, LAB, F53, GANG, SPREAD, EXT>(a, block, coop, s);
-        case 2: return exact_one<2, PRIO, DOM, LAB, F53, GANG, SPREAD, EXT>(a, block, coop, s);
-        case 4: return exact_one<4, PRIO, DOM, LAB, F53, GANG, SPREAD, EXT>(a, block, coop, s);
-        case 8: return exact_one<8, PRIO, DOM, LAB, F53, GANG, SPREAD, EXT>(a, block, coop, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <int NPT, int BS, int PRIO, int DOM, bool LAB, bool F53>
-hipError_t exact1_one(const ExactArgs &a, hipStream_t s) {
-    hipLaunchKernelGGL((k_exact1<NPT, BS, PRIO, DOM, LAB, F53>), dim3(1), dim3(BS), 0, s, a);
-    return hipGetLastError();
-}
-// (npt, block): resource slots <= 4 per thread of 1024 (registers); best-price more
-template <int PRIO, int DOM, bool LAB, bool F53>
-hipError_t exact1_npt(int npt, int bs, const ExactArgs &a, hipStream_t s) {
-    if (bs == 1024) {
-        switch (npt) {
-            case 1: return exact1_one<1, 1024, PRIO, DOM, LAB, F53>(a, s);
-            case 2: return exact1_one<2, 1024, PRIO, DOM, LAB, F53>(a, s);
-            case 3: return exact1_one<3, 1024, PRIO, DOM, LAB, F53>(a, s);
-            case 4: return exact1_one<4, 1024, PRIO, DOM, LAB, F53>(a, s);
-            default: break;
-        }
-        if constexpr (PRIO == kPrioPrice) {
-            switch (npt) {
-                case 5: return exact1_one<5, 1024, PRIO, DOM, LAB, F53>(a, s);
-                case 6: return exact1_one<6, 1024, PRIO, DOM, LAB, F53>(a, s);
-                case 8: return exact1_one<8, 1024, PRIO, DOM, LAB, F53>(a, s);
-                case 12: return exact1_one<12, 1024, PRIO, DOM, LAB, F53>(a, s);
-                case 16: return exact1_one<16, 1024, PRIO, DOM, LAB, F53>(a, s);
-                default: return hipErrorInvalidValue;
-            }
-        }
-        return hipErrorInvalidValue;
-    }
-    if constexpr (PRIO == kPrioPrice) {
-        if (bs == 512 && npt == 10) return exact1_one<10, 512, PRIO, DOM, LAB, F53>(a, s);
-        if (bs == 256 && npt == 20) return exact1_one<20, 256, PRIO, DOM, LAB, F53>(a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
 template <int KC, int PRIO, int DOM, bool LAB, bool F53>
 hipError_t score_one(const ScoreArgs &a, int pod_groups, hipStream_t s) {
     const size_t lds = score_lds_bytes(KC);
@@ -1427,35 +819,6 @@ hipError_t launch_prep_nodes(NodeRec *nodes, int64_t n, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_prep_nodes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nodes, n);
     return hipGetLastError();
-}
-
-hipError_t launch_exact(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
-                        hipStream_t s) {
-    KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, false>(npt, a, block, coop, s)));
-}
-
-hipError_t launch_exact_gang(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
-                             hipStream_t s) {
-    if (!a.gang_end) return hipErrorInvalidValue;
-    KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, true>(npt, a, block, coop, s)));
-}
-
-hipError_t launch_exact_spread(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
-                               hipStream_t s) {
-    if (!a.sp_dom || !a.sp_counts || !a.sp_skew || !a.sp_word || a.sp_D < 1 || a.sp_S < 1 ||
-        (int64_t)a.sp_D * a.sp_S > kSpreadMaxCells || a.sp_S > kSpreadMaxGroups)
-        return hipErrorInvalidValue;
-    KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, false, true>(npt, a, block, coop, s)));
-}
-
-hipError_t launch_exact_ext(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
-                            hipStream_t s) {
-    if (!a.ext || !a.ext_req || !a.ext_word || a.n_ext < 1 || a.n_ext > kExtMax) return hipErrorInvalidValue;
-    KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, false, false, true>(npt, a, block, coop, s)));
-}
-
-hipError_t launch_exact1(int npt, int bs, int prio, int dom, bool lab, bool f53, const ExactArgs &a, hipStream_t s) {
-    KSCHED_DISPATCH(prio, dom, lab, f53, (exact1_npt<P_, D_, L_, F_>(npt, bs, a, s)));
 }
 
 hipError_t launch_score_topk(int KC, int prio, int dom, bool lab, bool f53, const ScoreArgs &a, int pod_groups,

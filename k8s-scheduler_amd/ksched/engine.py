@@ -297,28 +297,38 @@ class Engine:
         self.sync()
         return self.results()
 
+    def _schedule_with(self, name, req_cpu, req_mem, req_pods, selector, extra, tail=()):
+        """What schedule_gangs / schedule_spread / schedule_ext share: the contiguous request arrays and their length
+        check, the three outputs, the call of ksched_<name> -- extra(p), the extension's arguments (checked against
+        the pod count), go between the selectors and the outputs, tail after them -- and self.p.  Returns (idx,
+        score, feasible)."""
+        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
+        p = rc.shape[0]
+        assert rm.shape[0] == p and rp.shape[0] == p
+        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
+        ext_args = extra(p)
+        oi = np.empty(p, np.int32); os_ = np.empty(p, np.float64); of = np.empty(p, np.int32)
+        self._chk(getattr(L.lib(), "ksched_" + name)(self._ctx, p, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64),
+                                                     L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64), *ext_args,
+                                                     L.ptr(oi, C.c_int32), L.ptr(os_, C.c_double), L.ptr(of, C.c_int32),
+                                                     *tail), name)
+        self.p = p
+        return oi, os_, of
+
     def schedule_gangs(self, req_cpu, req_mem, req_pods, selector, gang_off, gang_min=None):
         """The pending pods in all-or-nothing groups (ksched_schedule_gangs): gang g is pods [gang_off[g],
         gang_off[g + 1]) and is bound only if at least gang_min[g] of its members (None: all) find a node; a
         rejected gang's commits are undone before the next gang is evaluated.  One launch of the exact kernel,
         whatever the engine's mode.  Returns (idx, score, feasible, gang_placed): idx is GANG_REJECTED for a member
         that found a node in a rejected gang; gang_placed[g] = members bound (0 for a rejected gang)."""
-        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
-        p = rc.shape[0]
-        assert rm.shape[0] == p and rp.shape[0] == p
-        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
         off = _i64(gang_off)
         ng = off.shape[0] - 1
         gmin = None if gang_min is None else np.ascontiguousarray(gang_min, dtype=np.int32)
         assert ng >= 0 and (gmin is None or gmin.shape[0] == ng)
-        oi = np.empty(p, np.int32); os_ = np.empty(p, np.float64); of = np.empty(p, np.int32)
         gp = np.empty(ng, np.int32)
-        self._chk(L.lib().ksched_schedule_gangs(self._ctx, p, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64),
-                                                L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64), ng, L.ptr(off, C.c_int64),
-                                                L.ptr(gmin, C.c_int32), L.ptr(oi, C.c_int32), L.ptr(os_, C.c_double),
-                                                L.ptr(of, C.c_int32), L.ptr(gp, C.c_int32)), "schedule_gangs")
-        self.p = p
-        return oi, os_, of, gp
+        return self._schedule_with("schedule_gangs", req_cpu, req_mem, req_pods, selector,
+                                   lambda p: (ng, L.ptr(off, C.c_int64), L.ptr(gmin, C.c_int32)),
+                                   (L.ptr(gp, C.c_int32),)) + (gp,)
 
     def load_spread(self, node_domain, max_skew, counts=None, n_domains=None):
         """The spread table of schedule_spread() (ksched_load_spread): node j lies in topology domain node_domain[j]
@@ -353,20 +363,13 @@ class Engine:
         group[i] of the load_spread() table (-1: none) and, where enforce[i] (None: every pod), may only land in a
         domain whose count stays within the group's max_skew of the emptiest domain; every placed pod of a group is
         counted.  One launch of the exact kernel, whatever the engine's mode.  Returns (idx, score, feasible)."""
-        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
-        p = rc.shape[0]
-        assert rm.shape[0] == p and rp.shape[0] == p
-        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
         gr = np.ascontiguousarray(group, dtype=np.int32)
         en = None if enforce is None else np.ascontiguousarray(np.asarray(enforce) != 0, dtype=np.uint8)
-        assert gr.shape[0] == p and (en is None or en.shape[0] == p)
-        oi = np.empty(p, np.int32); os_ = np.empty(p, np.float64); of = np.empty(p, np.int32)
-        self._chk(L.lib().ksched_schedule_spread(self._ctx, p, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64),
-                                                 L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64), L.ptr(gr, C.c_int32),
-                                                 L.ptr(en, C.c_uint8), L.ptr(oi, C.c_int32), L.ptr(os_, C.c_double),
-                                                 L.ptr(of, C.c_int32)), "schedule_spread")
-        self.p = p
-        return oi, os_, of
+
+        def extra(p):
+            assert gr.shape[0] == p and (en is None or en.shape[0] == p)
+            return L.ptr(gr, C.c_int32), L.ptr(en, C.c_uint8)
+        return self._schedule_with("schedule_spread", req_cpu, req_mem, req_pods, selector, extra)
 
     def load_ext(self, node_ext):
         """The extended-resource table of schedule_ext() (ksched_load_ext): node_ext[r, j], int64 [R, n] with R in
@@ -390,19 +393,12 @@ class Engine:
         int64 [R, p] (None: zeros), is pod i's request for resource r; a zero request is not checked, any other must
         not exceed the node's column, and the placed pod's requests are subtracted from its node's columns.  One
         launch of the exact kernel, whatever the engine's mode.  Returns (idx, score, feasible)."""
-        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
-        p = rc.shape[0]
-        assert rm.shape[0] == p and rp.shape[0] == p
-        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
         re_ = None if req_ext is None else np.ascontiguousarray(req_ext, dtype=np.int64)
-        assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], p))
-        oi = np.empty(p, np.int32); os_ = np.empty(p, np.float64); of = np.empty(p, np.int32)
-        self._chk(L.lib().ksched_schedule_ext(self._ctx, p, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64),
-                                              L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64), L.ptr(re_, C.c_int64),
-                                              L.ptr(oi, C.c_int32), L.ptr(os_, C.c_double), L.ptr(of, C.c_int32)),
-                  "schedule_ext")
-        self.p = p
-        return oi, os_, of
+
+        def extra(p):
+            assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], p))
+            return (L.ptr(re_, C.c_int64),)
+        return self._schedule_with("schedule_ext", req_cpu, req_mem, req_pods, selector, extra)
 
 
 def engine_for(cl, mode: Optional[int] = None, **kw) -> Engine:

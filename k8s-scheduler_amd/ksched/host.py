@@ -501,22 +501,14 @@ class FakeCluster:
         pod.node_name = node.name
         self.events.append(dict(reason="Scheduled", message=f"Successfully assigned {pod.name} to {node.name}"))
 
-    def schedule_pods(self, pending: Optional[List[Pod]] = None, selectors=None):
-        """schedulePods (anchor/schedule.go:185-197): one engine call resolves every pending pod in order;
-        binds follow in the same order.  Returns a list of (pod, node | Exception).  By default the
-        pending set is getUnscheduledPods' (unbound pods annotated for this scheduler,
-        anchor/schedule.go:175-177); pass `pending` to schedule any other list (the watch path)."""
-        pending = self.unscheduled_pods() if pending is None else pending
-        rc, rm, rp = pack_pods(pending)
-        if selectors is None and self.use_labels:
-            selectors = [self.selector_of(p) for p in pending]
-        sel = None if not self.use_labels else np.asarray(selectors, dtype=np.uint64)
-        idx, score, feas = self.engine.schedule(rc, rm, rp, sel)
-        why = self._explain_failures(idx) if self.explain_failures else {}
+    def _resolve(self, pods, idx, why=None):
+        """One engine call's per-pod results as the (pod, node | Exception) list, in order: NO_FIT posts a
+        FailedScheduling event (with the per-node lines of why[k], where the call has them for pod k) and gives a
+        FitError, NO_POSITIVE_SCORE a NilNodeError, any other index binds the pod to that node."""
         out = []
-        for k, (pod, i) in enumerate(zip(pending, idx)):
+        for k, (pod, i) in enumerate(zip(pods, idx)):
             if i == L.NO_FIT:
-                msg = (self.failed_scheduling_message(pod, why[k]) if k in why
+                msg = (self.failed_scheduling_message(pod, why[k]) if why and k in why
                        else f"pod ({pod.name}) failed to fit in any node")
                 self.events.append(dict(reason="FailedScheduling", message=msg, type="Warning",
                                         involved=pod.name))
@@ -528,6 +520,19 @@ class FakeCluster:
                 self.bind(pod, node)
                 out.append((pod, node))
         return out
+
+    def schedule_pods(self, pending: Optional[List[Pod]] = None, selectors=None):
+        """schedulePods (anchor/schedule.go:185-197): one engine call resolves every pending pod in order;
+        binds follow in the same order.  Returns a list of (pod, node | Exception).  By default the
+        pending set is getUnscheduledPods' (unbound pods annotated for this scheduler,
+        anchor/schedule.go:175-177); pass `pending` to schedule any other list (the watch path)."""
+        pending = self.unscheduled_pods() if pending is None else pending
+        rc, rm, rp = pack_pods(pending)
+        if selectors is None and self.use_labels:
+            selectors = [self.selector_of(p) for p in pending]
+        sel = None if not self.use_labels else np.asarray(selectors, dtype=np.uint64)
+        idx, score, feas = self.engine.schedule(rc, rm, rp, sel)
+        return self._resolve(pending, idx, self._explain_failures(idx) if self.explain_failures else {})
 
     def schedule_gangs(self, pending: Optional[List[Pod]] = None):
         """schedule_pods with pod groups (group_gangs; ksched_schedule_gangs): one engine call resolves every gang
@@ -553,19 +558,11 @@ class FakeCluster:
                            f"{int(gmin[g])} needed")
                     self.events.append(dict(reason="FailedScheduling", message=msg, type="Warning", involved=pod.name))
                     out.append((pod, GangRejected(msg)))
-                elif i == L.NO_FIT:
-                    self.events.append(dict(reason="FailedScheduling", message=f"pod ({pod.name}) failed to fit in any node",
-                                            type="Warning", involved=pod.name))
-                    out.append((pod, FitError(f"Unable to schedule pod ({pod.name}) failed to fit in any node")))
-                elif i == L.NO_POSITIVE_SCORE:
-                    if rejected:
-                        self.events.append(dict(reason="FailedScheduling", type="Warning", involved=pod.name,
-                                                message=f"pod ({pod.name}) found no node with a positive score"))
-                    out.append((pod, NilNodeError(pod.name)))
-                else:
-                    node = self.nodes[int(i)]
-                    self.bind(pod, node)
-                    out.append((pod, node))
+                    continue
+                if i == L.NO_POSITIVE_SCORE and rejected:
+                    self.events.append(dict(reason="FailedScheduling", type="Warning", involved=pod.name,
+                                            message=f"pod ({pod.name}) found no node with a positive score"))
+                out += self._resolve([pod], [i])
         return out
 
     def schedule_spread(self, pending: Optional[List[Pod]] = None):
@@ -581,19 +578,7 @@ class FakeCluster:
         rc, rm, rp = pack_pods(pending)
         sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
         idx, _, _ = self.engine.schedule_spread(rc, rm, rp, sel, group, enforce)
-        out = []
-        for pod, i in zip(pending, idx):
-            if i == L.NO_FIT:
-                self.events.append(dict(reason="FailedScheduling", message=f"pod ({pod.name}) failed to fit in any node",
-                                        type="Warning", involved=pod.name))
-                out.append((pod, FitError(f"Unable to schedule pod ({pod.name}) failed to fit in any node")))
-            elif i == L.NO_POSITIVE_SCORE:
-                out.append((pod, NilNodeError(pod.name)))
-            else:
-                node = self.nodes[int(i)]
-                self.bind(pod, node)
-                out.append((pod, node))
-        return out
+        return self._resolve(pending, idx)
 
     def schedule_ext(self, pending: Optional[List[Pod]] = None):
         """schedule_pods with the pending pods' extended resources (ext_tables; ksched_schedule_ext) in the fit
@@ -606,19 +591,7 @@ class FakeCluster:
         rc, rm, rp = pack_pods(pending)
         sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
         idx, _, _ = self.engine.schedule_ext(rc, rm, rp, sel, req_ext)
-        out = []
-        for pod, i in zip(pending, idx):
-            if i == L.NO_FIT:
-                self.events.append(dict(reason="FailedScheduling", message=f"pod ({pod.name}) failed to fit in any node",
-                                        type="Warning", involved=pod.name))
-                out.append((pod, FitError(f"Unable to schedule pod ({pod.name}) failed to fit in any node")))
-            elif i == L.NO_POSITIVE_SCORE:
-                out.append((pod, NilNodeError(pod.name)))
-            else:
-                node = self.nodes[int(i)]
-                self.bind(pod, node)
-                out.append((pod, node))
-        return out
+        return self._resolve(pending, idx)
 
     def schedule_pod(self, pod: Pod, selector: Optional[int] = None):
         """schedulePod (anchor/schedule.go:68-89) for a single pod."""
