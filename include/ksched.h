@@ -432,8 +432,8 @@ int ksched_schedule_spread(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, c
  * KSCHED_E_INVALID (nothing changed; a table loaded earlier survives): n_ext outside [1, KSCHED_EXT_MAX], a null
  * node_ext, a negative request, p outside [0, 2^30), opts.nranks > 1.
  *
- * Out of scope: extended columns in rank, preempt, explain, gangs and spread; the batched pipeline and multi-rank;
- * the one-workgroup exact kernel (an ext run always takes the multi-slot one); an apply_delta for the table; init
+ * Out of scope: extended columns in rank, preempt and explain (with gangs and spread: ksched_schedule_constrained
+ * below); the batched pipeline and multi-rank; the one-workgroup exact kernel (an ext run always takes the multi-slot one); an apply_delta for the table; init
  * containers and pod overhead; quantity suffixes (amounts are whole numbers, pre-scaled by the caller); scoring on
  * extended resources.
  *
@@ -449,6 +449,67 @@ int ksched_schedule_ext(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, cons
                         const int64_t *req_pods, const uint64_t *selector,
                         const int64_t *req_ext /* n_ext * p, req_ext[r * p + i]; NULL = all zero */,
                         int32_t *out_idx, double *out_score, int32_t *out_feasible);
+
+/* ---- gangs, spread and extended resources together (added within ABI 6: probe with dlsym(lib, "ksched_schedule_constrained"); the version number did not move) ----
+ * The three calls above in ONE launch of the exact kernel whatever opts.mode says (stats.pipeline == KSCHED_PIPE_EXACT,
+ * stats.pair_evals == p * n): a distributed training job is a gang of pods that each ask for amd.com/gpu and spread over
+ * zones, and a rejected gang must also give back the GPUs it took and the spread counts it raised -- which three calls
+ * one after another cannot do.  The arguments are flat (no struct of pointers: the cgo rule at the top of this file).
+ *
+ * Each constraint is on or off for the whole call:
+ *   gang_off      NULL: n_gangs must be 0, every pod is a gang of one, gang_min and out_gang_placed are ignored.
+ *                 Given: ksched_schedule_gangs' rules for n_gangs, gang_off and gang_min, unchanged.
+ *   spread_group  NULL: no pod is in a spread group; no spread table is needed, a loaded one is neither read nor moved.
+ *                 Given: a table from ksched_load_spread must be loaded (KSCHED_E_STATE otherwise);
+ *                 ksched_schedule_spread's rules for spread_group and spread_enforce.
+ *   req_ext       NULL: no pod asks for an extended resource; no table is needed, a loaded one is neither read nor moved.
+ *                 Given: a table from ksched_load_ext must be loaded (KSCHED_E_STATE otherwise); ksched_schedule_ext's
+ *                 rules.
+ *
+ * Per pod i, in order:
+ *   eligible(i, j) = fits(i, j) && spread_ok(i, j) && ext_ok(i, j)
+ * fits is the scheduler's predicate, with the label check under opts.use_labels; spread_ok is ksched_schedule_spread's
+ * clause (true for a pod that does not enforce); ext_ok is ksched_schedule_ext's (true for a pod that asks for nothing).
+ * Everything else is ksched_schedule in exact mode with eligible in the place of fits, exactly as those calls word it:
+ * out_feasible counts eligible nodes, zero eligible nodes is KSCHED_NO_FIT, the key and the tie-break are unchanged, and
+ * under KSCHED_DOMAIN_ALL an ineligible node can still win the argmax.
+ *
+ * A pod placed on w commits alloc[w] -= (req_cpu, req_mem, 1); ext[r][w] -= req_ext[r][i], wrapping; and, where its
+ * group s >= 0 and node_domain[w] >= 0, counts[s][node_domain[w]] += 1.  Within a gang these commits are tentative, and
+ * later members of the same gang see all three.  At the end of gang g, placed >= gang_min[g] decides as in
+ * ksched_schedule_gangs:
+ *   accepted: all three kinds of commit stand.
+ *   rejected: all three are undone -- the node rows, every ext column and every spread count (with each row's minimum)
+ *     are bit-identical to their values before the gang's first member.  Out codes and out_gang_placed are
+ *     ksched_schedule_gangs': KSCHED_GANG_REJECTED with score 0 for members that had found a node, the member's own code
+ *     for those that had not; out_feasible is what each member saw at its turn.
+ *
+ * State: the spread counts and the ext table carry over from call to call, as with the single calls;
+ * ksched_read_spread / ksched_read_ext return them.  Afterwards ksched_explain_batch / ksched_explain_pod return
+ * KSCHED_E_STATE.
+ *
+ * KSCHED_E_INVALID (nothing changed; loaded tables survive): every invalid case of the three calls, gang_off == NULL
+ * with n_gangs != 0, p outside [0, 2^30), opts.nranks > 1.
+ *
+ * Equivalences: with all three off the call is ksched_schedule in exact mode; with exactly one on it is that
+ * constraint's own call, output for output and state for state.
+ *
+ * Worked example (best-price, feasible domain, ample cpu and memory): nodes n0 (zone A, price 0.1, gpu 2), n1 (A, 0.2,
+ * gpu 1), n2 (B, 0.5, gpu 1); one spread group with max_skew 1 and counts 0; the gangs {p0, p1, p2}, {p3, p4}, {p5},
+ * every member required; p0-p4 are in the group and enforce, p5 is in no group; the gpu requests are 1, 1, 1, 0, 2, 1.
+ * p0: all three nodes are eligible, the cheapest is n0 (A 1, B 0; gpu 1, 1, 1).  p1: zone A would make the skew 2, only
+ * n2 (A 1, B 1; gpu 1, 1, 0).  p2: both zones are allowed and gpu >= 1 leaves n0 and n1: n0 (A 2, B 1; gpu 0, 1, 0); gang
+ * 0 is accepted with 3 placed.  p3 asks for no gpu, so no column is checked; only zone B is allowed: n2, tentatively A 2,
+ * B 2 -- the row's minimum rises to 2.  p4 asks for gpu 2 and no node has it: KSCHED_NO_FIT.  Gang 1 is rejected: p3
+ * becomes KSCHED_GANG_REJECTED, the counts go back to A 2, B 1 (the minimum falls back to 1) and n2's row is restored.
+ * p5: n1 is the only node with a gpu.  out_idx = {0, 2, 0, -3, -1, 1}, out_feasible = {3, 1, 2, 1, 0, 1},
+ * out_gang_placed = {3, 0, 1}, final counts A 2, B 1, final gpu column {0, 0, 0}. */
+int ksched_schedule_constrained(ksched_ctx *ctx, int64_t p,
+        const int64_t *req_cpu, const int64_t *req_mem, const int64_t *req_pods, const uint64_t *selector,
+        int64_t n_gangs, const int64_t *gang_off /* n_gangs + 1, or NULL */, const int32_t *gang_min /* or NULL */,
+        const int32_t *spread_group /* p, or NULL */, const uint8_t *spread_enforce /* p, or NULL */,
+        const int64_t *req_ext /* n_ext * p, or NULL */,
+        int32_t *out_idx, double *out_score, int32_t *out_feasible, int32_t *out_gang_placed);
 
 /* Same, in two halves, with the pods staged in HBM: upload once, run many times (bench). */
 int ksched_upload_pods(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,

@@ -1,12 +1,14 @@
 // ksched_constraints.hip -- libksched: the three extensions of exact mode above the kernel.  The schedule calls
-// (ksched_schedule_gangs / _spread / _ext) check and pack on the host, stage what they packed and run k_exact with their
-// extension (ExactRun, ksched_exact.h); the table calls load and read the context's spread and extended-resource tables.
+// (ksched_schedule_gangs / _spread / _ext, and ksched_schedule_constrained for the three in one run) check and pack on
+// the host, stage what they packed and run k_exact with their extension (ExactRun, ksched_exact.h); the table calls load
+// and read the context's spread and extended-resource tables.
 #include <cstring>
 
 #include <new>
 
 #include "ksched_ctx.h"
 #include "ksched_ext.h"
+#include "ksched_gang.h"
 #include "ksched_spread.h"
 
 using namespace ksched;
@@ -22,7 +24,7 @@ struct Staged {
     size_t bytes;
 };
 
-// What the three schedule calls share once their checks have passed and their arrays are packed: the pods go up, the
+// What the schedule calls share once their checks have passed and their arrays are packed: the pods go up, the
 // staged arrays are reserved and copied in the stream of the kernel that reads them -- finished before the host arrays
 // go (ksched_upload_pods) -- then the run over them, the sync on both outcomes, and the results.
 template <class... S>
@@ -46,6 +48,17 @@ int schedule_staged(ksched_ctx *c, ExactRun run, const char *name, int64_t p, co
     if ((r = run_impl(c, run)) != KSCHED_OK) { ksched_sync(c); return r; }
     if ((r = ksched_sync(c)) != KSCHED_OK) return r;
     return ksched_download_results(c, p, oi, os, of);
+}
+
+// After a run with gangs: the members bound per gang come down, stats.placed is their sum (a rolled-back member is not
+// placed), and the caller gets them where it asked (out may be null).
+int gang_results(ksched_ctx *c, size_t ng, int32_t *out) {
+    std::vector<int32_t> gp(ng);
+    if (ng > 0) HIPCHK(c, hipMemcpy(gp.data(), c->d->gplaced, ng * 4, hipMemcpyDeviceToHost));
+    c->st.placed = 0;
+    for (int32_t v : gp) c->st.placed += v;
+    if (out && ng > 0) std::memcpy(out, gp.data(), ng * 4);
+    return KSCHED_OK;
 }
 
 }  // namespace
@@ -131,41 +144,21 @@ int ksched_schedule_gangs(ksched_ctx *c, int64_t p, const int64_t *rc, const int
     static_assert(KSCHED_GANG_MAX == kGangMax && KSCHED_GANG_REJECTED == kGangRejected, "gang constants");
     if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_gangs before load_nodes");
     if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_gangs is single-GPU (the exact kernel)");
-    if (p < 0 || n_gangs < 0 || n_gangs > p || !gang_off || gang_off[0] != 0 || gang_off[n_gangs] != p)
-        return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_off must run from 0 to p over n_gangs <= p gangs");
-    // every offset and minimum is checked before anything is written or allocated: each offset above its
-    // predecessor and at most p (so every gang's pods lie in [0, p)), each gang within the cap
-    for (int64_t g = 0; g < n_gangs; ++g) {
-        if (gang_off[g + 1] <= gang_off[g] || gang_off[g + 1] > p)
-            return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_off must be strictly increasing and end at p");
-        const int64_t size = gang_off[g + 1] - gang_off[g];
-        if (size > KSCHED_GANG_MAX) return fail(c, KSCHED_E_INVALID, "schedule_gangs: a gang has more than KSCHED_GANG_MAX members");
-        if (gang_min && (gang_min[g] < 1 || gang_min[g] > size))
-            return fail(c, KSCHED_E_INVALID, "schedule_gangs: gang_min must be in 1..size");
-    }
+    // every offset and minimum is checked before anything is written or allocated (ksched_gang.h)
+    if (const char *why = gang_check(p, n_gangs, gang_off, gang_min))
+        return fail(c, KSCHED_E_INVALID, std::string("schedule_gangs: ") + why);
     // staged per pod, so the kernel reads a gang's end with its last member's request: 0, or size | minimum << 16
-    static_assert(KSCHED_GANG_MAX < (1 << 15), "ExactArgs::gang_end packs size and minimum into 16 bits each");
     std::vector<int32_t> gend;
     try {
-        gend.assign((size_t)p, 0);
+        gang_pack_ends(p, n_gangs, gang_off, gang_min, &gend);
     } catch (const std::bad_alloc &) {
         return fail(c, KSCHED_E_NOMEM, "schedule_gangs: host staging buffer");
-    }
-    for (int64_t g = 0; g < n_gangs; ++g) {
-        const int32_t size = (int32_t)(gang_off[g + 1] - gang_off[g]);
-        gend[(size_t)gang_off[g + 1] - 1] = size | (gang_min ? gang_min[g] : size) << 16;
     }
     const size_t ng = (size_t)n_gangs;
     const int r = schedule_staged(c, kRunGang, "schedule_gangs", p, rc, rm, rp, sel, oi, os, of,
                                   Staged<int32_t>{c->d->gend, gend.data(), (size_t)p * 4},
                                   Staged<int32_t>{c->d->gplaced, nullptr, ng * 4});
-    if (r != KSCHED_OK) return r;
-    std::vector<int32_t> gp(ng);
-    if (ng > 0) HIPCHK(c, hipMemcpy(gp.data(), c->d->gplaced, ng * 4, hipMemcpyDeviceToHost));
-    c->st.placed = 0;
-    for (int32_t v : gp) c->st.placed += v;
-    if (out_gang_placed && ng > 0) std::memcpy(out_gang_placed, gp.data(), ng * 4);
-    return KSCHED_OK;
+    return r != KSCHED_OK ? r : gang_results(c, ng, out_gang_placed);
 }
 
 int ksched_schedule_spread(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
@@ -207,6 +200,49 @@ int ksched_schedule_ext(ksched_ctx *c, int64_t p, const int64_t *rc, const int64
     return schedule_staged(c, kRunExt, "schedule_ext", p, rc, rm, rp, sel, oi, os, of,
                            Staged<int64_t>{c->d->ereq, reqs.data(), reqs.size() * 8},
                            Staged<int32_t>{c->d->eword, words.data(), (size_t)p * 4});
+}
+
+// Gangs, spread and extended resources in one run of k_exact<kRunAll>.  A constraint whose argument is NULL is off for
+// the whole call: its per-pod words say so (gangs of one, no group, no request) and the kernel is not given its table.
+int ksched_schedule_constrained(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                                const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
+                                const int32_t *spread_group, const uint8_t *spread_enforce, const int64_t *req_ext,
+                                int32_t *oi, double *os, int32_t *of, int32_t *out_gang_placed) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_constrained before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_constrained is single-GPU (the exact kernel)");
+    if (p < 0 || p >= ((int64_t)1 << 30)) return fail(c, KSCHED_E_INVALID, "schedule_constrained: p must be in [0, 2^30)");
+    if (!gang_off && n_gangs != 0)
+        return fail(c, KSCHED_E_INVALID, "schedule_constrained: n_gangs must be 0 without gang_off");
+    if (spread_group && c->spread_S == 0)
+        return fail(c, KSCHED_E_STATE, "schedule_constrained: no spread table (ksched_load_spread after every ksched_load_nodes)");
+    if (req_ext && c->ext_R == 0)
+        return fail(c, KSCHED_E_STATE, "schedule_constrained: no extended-resource table (ksched_load_ext after every ksched_load_nodes)");
+    // every argument is checked, and every per-pod word is packed, before anything is written or allocated
+    std::vector<int32_t> gend, swords, ewords;
+    std::vector<int64_t> reqs;
+    try {
+        const char *why = gang_off ? gang_check(p, n_gangs, gang_off, gang_min) : nullptr;
+        if (!why && spread_group) why = spread_pack_words(p, c->spread_S, spread_group, spread_enforce, &swords);
+        if (!why && req_ext) why = ext_pack_pods(p, c->ext_R, req_ext, &reqs, &ewords);
+        if (why) return fail(c, KSCHED_E_INVALID, std::string("schedule_constrained: ") + why);
+        if (gang_off) gang_pack_ends(p, n_gangs, gang_off, gang_min, &gend);
+        else gang_pack_singles(p, &gend);
+        if (!spread_group) swords.assign((size_t)p, -1);
+        if (!req_ext) ewords.assign((size_t)p, 0);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "schedule_constrained: host staging buffer");
+    }
+    const size_t ng = gang_off ? (size_t)n_gangs : (size_t)p;  // the kernel's gangs: the caller's, or one per pod
+    c->all_spread = spread_group != nullptr;
+    c->all_ext = req_ext != nullptr;
+    const int r = schedule_staged(c, kRunAll, "schedule_constrained", p, rc, rm, rp, sel, oi, os, of,
+                                  Staged<int32_t>{c->d->gend, gend.data(), (size_t)p * 4},
+                                  Staged<int32_t>{c->d->gplaced, nullptr, ng * 4},
+                                  Staged<int32_t>{c->d->sword, swords.data(), (size_t)p * 4},
+                                  Staged<int64_t>{c->d->ereq, reqs.data(), reqs.size() * 8},
+                                  Staged<int32_t>{c->d->eword, ewords.data(), (size_t)p * 4});
+    return r != KSCHED_OK ? r : gang_results(c, ng, gang_off ? out_gang_placed : nullptr);
 }
 
 }  // extern "C"

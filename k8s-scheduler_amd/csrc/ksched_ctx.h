@@ -197,6 +197,7 @@ struct ksched_ctx {
     bool bound_valid = false;    // ksched_load_bound's table describes the loaded nodes (every load_nodes clears it)
     int32_t spread_D = 0, spread_S = 0;  // ksched_load_spread's table; 0: none (every load_nodes clears it)
     int32_t ext_R = 0;           // ksched_load_ext's table: its resource columns; 0: none (every load_nodes clears it)
+    bool all_spread = false, all_ext = false;  // ksched_schedule_constrained: the tables its kRunAll launch is given
     // pods
     int64_t p = 0;
     // batched workspace
@@ -290,7 +291,7 @@ bool lg_meet(ksched_lgroup *g, Mine mine, Last last) {
 }
 
 // ksched_engine.hip
-int run_impl(ksched_ctx *c, ExactRun run);  // ksched_run (kRunPlain), or the exact kernel over what an extension's call staged
+int run_impl(ksched_ctx *c, ExactRun run);  // ksched_run (kRunPlain), or the exact kernel over what a constraint call staged
 
 // ksched_xchg.hip
 bool group_min(ksched_group *g, int v, int *out);  // all ranks meet; the minimum of their values (false: a rank never arrived)

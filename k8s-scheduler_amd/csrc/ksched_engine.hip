@@ -462,8 +462,9 @@ int enqueue_persistent(ksched_ctx *c) {
     return KSCHED_OK;
 }
 
-// run (ExactRun, ksched_exact.h): a plain exact run, or the run of ksched_schedule_gangs / _spread / _ext over what
-// that call staged -- always k_exact, the multi-slot kernel, under the same geometry and launch rule as a plain run
+// run (ExactRun, ksched_exact.h): a plain exact run, or the run of ksched_schedule_gangs / _spread / _ext /
+// _constrained over what that call staged -- always k_exact, the multi-slot kernel, under the same geometry and launch
+// rule as a plain run
 int enqueue_exact(ksched_ctx *c, ExactRun run) {
     if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "exact mode is single-GPU; use batched mode across ranks");
     const int64_t n = c->n_local;
@@ -527,6 +528,14 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
         case kRunExt:
             a.ext = c->d->etab; a.ext_req = c->d->ereq; a.ext_word = c->d->eword; a.n_ext = c->ext_R;
             break;
+        case kRunAll:  // every staged word; a table only where ksched_schedule_constrained was given its argument
+            a.gang_end = c->d->gend; a.gang_placed = c->d->gplaced; a.sp_word = c->d->sword; a.ext_word = c->d->eword;
+            if (c->all_spread) {
+                a.sp_dom = c->d->sdom; a.sp_counts = c->d->scnt; a.sp_skew = c->d->sskew;
+                a.sp_D = c->spread_D; a.sp_S = c->spread_S;
+            }
+            if (c->all_ext) { a.ext = c->d->etab; a.ext_req = c->d->ereq; a.n_ext = c->ext_R; }
+            break;
     }
     HIPCHK(c, launch_exact(run, npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
                            G > 1 && !c->diag.plain_launch, c->stream));
@@ -537,8 +546,8 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
 
 }  // namespace
 
-// ksched_run, or the run of ksched_schedule_gangs / ksched_schedule_spread / ksched_schedule_ext: the exact kernel over
-// the staged gangs / spread words / extended requests whatever opts.mode
+// ksched_run, or the run of ksched_schedule_gangs / ksched_schedule_spread / ksched_schedule_ext /
+// ksched_schedule_constrained: the exact kernel over the staged gangs / spread words / extended requests whatever opts.mode
 int ksched::run_impl(ksched_ctx *c, ExactRun run) {
     if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "run before load_nodes");
     if (c->o.nranks > 1 && !c->comm && !c->group && !c->xchg_ready)

@@ -7,12 +7,16 @@
 
 namespace ksched {
 
-// Which extension of k_exact a launch runs (at most one): the value travels from the C entry point
-// (ksched_schedule_gangs / _spread / _ext, ksched_constraints.hip) through run_impl and enqueue_exact to the kernel's
-// template parameter.  kRunGang: the staged gangs in d->gend; kRunSpread: the staged words in d->sword and the context's
-// table; kRunExt: the staged requests in d->ereq / d->eword and the context's table.  Every run but kRunPlain is the
-// multi-slot kernel k_exact whatever opts.mode, under the same geometry and launch rule as a plain exact run.
-enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3 };
+// Which extension of k_exact a launch runs -- none, one, or (kRunAll) all three together: the value travels from the C
+// entry point (ksched_schedule_gangs / _spread / _ext / _constrained, ksched_constraints.hip) through run_impl and
+// enqueue_exact to the kernel's template parameter.  kRunGang: the staged gangs in d->gend; kRunSpread: the staged words
+// in d->sword and the context's table; kRunExt: the staged requests in d->ereq / d->eword and the context's table;
+// kRunAll (ksched_schedule_constrained): all of these in one launch, a rejected gang undoing its extended-resource and
+// spread commits with its node rows.  No other pairing is instantiated: a kRunAll launch switches a constraint it does
+// not need off by uniform runtime values (sp_S == 0 with every sp_word -1; n_ext == 0 with every ext_word 0; gangs of
+// one).  Every run but kRunPlain is the multi-slot kernel k_exact whatever opts.mode, under the same geometry and launch
+// rule as a plain exact run.
+enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3, kRunAll = 4 };
 
 struct ExactArgs {
     NodeRec *nodes;
@@ -34,13 +38,13 @@ struct ExactArgs {
     const int32_t *sp_dom;    // [n] node -> topology domain in [0, sp_D), or -1: the node does not carry the key
     int32_t *sp_counts;       // [sp_S][sp_D] matching pods bound per (group, domain): read at entry, written at exit
     const int32_t *sp_skew;   // [sp_S] the groups' maximum skew
-    int32_t sp_D, sp_S;       // sp_S * sp_D <= kSpreadMaxCells
+    int32_t sp_D, sp_S;       // sp_S * sp_D <= kSpreadMaxCells (kRunAll: sp_S == 0 -- no table, every sp_word is -1)
     const int32_t *sp_word;   // per pod: -1 (no group), or group << 1 | enforce; the kernel reads it with the request
     // k_exact<EXT> (ksched_schedule_ext): the context's extended-resource table and the staged requests
     int64_t *ext;             // [n_ext][n] allocatable per (resource, node): read at entry, written at exit
     const int64_t *ext_req;   // [p][kExtMax] requests, pod-major (columns at and beyond n_ext: 0)
     const int32_t *ext_word;  // per pod: bit r set where ext_req[i][r] != 0; the kernel reads it with the request
-    int32_t n_ext;            // 1..kExtMax
+    int32_t n_ext;            // 1..kExtMax (kRunAll: 0 -- no table, every ext_word is 0)
 };
 constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
 constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
@@ -55,8 +59,9 @@ constexpr int kExact1Block = 1024;  // k_exact1: the whole node set in one workg
 // host-side launchers (ksched_exact.hip).  fast53: every allocatable and request magnitude stays
 // below 2^52 for the whole call (host-checked), enabling (double)(a-r) == (double)a - (double)r.
 // One launch of k_exact<run>.  kRunGang: a.gang_end set (a.gang_placed may be null); kRunSpread: a.sp_* set; kRunExt:
-// a.ext* set, dynamic LDS of a.n_ext * block * npt * 8 bytes.  (An extension never runs k_exact1: the one-workgroup
-// kernel knows no gang log, spread table or extended-resource table.)
+// a.ext* set, dynamic LDS of a.n_ext * block * npt * 8 bytes; kRunAll: a.gang_end, a.sp_word and a.ext_word set, the
+// spread table's fields set or sp_S == 0, the extended-resource table's set or n_ext == 0.  (An
+// extension never runs k_exact1: the one-workgroup kernel knows no gang log, spread table or extended-resource table.)
 hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
                         bool cooperative, hipStream_t s);
 // exact mode on one workgroup of bs threads, npt node slots each: bs 1024 with npt 1-4 (resource) or 1-6, 8, 12, 16

@@ -1,6 +1,6 @@
 // ksched_exact.hip -- CDNA4 (gfx950) kernels of exact mode: k_exact with its three extensions (gangs, topology
-// spread, extended resources), the one-workgroup k_exact1, and their launchers.  Compiled with
-// -ffp-contract=off: every double op rounds individually, exactly like the Go reference.
+// spread, extended resources; each alone, or all three composed), the one-workgroup k_exact1, and their launchers.
+// Compiled with -ffp-contract=off: every double op rounds individually, exactly like the Go reference.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -65,6 +65,19 @@ __device__ __forceinline__ int64_t *ext_table() {
     }
 }
 
+// k_exact<kRunAll>: the topology domains of a workgroup's slots, slot s = tid + k * kExactBlock at [s] (consecutive
+// lanes read consecutive words: conflict-free).  The registers of the spread kernels are full,
+// and this kind carries the gang state and the extended-resource pointers beside them.
+template <bool ALL, int NPT>
+__device__ __forceinline__ int32_t *dom_table() {
+    if constexpr (ALL) {
+        __shared__ int32_t s_dom[kExactBlock * NPT];
+        return s_dom;
+    } else {
+        return nullptr;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Exact mode: one persistent launch schedules every pod in order.
 //   - workgroup g owns nodes [g*per_wg, (g+1)*per_wg); thread t holds nodes g*per_wg + t + k*256
@@ -104,10 +117,21 @@ __device__ __forceinline__ int64_t *ext_table() {
 //   uniform skip, so a pod that asks for nothing reads no LDS.  The owner lane of the winning slot subtracts the
 //   non-zero requests from its own slot's words.  Only the owning thread ever reads or writes a slot's words: no
 //   new barrier, exchange or wait; the tag and parity sequence unchanged.
+// ALL (ksched_schedule_constrained): the three together, the only pairing instantiated.  A
+//   constraint the call does not use is switched off by uniform runtime values: sp_S == 0 (no table is loaded or
+//   written back, every sp_word is -1), n_ext == 0 (no dynamic LDS, every ext_word is 0), gangs of one.  The slots'
+//   domains live in LDS (dom_table), not in registers.  A rejected gang's walk over the log also undoes the other two
+//   commits: the owner lane of a logged member's slot adds the member's non-zero requests back to its own words
+//   (ext_word / ext_req reloaded, uniform, as the cpu and memory requests are), and thread 0 of every workgroup
+//   decrements the count of every logged member with a group on a node that carries the key, keeping the row's
+//   minimum and the number of domains at it exact per decrement (a value below the minimum becomes the minimum, held
+//   once; a value equal to it is one more holder).  The next pod's gathers read the table before its first barrier, so
+//   a walk that moved the table ends with one barrier (workgroup-uniform: rejected, and a logged member was counted).
 // ------------------------------------------------------------------------------------------------
 template <int NPT, int PRIO, int DOM, bool LAB, bool F53, ExactRun RUN>
 __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
-    constexpr bool GANG = RUN == kRunGang, SPREAD = RUN == kRunSpread, EXT = RUN == kRunExt;
+    constexpr bool ALL = RUN == kRunAll;
+    constexpr bool GANG = RUN == kRunGang || ALL, SPREAD = RUN == kRunSpread || ALL, EXT = RUN == kRunExt || ALL;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -135,11 +159,17 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
             lab[k] = 0; pr[k] = 0.f; id[k] = kNoIdx;
         }
     }
-    [[maybe_unused]] int32_t dom[SPREAD ? NPT : 1];  // SPREAD: the slots' topology domains (-1: the node lacks the key)
+    // SPREAD: the slots' topology domains (-1: the node lacks the key).  ALL: the same in LDS, this thread's slot k at
+    // s_dom[k * kExactBlock] (no other thread touches it); every one -1 where sp_S == 0 says there is no table
+    [[maybe_unused]] int32_t dom[SPREAD && !ALL ? NPT : 1];
+    [[maybe_unused]] int32_t *const s_dom = ALL ? dom_table<ALL, NPT>() + tid : nullptr;
     [[maybe_unused]] SpreadTable *const sp = spread_table<SPREAD>();
     if constexpr (SPREAD) {
 #pragma unroll
-        for (int k = 0; k < NPT; ++k) dom[k] = id[k] != kNoIdx ? A.sp_dom[id[k]] : -1;
+        for (int k = 0; k < NPT; ++k) {
+            if constexpr (ALL) s_dom[k * kExactBlock] = A.sp_S > 0 && id[k] != kNoIdx ? A.sp_dom[id[k]] : -1;
+            else dom[k] = id[k] != kNoIdx ? A.sp_dom[id[k]] : -1;
+        }
         const int cells = A.sp_S * A.sp_D;
         for (int c = tid; c < cells; c += kExactBlock) sp->cnt[c] = A.sp_counts[c];
         __syncthreads();
@@ -217,7 +247,14 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
             if (id[k] != kNoIdx) {
                 bool f = fits(rc, rm, rp, sel, a0[k], a1[k], a2[k], lab[k], LAB);
                 if constexpr (SPREAD) {
-                    if (enf) f = f && dom[k] >= 0 && (int64_t)sp->cnt[srow + (dom[k] < 0 ? 0 : dom[k])] <= slim;
+                    if constexpr (ALL) {
+                        if (enf) {
+                            const int32_t dk = s_dom[k * kExactBlock];
+                            f = f && dk >= 0 && (int64_t)sp->cnt[srow + (dk < 0 ? 0 : dk)] <= slim;
+                        }
+                    } else {
+                        if (enf) f = f && dom[k] >= 0 && (int64_t)sp->cnt[srow + (dom[k] < 0 ? 0 : dom[k])] <= slim;
+                    }
                 }
                 if constexpr (EXT) {
                     if (eword != 0) {  // (uniform: a pod that asks for no column reads no LDS)
@@ -360,19 +397,53 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                     __syncthreads();  // the log's last entry
                     const int64_t first = i + 1 - gsize;
                     uint32_t dirty = 0;
+                    [[maybe_unused]] bool moved = false;  // ALL: the walk decremented a count of the spread table
 #pragma nounroll
                     for (int32_t m = 0; m < gsize; ++m) {
                         const int32_t li = s_log[m];
                         if (li < 0) continue;  // a member that failed keeps its own code
                         if (g == 0 && tid == 0) { A.out.idx[first + m] = kGangRejected; A.out.score[first + m] = 0.0; }
                         const int64_t urc = A.pods.rc[first + m], urm = A.pods.rm[first + m];
+                        [[maybe_unused]] const int32_t uew = ALL ? A.ext_word[first + m] : 0;
 #pragma unroll
                         for (int k = 0; k < NPT; ++k) {
                             if (id[k] == li) {  // the commit's inverse: a wrapping add undoes the wrapping subtract
                                 a0[k] = wadd(a0[k], urc); a1[k] = wadd(a1[k], urm); a2[k] = wadd(a2[k], 1);
                                 dirty |= 1u << k;
+                                if constexpr (ALL) {
+                                    if (uew != 0) {  // the owner lane: the member's non-zero requests back to its own words
+#pragma unroll
+                                        for (int r = 0; r < kExtMax; ++r)
+                                            if (uew >> r & 1) {
+                                                int64_t *w = ext + r * kExtCol + k * kExactBlock;
+                                                *w = wadd(*w, A.ext_req[(first + m) * kExtMax + r]);
+                                            }
+                                    }
+                                }
                             }
                         }
+                        if constexpr (ALL) {
+                            const int32_t usw = A.sp_word[first + m];
+                            if (usw >= 0) {  // (the same in every thread of every workgroup, as the increment was)
+                                const int32_t wd = A.sp_dom[__builtin_amdgcn_readfirstlane(li)];
+                                if (wd >= 0) {
+                                    moved = true;
+                                    if (tid == 0) {
+                                        // the row's minimum and its holders stay what a fresh load would count: a value
+                                        // below the minimum is the new minimum, held once; one equal to it, one more holder
+                                        const int32_t s = usw >> 1;
+                                        int32_t *row = sp->cnt + s * A.sp_D;
+                                        const int32_t v = row[wd] - 1;
+                                        row[wd] = v;
+                                        if (v < sp->mn[s]) { sp->mn[s] = v; sp->nmin[s] = 1; }
+                                        else if (v == sp->mn[s]) ++sp->nmin[s];
+                                    }
+                                }
+                            }
+                        }
+                    }
+                    if constexpr (ALL) {
+                        if (moved) __syncthreads();  // the next pod's gathers come before its first barrier
                     }
 #pragma unroll
                     for (int k = 0; k < NPT; ++k) {
@@ -557,9 +628,10 @@ namespace {
 
 template <int NPT, int PRIO, int DOM, bool LAB, bool F53, ExactRun RUN>
 hipError_t exact_one(const ExactArgs &a, int block, bool coop, hipStream_t s) {
-    constexpr bool EXT = RUN == kRunExt;
+    constexpr bool EXT = RUN == kRunExt || RUN == kRunAll;
     auto fn = k_exact<NPT, PRIO, DOM, LAB, F53, RUN>;
-    // EXT: the workgroup's slots of every column (ext_table), at most kExtMax * 256 * 8 * 8 B = 64 KiB
+    // EXT: the workgroup's slots of every column (ext_table), at most kExtMax * 256 * 8 * 8 B = 64 KiB (kRunAll without
+    // a table: n_ext == 0, none)
     const size_t lds = EXT ? (size_t)a.n_ext * kExactBlock * NPT * sizeof(int64_t) : 0;
     if (EXT && block != kExactBlock) return hipErrorInvalidValue;
     if (coop && a.G > 1) {
@@ -589,6 +661,7 @@ hipError_t exact_run(ExactRun run, int npt, const ExactArgs &a, int block, bool 
         case kRunGang: return exact_npt<PRIO, DOM, LAB, F53, kRunGang>(npt, a, block, coop, s);
         case kRunSpread: return exact_npt<PRIO, DOM, LAB, F53, kRunSpread>(npt, a, block, coop, s);
         case kRunExt: return exact_npt<PRIO, DOM, LAB, F53, kRunExt>(npt, a, block, coop, s);
+        case kRunAll: return exact_npt<PRIO, DOM, LAB, F53, kRunAll>(npt, a, block, coop, s);
     }
     return hipErrorInvalidValue;
 }
@@ -644,6 +717,13 @@ hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool
             break;
         case kRunExt:
             if (!a.ext || !a.ext_req || !a.ext_word || a.n_ext < 1 || a.n_ext > kExtMax) return hipErrorInvalidValue;
+            break;
+        case kRunAll:  // each kind's fields, with "no table" (sp_S == 0, n_ext == 0) accepted for this kind only
+            if (!a.gang_end || !a.sp_word || !a.ext_word) return hipErrorInvalidValue;
+            if (a.sp_S != 0 && (!a.sp_dom || !a.sp_counts || !a.sp_skew || a.sp_D < 1 || a.sp_S < 1 ||
+                                (int64_t)a.sp_D * a.sp_S > kSpreadMaxCells || a.sp_S > kSpreadMaxGroups))
+                return hipErrorInvalidValue;
+            if (a.n_ext != 0 && (!a.ext || !a.ext_req || a.n_ext < 1 || a.n_ext > kExtMax)) return hipErrorInvalidValue;
             break;
         default: return hipErrorInvalidValue;
     }

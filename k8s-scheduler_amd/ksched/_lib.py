@@ -123,6 +123,8 @@ SIGNATURES = [
     ("ksched_load_ext", C.c_int, [CTX, C.c_int32, I64P]),
     ("ksched_read_ext", C.c_int, [CTX, I64P]),
     ("ksched_schedule_ext", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, I64P, I32P, F64P, I32P]),
+    ("ksched_schedule_constrained", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, C.c_int64, I64P, I32P, I32P, U8P,
+                                              I64P, I32P, F64P, I32P, I32P]),
     ("ksched_upload_pods", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P]),
     ("ksched_run", C.c_int, [CTX]),
     ("ksched_sync", C.c_int, [CTX]),

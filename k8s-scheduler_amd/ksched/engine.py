@@ -298,7 +298,7 @@ class Engine:
         return self.results()
 
     def _schedule_with(self, name, req_cpu, req_mem, req_pods, selector, extra, tail=()):
-        """What schedule_gangs / schedule_spread / schedule_ext share: the contiguous request arrays and their length
+        """What schedule_gangs / schedule_spread / schedule_ext / schedule_constrained share: the contiguous request arrays and their length
         check, the three outputs, the call of ksched_<name> -- extra(p), the extension's arguments (checked against
         the pod count), go between the selectors and the outputs, tail after them -- and self.p.  Returns (idx,
         score, feasible)."""
@@ -399,6 +399,31 @@ class Engine:
             assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], p))
             return (L.ptr(re_, C.c_int64),)
         return self._schedule_with("schedule_ext", req_cpu, req_mem, req_pods, selector, extra)
+
+    def schedule_constrained(self, req_cpu, req_mem, req_pods, selector, gang_off=None, gang_min=None, group=None,
+                             enforce=None, req_ext=None):
+        """schedule_gangs(), schedule_spread() and schedule_ext() in one launch of the exact kernel
+        (ksched_schedule_constrained): a pod's node must fit, satisfy its spread constraint and hold its extended
+        requests; a placed pod commits its node row, the load_ext() columns and the load_spread() count, and a rejected
+        gang undoes all three.  Each constraint is off where its argument is None: gang_off (every pod a gang of one),
+        group (no pod in a spread group; no table needed, a loaded one stays), req_ext (the same for the ext table).
+        Returns (idx, score, feasible, gang_placed); gang_placed is empty when gang_off is None."""
+        off = None if gang_off is None else _i64(gang_off)
+        ng = 0 if off is None else off.shape[0] - 1
+        gmin = None if gang_min is None or off is None else np.ascontiguousarray(gang_min, dtype=np.int32)
+        assert ng >= 0 and (gmin is None or gmin.shape[0] == ng)
+        gr = None if group is None else np.ascontiguousarray(group, dtype=np.int32)
+        en = None if enforce is None or gr is None else np.ascontiguousarray(np.asarray(enforce) != 0, dtype=np.uint8)
+        re_ = None if req_ext is None else np.ascontiguousarray(req_ext, dtype=np.int64)
+        gp = np.empty(ng, np.int32)
+
+        def extra(p):
+            assert (gr is None or gr.shape[0] == p) and (en is None or en.shape[0] == p)
+            assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], p))
+            return (ng, L.ptr(off, C.c_int64), L.ptr(gmin, C.c_int32), L.ptr(gr, C.c_int32), L.ptr(en, C.c_uint8),
+                    L.ptr(re_, C.c_int64))
+        return self._schedule_with("schedule_constrained", req_cpu, req_mem, req_pods, selector, extra,
+                                   (L.ptr(gp, C.c_int32),)) + (gp,)
 
 
 def engine_for(cl, mode: Optional[int] = None, **kw) -> Engine:

@@ -545,6 +545,10 @@ class FakeCluster:
         rc, rm, rp = pack_pods(pods)
         sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
         idx, _, _, placed = self.engine.schedule_gangs(rc, rm, rp, sel, off, gmin)
+        return self._resolve_gangs(pods, off, gmin, idx, placed)
+
+    def _resolve_gangs(self, pods, off, gmin, idx, placed):
+        """A gang call's per-pod results, gang by gang, as the (pod, node | Exception) list (see schedule_gangs)."""
         out = []
         for g in range(len(gmin)):
             lo, hi = int(off[g]), int(off[g + 1])
@@ -592,6 +596,25 @@ class FakeCluster:
         sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
         idx, _, _ = self.engine.schedule_ext(rc, rm, rp, sel, req_ext)
         return self._resolve(pending, idx)
+
+    def schedule_constrained(self, pending: Optional[List[Pod]] = None):
+        """schedule_gangs, schedule_spread and schedule_ext in one engine call (ksched_schedule_constrained): the
+        pending pods are grouped into their gangs first (group_gangs reorders them), the spread and extended-resource
+        tables are built for the reordered list (spread_tables, ext_tables) and reloaded from self.pods' bound pods,
+        and one launch resolves every gang in order -- a rejected gang gives back the extended resources it took and
+        the spread counts it raised.  Resolved gang by gang exactly as schedule_gangs does: binds, GangRejected and
+        events."""
+        pending = self.unscheduled_pods() if pending is None else pending
+        pods, off, gmin = group_gangs(pending)
+        bound = [p for p in self.pods if p.node_name]
+        node_domain, skew, counts, group, enforce = spread_tables(self.nodes, bound, pods)
+        _, node_ext, req_ext = ext_tables(self.nodes, bound, pods)
+        self.engine.load_spread(node_domain, skew, counts)
+        self.engine.load_ext(node_ext)
+        rc, rm, rp = pack_pods(pods)
+        sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
+        idx, _, _, placed = self.engine.schedule_constrained(rc, rm, rp, sel, off, gmin, group, enforce, req_ext)
+        return self._resolve_gangs(pods, off, gmin, idx, placed)
 
     def schedule_pod(self, pod: Pod, selector: Optional[int] = None):
         """schedulePod (anchor/schedule.go:68-89) for a single pod."""
