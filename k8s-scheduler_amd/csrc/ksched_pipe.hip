@@ -70,7 +70,16 @@ __device__ __forceinline__ int wave_incl_sum(int v) {
     }
     return v;
 }
-
+// OR over the wave's lanes (DPP butterfly; every lane ends with the result)
+template <int S>
+__device__ __forceinline__ uint64_t or_stage(uint64_t v) {
+    return v | (((uint64_t)wpartner<S>((uint32_t)(v >> 32)) << 32) | wpartner<S>((uint32_t)v));
+}
+__device__ __forceinline__ uint64_t wave_or_u64(uint64_t v) {
+    v = or_stage<0>(v); v = or_stage<1>(v); v = or_stage<2>(v);
+    v = or_stage<3>(v); v = or_stage<4>(v); v = or_stage<5>(v);
+    return v;
+}
 // ---- barrier of ONE role's waves (LDS counter; s_barrier would wait for the other role too) ----------
 __device__ __forceinline__ void role_sync(unsigned *ctr, unsigned &target, unsigned nwaves) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -314,19 +323,21 @@ struct ScoreLayout {
     __host__ __device__ static size_t hrec_bytes(int R) { return (size_t)kSW * hrec_qw(R) * 64 * 2; }
     __host__ __device__ static size_t total_with_hrec(int R) { return total_screen(R) + hrec_bytes(R); }
     // the pair lists (score_role's exact phase), inside the fold area after the screened scan's bound lists, queue
-    // counts and row queues, in front of s_cnt: cnt[64] u32, nel[64] u32, key[kPairMax] f64, row[64][kPairCap] u16
+    // counts and row queues, in front of s_cnt: cnt[64] u32, nel[64] u32, key[kPairMax] f64, row[64][kPairCap] u16,
+    // wmask[kSW] u64
     __host__ __device__ static size_t pair_off(int R) {
         const size_t QW = (size_t)(R + kSW - 1) / kSW;
         return ((size_t)kSW * KC * 64 * 4 + kSW * 4 + 4 * kSW * QW + 15) / 16 * 16;
     }
-    static constexpr size_t pair_bytes = 64 * 4 * 2 + (size_t)kPairMax * 8 + (size_t)64 * kPairCap * 2;
+    static constexpr size_t pair_bytes = 64 * 4 * 2 + (size_t)kPairMax * 8 + (size_t)64 * kPairCap * 2 + kSW * 8;
     __host__ __device__ static bool pairs_fit(int R) { return pair_off(R) + pair_bytes <= (size_t)kSW * KC * 64 * 12; }
 };
 struct PairArea {
-    uint32_t *cnt;  // [64] needed rows per pod (atomic; past kPairCap: the batch takes the row path)
-    uint32_t *nel;  // [64] eligible keys per pod
-    double *key;    // [kPairMax] the pairs' exact keys (-inf: no key), pod-major
-    uint16_t *row;  // [64][kPairCap] the needed rows of each pod
+    uint32_t *cnt;    // [64] needed rows per pod (atomic; past kPairCap: the batch takes the row path)
+    uint32_t *nel;    // [64] eligible keys per pod
+    double *key;      // [kPairMax] the pairs' exact keys (-inf: no key), pod-major
+    uint16_t *row;    // [64][kPairCap] the needed rows of each pod
+    uint64_t *wmask;  // [kSW] the rows of each wave that some pod needs (keep_h: a wave has at most 64 rows, pipe_one)
 };
 
 // LDS of a merger workgroup: kMS slots of {control words | merge scratch | exchange messages}
@@ -376,6 +387,7 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
         pr.nel = pr.cnt + 64;
         pr.key = reinterpret_cast<double *>(pa + 512);
         pr.row = reinterpret_cast<uint16_t *>(pa + 512 + (size_t)kPairMax * 8);
+        pr.wmask = reinterpret_cast<uint64_t *>(pa + 512 + (size_t)kPairMax * 8 + (size_t)64 * kPairCap * 2);
     }
     constexpr int kST = kSW * 64;
     const int tid = threadIdx.x;
@@ -408,6 +420,9 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
     // the exact phase over (row, pod) pairs (PairArea) when the lists fit the fold area; else every needed row is
     // scored for every pod (the row path)
     constexpr bool kPairs = kScreen;
+    // Round 10's forms of pass 2 (per-lane row masks) and of the rank (the held pair) are built into the KC <= 4 kernels
+    // only: in the KC = 8 ones, at the register limit, they cost 20-28 B of scratch per lane
+    constexpr bool kMasks = KC <= 4;
     const bool pairs_ok = kPairs && !P.no_pairs && ScoreLayout<KC, K>::pairs_fit(R);
     constexpr int kScreenOffBatches = 16;
     constexpr bool kPrefetch = kSW > 8;  // wave kSW - 1 does not fold
@@ -535,6 +550,9 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
         if (kPairs && tid < 64) { pr.cnt[tid] = 0; pr.nel[tid] = 0; }
         bool pairs = false;          // this batch's exact phase runs over the pair lists
         int pT = 0, pincl = 0, pexcl = 0;  // ... pairs in all, and lane (pod) p's range [pexcl, pincl)
+        // the pair this thread scored, kept for the rank: its pod, the pod's range of pairs, its row and key
+        int hp = 0, hex = 0, hin = 0, hr = 0;
+        double hk = -__builtin_inf();
         const int64_t pod = p0 + lane;
         const bool active = (lane < P.B) && (pod < NP);
         const int64_t rc = active ? P.pods.rc[pod] : 0;
@@ -555,6 +573,7 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
             const int Rv = (int)((n - g + G - 1) / G);  // rows of this workgroup that hold a node
             const int QW = (R + kSW - 1) / kSW;
             const bool keep_h = P.screen_h != 0;      // pass 1 leaves a record per pair for pass 2
+            const bool masks = keep_h && kMasks;
             // the records of a wave's rows k (r = wave + k kSW): rows 2i and 2i + 1 share a 32-bit word per lane
             uint32_t *hw = reinterpret_cast<uint32_t *>(hrec) + (size_t)wave * (ScoreLayout<KC, K>::hrec_qw(R) / 2) * 64 + lane;
             // One row for every pod of the batch: the f32 fractions decide the predicate unless one lies
@@ -711,6 +730,33 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                 // inactive lane
                 const int tq = active ? screen_rec_threshold(L) : -1;
                 const int tqn = active ? screen_rec_threshold_nf(L) : -1;
+                if constexpr (kMasks) {
+                // the rows of this wave that this lane's pod needs, one bit per row (nr <= 64: pipe_one) -- no
+                // ballot and no queue here: the pair path never reads the row queue
+                uint64_t mine = 0;
+                for (int i0 = 0; i0 < nr; i0 += 16) {
+                    uint32_t x[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) x[u] = hw[(size_t)((i0 + 2 * u < nr ? i0 + 2 * u : i0) / 2) * 64];
+                    uint32_t m16 = 0;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        m16 |= (screen_rec_needed(x[u] & 0xffffu, tq, tqn) ? 1u : 0u) << (2 * u);
+                        m16 |= (screen_rec_needed(x[u] >> 16, tq, tqn) ? 1u : 0u) << (2 * u + 1);
+                    }
+                    mine |= (uint64_t)m16 << i0;
+                }
+                if (nr < 64) mine &= (1ull << nr) - 1ull;  // rows past the wave's last
+                // one slot reservation per lane for all of the wave's rows its pod needs
+                const int c = __builtin_popcountll(mine);
+                uint32_t s = c ? atomicAdd(&pr.cnt[lane], (uint32_t)c) : 0u;
+                for (uint64_t mm = mine; mm; mm &= mm - 1ull, ++s)
+                    if (s < (uint32_t)kPairCap)
+                        pr.row[lane * kPairCap + s] = (uint16_t)(wave + __builtin_ctzll(mm) * kSW);
+                // the wave's rows some pod needs: the count of distinct needed rows, and the row path's queue
+                const uint64_t wm = wave_or_u64(mine);
+                if (lane == 0) pr.wmask[wave] = wm;
+                } else {  // one ballot per row: the wave queues its needed rows as it goes
                 for (int i0 = 0; i0 < nr; i0 += 8) {
                     uint16_t hv[8];
 #pragma unroll
@@ -743,6 +789,7 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                                 pr.row[lane * kPairCap + s] = (uint16_t)(wave + (i0 + __builtin_ctz(mm)) * kSW);
                     }
                 }
+                }
             } else {
                 for (int r0 = wave; r0 < Rv; r0 += kSW * kSPU) {
                     float4 yv[kSPU];
@@ -765,12 +812,9 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                     }
                 }
             }
-            if (lane == 0) qcnt[wave] = qn;
+            if (!masks && lane == 0) qcnt[wave] = qn;
             if (g == 0 && tid == 0) trace_at(P, b, 14);
             sync();
-            int base[kSW], tot = 0;
-#pragma unroll
-            for (int w = 0; w < kSW; ++w) { base[w] = tot; tot += qcnt[w]; }
             // ---- the pair lists (every wave computes the same prefix over the pods' counts, lane = pod): when
             // none overflowed, thread e scores the e-th needed (row, pod) pair exactly -- ~4-8 pairs per pod
             // instead of every pod against every needed row ----
@@ -781,6 +825,14 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                 pT = __builtin_amdgcn_readlane(pincl, 63);
                 pairs = pairs_ok && __ballot(c > kPairCap) == 0 && pT <= kPairMax;  // workgroup-uniform
             }
+            // the distinct needed rows (tot) and the row queues' offsets: from the waves' counts, or (masks) from their
+            // masks -- then by one idle wave on the pair path (it has pairs only past 640 of them), by all on the row path
+            constexpr int kStatWave = kSW - 2;
+            int base[kSW], tot = 0;
+            if (!masks) {
+#pragma unroll
+                for (int w = 0; w < kSW; ++w) { base[w] = tot; tot += qcnt[w]; }
+            }
             if (pairs) {
                 for (int e0 = wave * 64; e0 < pT; e0 += kST) {  // wave-uniform trip count: every lane shuffles
                     const int e = e0 + lane;
@@ -788,11 +840,12 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                     int p = 0;  // the pod: how many lanes' inclusive counts are <= e
 #pragma unroll
                     for (int st = 32; st; st >>= 1) p += bperm(pincl, p + st - 1) <= ec ? st : 0;
-                    const int s = ec - bperm(pexcl, p);
+                    const int ex = bperm(pexcl, p);
+                    const int in = kMasks ? bperm(pincl, p) : 0;
                     const int64_t qc = bperm64(rc, p), qm = bperm64(rm, p), qp = bperm64(rp, p);
                     const uint64_t qs = LAB ? (uint64_t)bperm64((int64_t)sel, p) : 0ull;
                     if (e < pT) {
-                        const int r = pr.row[p * kPairCap + s];
+                        const int r = pr.row[p * kPairCap + (ec - ex)];
                         const NodeRec &nd = rows[r];
                         const int64_t ac = nd.a[0], am = nd.a[1], ap = nd.a[2];
                         const bool f = fits(qc, qm, qp, qs, ac, am, ap, nd.labels, LAB);
@@ -802,9 +855,24 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                                                                       nd.y[1], nd.y[2], y3, nd.price, &k);
                         pr.key[e] = el ? k : -__builtin_inf();
                         if (el) atomicAdd(&pr.nel[p], 1u);
+                        // this thread ranks the same pair after the barrier when the ranking waves hold every pair
+                        // at once (`held` below: both loops then have one trip with the same e)
+                        if constexpr (kMasks) { hp = p; hex = ex; hin = in; hr = r; hk = el ? k : -__builtin_inf(); }
                     }
                 }
-            } else
+                if (masks && wave == kStatWave)
+                    tot = (int)wave_sum_i64(lane < kSW ? (int64_t)__builtin_popcountll(pr.wmask[lane]) : 0);
+            } else {
+            if (masks) {
+                // the row queues from the waves' masks, in the order pass 2 used to build them (wave, then row)
+                const uint64_t wm = pr.wmask[wave];
+                if ((wm >> lane) & 1ull)
+                    qrow[wave * QW + __builtin_popcountll(wm & ((1ull << lane) - 1ull))] = (uint16_t)(wave + lane * kSW);
+                if (lane == 0) qcnt[wave] = __builtin_popcountll(wm);
+                sync();
+#pragma unroll
+                for (int w = 0; w < kSW; ++w) { base[w] = tot; tot += qcnt[w]; }
+            }
             // ---- the queued rows, dealt round-robin to the waves (balanced), scored exactly for every pod;
             // arrival order is not node order, so the insert ranks ties by node index ----
             for (int e = wave; e < tot; e += kSW) {
@@ -820,7 +888,8 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                                                               nd.af[2], nd.y[0], nd.y[1], nd.y[2], y3, nd.price, &k);
                 if (el) list_insert_ordered<KC>(key, idx, k, (int32_t)(P.node_offset + g + (int64_t)r * G));
             }
-            if (wave == 0 && lane == 0) { pc->s_ex = tot; pc->s_pairs = pairs ? pT : -1; }
+            }
+            if (wave == (masks ? kStatWave : 0) && lane == 0) { pc->s_ex = tot; pc->s_pairs = pairs ? pT : -1; }
         } else
         // kPU rows per step: their keys are independent f64 chains the scheduler interleaves; inserted
         // in ascending node order afterwards
@@ -906,36 +975,41 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                 prefetch_next();
             } else {
                 constexpr int RW = kPrefetch ? kSW - 1 : kSW;  // the ranking waves
+                // every pair at once: a thread ranks the pair it scored, whose pod, range, row and key it still holds
+                // -- no second search for the pod, no reload of the key (workgroup-uniform)
+                const bool held = kMasks && pT <= RW * 64;
                 for (int e0 = wave * 64; e0 < pT; e0 += RW * 64) {  // wave-uniform trip count: every lane shuffles
                     const int e = e0 + lane;
-                    const int ec = e < pT ? e : pT - 1;
-                    int p = 0;
+                    int p = hp, ex = hex, in = hin, r = hr;
+                    double k = hk;
+                    if (!held) {
+                        const int ec = e < pT ? e : pT - 1;
+                        p = 0;
 #pragma unroll
-                    for (int st = 32; st; st >>= 1) p += bperm(pincl, p + st - 1) <= ec ? st : 0;
-                    const int ex = bperm(pexcl, p), in = bperm(pincl, p);
-                    if (e < pT) {
-                        const double k = pr.key[e];
-                        if (k != -__builtin_inf()) {
-                            const uint16_t *prow = pr.row + p * kPairCap;
-                            const int r = prow[e - ex];
-                            int rank = 0;
-                            int e2 = ex;
-                            for (; e2 + 4 <= in; e2 += 4) {  // four loads in flight
-                                double k2[4];
-                                int r2[4];
+                        for (int st = 32; st; st >>= 1) p += bperm(pincl, p + st - 1) <= ec ? st : 0;
+                        ex = bperm(pexcl, p);
+                        in = bperm(pincl, p);
+                        if (e < pT) { k = pr.key[e]; r = pr.row[p * kPairCap + e - ex]; }
+                    }
+                    if (e < pT && k != -__builtin_inf()) {
+                        const uint16_t *prow = pr.row + p * kPairCap;
+                        int rank = 0;
+                        int e2 = ex;
+                        for (; e2 + 4 <= in; e2 += 4) {  // four loads in flight
+                            double k2[4];
+                            int r2[4];
 #pragma unroll
-                                for (int u = 0; u < 4; ++u) { k2[u] = pr.key[e2 + u]; r2[u] = prow[e2 + u - ex]; }
+                            for (int u = 0; u < 4; ++u) { k2[u] = pr.key[e2 + u]; r2[u] = prow[e2 + u - ex]; }
 #pragma unroll
-                                for (int u = 0; u < 4; ++u) rank += (k2[u] > k || (k2[u] == k && r2[u] < r)) ? 1 : 0;
-                            }
-                            for (; e2 < in; ++e2) {
-                                const double k2 = pr.key[e2];
-                                const int r2 = prow[e2 - ex];
-                                rank += (k2 > k || (k2 == k && r2 < r)) ? 1 : 0;
-                            }
-                            if (rank < KC && p < P.B && p0 + p < NP)
-                                store_entry(p, rank, k, (int32_t)(P.node_offset + g + (int64_t)r * G));
+                            for (int u = 0; u < 4; ++u) rank += (k2[u] > k || (k2[u] == k && r2[u] < r)) ? 1 : 0;
                         }
+                        for (; e2 < in; ++e2) {
+                            const double k2 = pr.key[e2];
+                            const int r2 = prow[e2 - ex];
+                            rank += (k2 > k || (k2 == k && r2 < r)) ? 1 : 0;
+                        }
+                        if (rank < KC && p < P.B && p0 + p < NP)
+                            store_entry(p, rank, k, (int32_t)(P.node_offset + g + (int64_t)r * G));
                     }
                 }
                 if (wave == 0 && lane < P.B && p0 + lane < NP) {
@@ -1637,7 +1711,8 @@ hipError_t pipe_one(const PipeLaunch &L0, int launch, PipeInfo *info, hipStream_
     constexpr size_t kLds = (size_t)160 * 1024;
     int R = 0;
     for (int r = 0; r < L.R; ++r) R = L.P[r].rows_per_wg > R ? L.P[r].rows_per_wg : R;
-    const int sh = ScoreLayout<KC, K>::total_with_hrec(R) <= kLds ? 1 : 0;
+    // (pass 2 holds a wave's needed rows in one 64-bit mask per lane: records that fit leave a wave fewer rows anyway)
+    const int sh = ScoreLayout<KC, K>::total_with_hrec(R) <= kLds && ScoreLayout<KC, K>::hrec_qw(R) <= 64 ? 1 : 0;
     const int so = ScoreLayout<KC, K>::total_screen(R) <= kLds ? 1 : 0;
     for (int r = 0; r < L.R; ++r) { L.P[r].screen_h = sh; L.P[r].screen_ok = so; }
     const size_t sl = sh ? ScoreLayout<KC, K>::total_with_hrec(R)

@@ -64,6 +64,26 @@ def main():
             v = us(v.astype(np.float64))
             q = np.percentile(v, [10, 50, 90, 99])
             print(f"{k:48s} {v.mean():7.2f} {q[0]:7.2f} {q[1]:7.2f} {q[2]:7.2f} {q[3]:7.2f} {v.max():9.1f}")
+    sc = b[(t[b, 11] > 0) & (t[b, 12] > 0) & (t[b, 14] > 0) & (t[b, 8] > 0) & (t[b, 9] > 0) & (t[b, 10] > 0)]
+    if len(sc):  # WG 0 wave 0's stamps of the screened scan (score_role)
+        pairs = (t[sc, 13] >> 32) & 0xffffffff
+        onp = pairs != 0xffffffff
+        scan = {
+            "  pass 1 (start -> 11)": t[sc, 11] - t[sc, 0],
+            "  bound (11 -> 12)": t[sc, 12] - t[sc, 11],
+            "  pass 2 (12 -> 14)": t[sc, 14] - t[sc, 12],
+            "  exact phase (14 -> 8)": t[sc, 8] - t[sc, 14],
+            "  barrier after the exact phase (8 -> 9)": t[sc, 9] - t[sc, 8],
+            "  rank and entry stores (9 -> 10)": t[sc, 10] - t[sc, 9],
+            "  drain, barrier, arrival (10 -> 5)": t[sc, 5] - t[sc, 10],
+            "  scan in all (start -> 5)": t[sc, 5] - t[sc, 0],
+        }
+        print(f"screened scan, WG 0 wave 0 ({len(sc)} batches; pair lists in {onp.sum()}, "
+              f"{pairs[onp].mean() if onp.any() else 0:.1f} pairs each, {(t[sc, 13] & 0xffffffff).mean():.2f} rows needed):")
+        for k, v in scan.items():
+            v = us(v.astype(np.float64))
+            q = np.percentile(v, [10, 50, 90, 99])
+            print(f"{k:48s} {v.mean():7.2f} {q[0]:7.2f} {q[1]:7.2f} {q[2]:7.2f} {q[3]:7.2f} {v.max():9.1f}")
     per = us((t[b, 4] - t[b - 1, 4]).astype(np.float64))
     med = np.median(per)
     slow = per > 3 * med
