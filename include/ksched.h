@@ -522,6 +522,12 @@ int ksched_set_timeout(ksched_ctx *ctx, int32_t persist_ms);
 int ksched_sync(ksched_ctx *ctx);                /* waits for the run; fills stats */
 int ksched_download_results(ksched_ctx *ctx, int64_t p, int32_t *out_idx, double *out_score, int32_t *out_feasible);
 int ksched_get_stats(const ksched_ctx *ctx, ksched_stats *out);
+/* Diagnostics (added within ABI 6: probe with dlsym(lib, "ksched_get_commit_stamps")): the first n <= 32 words of the
+ * persistent commit's KSCHED_COMMIT_STAMPS sums of the last synced run -- zeros unless the context was created with
+ * that variable set.  [12] rounds, [13] failed guesses, [14] batches, [15] batches whose early read of the merge count
+ * sufficed, [29] batches whose inherited keys were loaded before the merges' wait, [30] batches that tried (those with an
+ * older export to inherit, voided ones included); the others are cycle sums (ksched_diag.hip prints them). */
+int ksched_get_commit_stamps(const ksched_ctx *ctx, int32_t n, int64_t *out);
 /* Turns the sampled per-kernel HIP-event timing (opts.timing / opts.timing_every) on or off for the
  * following calls (every = 0: keep the current sampling period). */
 int ksched_set_timing(ksched_ctx *ctx, int32_t timing, int32_t every);

@@ -335,6 +335,9 @@ struct HandoffRes {
 struct NoHandoff {
     __device__ int operator()(HandoffRes *, XRec *) const { return 0; }
 };
+struct NoInhReady {
+    __device__ bool operator()() const { return false; }
+};
 // commit(b)'s hand-off record for commit(b + 1) (one lane), behind a drain of every store of commit(b): both granules
 // and every chunk of the export it announces carry the tag, and commit(b + 1) polls them all in one round of loads
 __device__ __forceinline__ void put_handoff(Ctl *ctl, int64_t batch, int n1, int64_t cursor, int64_t rseq, int64_t plan_next) {
@@ -346,11 +349,14 @@ __device__ __forceinline__ void put_handoff(Ctl *ctl, int64_t batch, int n1, int
 
 // wait(): called by every thread once the work that needs no candidate list is done (the persistent
 // commit waits there for the batch's merges); false = give up (the caller reports the timeout).
+// inh_ready(): the persistent commit, every thread, before wait(): true when the mergers' keys of export(b - 2) can be
+// loaded already.
 // Returns 1 done, 0 error (a wait timed out), 2 the call ended elsewhere (persistent pipeline: stop quietly).
 template <int K, int PRIO, int DOM, bool LAB, bool F53, bool COH, int NT = kSpcThreads, typename Wait = NoWait,
-          typename Handoff = NoHandoff>
+          typename Handoff = NoHandoff, typename InhReady = NoInhReady>
 __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem, const LanePods *pre = nullptr,
-                                                Wait wait = Wait{}, Handoff handoff = Handoff{}) {
+                                                Wait wait = Wait{}, Handoff handoff = Handoff{},
+                                                InhReady inh_ready = InhReady{}) {
     constexpr int kSpcWaves = NT / 64;
     constexpr int kSpcThreads = NT;
     constexpr bool LAG3 = COH;  // the persistent pipeline runs at lag kPipeLag = 3
@@ -602,6 +608,37 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             t_pre = __builtin_amdgcn_s_memtime() - t_start;
             if (lane == 0 && wave != 0) atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[9]), (unsigned long long)t_pre);
         }
+        // the mergers' summaries and key columns of export(b - 2): element (pod j, entry e) of inh keys[batch % 4] ->
+        // S[j][e].  Stored before the mergers wait for the score arrivals, so usually complete (inh_ready) while this
+        // workgroup would only sit in the merges' wait: loaded and stored to S there, off the merge -> hand-off path
+        constexpr int kX2Per = 64 * 64 / kSpcThreads + (64 * 64 % kSpcThreads != 0);
+        const double *x2col = reinterpret_cast<const double *>(A.inh + (size_t)4 * A.B * 32) + (size_t)(A.batch % 4) * A.B * 64;
+        auto load_inh = [&](double *x2v) {
+            if (wave == 0 && pj) {
+                const uint64_t *sm = reinterpret_cast<const uint64_t *>(A.inh + ((size_t)(A.batch % 4) * A.B + lane) * 32);
+                smv[0] = ld_coh(sm); smv[1] = ld_coh(sm + 1); smv[2] = ld_coh(sm + 2);
+            }
+#pragma unroll
+            for (int u = 0; u < kX2Per; ++u) {
+                const int i = tid + u * kSpcThreads;
+                x2v[u] = (i < 64 * 64 && (i & 63) < n2 && (i >> 6) < nb) ? ld_coh_f64(x2col + i) : 0.0;
+            }
+        };
+        auto store_inh = [&](const double *x2v) {
+#pragma unroll
+            for (int u = 0; u < kX2Per; ++u) {
+                const int i = tid + u * kSpcThreads;
+                if (i < 64 * 64 && (i & 63) < n2 && (i >> 6) < nb) m.S[(size_t)(i >> 6) * kSpcRow + (i & 63)] = x2v[u];
+            }
+        };
+        const bool inh_any = A.batch >= 2 && n2 > 0;  // (uniform: export(b - 2) is this workgroup's own)
+        const bool inh_early = inh_any && inh_ready();
+        if (inh_early) {
+            double x2e[kX2Per];
+            load_inh(x2e);
+            store_inh(x2e);
+            if (tid == 0 && A.trace_row) A.trace_row[26] = wall_clock64();  // the inherited keys in S, early
+        }
         if (!wait()) return 0;  // the batch's merges (a workgroup barrier)
         if (dbg) {
             const uint64_t t = __builtin_amdgcn_s_memtime();
@@ -609,19 +646,8 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             t_start = t;
         }
         load_lists();
-        if (wave == 0 && A.batch >= 2 && n2 > 0 && pj) {
-            const uint64_t *sm = reinterpret_cast<const uint64_t *>(A.inh + ((size_t)(A.batch % 4) * A.B + lane) * 32);
-            smv[0] = ld_coh(sm); smv[1] = ld_coh(sm + 1); smv[2] = ld_coh(sm + 2);
-        }
-        // the mergers' key columns of export(b - 2): element (pod j, entry e) of inh keys[batch % 4] -> S[j][e]
-        constexpr int kX2Per = 64 * 64 / kSpcThreads + (64 * 64 % kSpcThreads != 0);
         double x2v[kX2Per];
-        const double *x2col = reinterpret_cast<const double *>(A.inh + (size_t)4 * A.B * 32) + (size_t)(A.batch % 4) * A.B * 64;
-#pragma unroll
-        for (int u = 0; u < kX2Per; ++u) {
-            const int i = tid + u * kSpcThreads;
-            x2v[u] = (i < 64 * 64 && (i & 63) < n2 && (i >> 6) < nb) ? ld_coh_f64(x2col + i) : 0.0;
-        }
+        if (inh_any && !inh_early) load_inh(x2v);
 #if KSCHED_XCHG_DEBUG
         if (A.xp && A.xp->xdbg && A.dbg_act >= 0 && A.dbg_act < A.xp->xdbg_cap) {  // diagnostics: the lists as loaded
             uint64_t *sums = A.xp->xdbg + xdbg_sums_off(A.xp->xdbg_cap, A.xp->B, A.xp->R, K);
@@ -635,17 +661,15 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
         }
 #endif
         hash_lists();
-#pragma unroll
-        for (int u = 0; u < kX2Per; ++u) {
-            const int i = tid + u * kSpcThreads;
-            if (i < 64 * 64 && (i & 63) < n2 && (i >> 6) < nb) m.S[(size_t)(i >> 6) * kSpcRow + (i & 63)] = x2v[u];
-        }
+        if (tid == 0 && A.trace_row) A.trace_row[30] = wall_clock64();  // the lists hashed (wave 0)
+        if (inh_any && !inh_early) store_inh(x2v);
         // the touched-node screen's thresholds: the mergers' (list_thr_bits, entry 1's pad); the hand-off's barrier
         // publishes them
         if (SCR && wave == 0) m.thr[lane] = (pj && A.touch_screen) ? __uint_as_float((uint32_t)thr0) : -__builtin_inff();
         // ---- the hand-off: commit(b - 1) published (a workgroup barrier) ----
         // (wave 0 lane e < n1 receives entry e of export(b - 1) with the record: the same round of loads)
         if (A.xp) jitter_at(A.xp->jitter, A.batch, 103);  // P1 done late
+        if (tid == 0 && A.trace_row) A.trace_row[27] = wall_clock64();  // P1 done: into the hand-off
         HandoffRes ho;
         const int hr = handoff(&ho, &xi);
         if (hr != 0) return hr < 0 ? 0 : 2;  // timed out / the end of the call (or another workgroup's error)

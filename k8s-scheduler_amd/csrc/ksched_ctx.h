@@ -132,6 +132,7 @@ struct ksched_bufs {
 //   KSCHED_NO_SCREEN             0        the exact scan everywhere (A/B of the screened scan)
 //   KSCHED_NO_PAIRS              0        the screened scan's exact phase by rows (A/B of the pair lists)
 //   KSCHED_NO_TOUCH_SCREEN       0        the commit keys every touched node exactly
+//   KSCHED_NO_EARLY_INH          0        the commit loads the mergers' inherited keys only after its merges' wait
 //   KSCHED_POISON                0        workspace and LDS filled with 0xff before every persistent run
 //   KSCHED_LDS_FILL=<u32>        unset    (without POISON) LDS only, filled with this pattern before every persistent run
 //   KSCHED_LDS_ROLE / _LO / _HI  7, 0, LDS size  ... in these roles (bit mask), from / up to this byte of the dynamic LDS
@@ -155,6 +156,7 @@ struct ksched_diag {
     bool no_screen = false;       // KSCHED_NO_SCREEN
     bool no_pairs = false;        // KSCHED_NO_PAIRS
     bool touch_screen = true;     // off with KSCHED_NO_TOUCH_SCREEN
+    bool early_inh = true;        // off with KSCHED_NO_EARLY_INH
     bool poison = false;          // KSCHED_POISON
     std::optional<uint32_t> lds_fill;  // KSCHED_LDS_FILL (unset: no fill)
     int lds_role = 7;             // KSCHED_LDS_ROLE
@@ -225,6 +227,7 @@ struct ksched_ctx {
     int prog_G = 0, prog_B = 0, prog_rows = 0;
     int64_t xdbg_calls = 0;       // KSCHED_XCHG_DUMP: dumps written so far
     bool persist_stats = false;  // stats come from the Ctl copy queued behind the run
+    int64_t commit_dbg[32] = {};  // KSCHED_COMMIT_STAMPS: the last persistent run's words (ksched_get_commit_stamps)
     int64_t persist_B = 0;
     // device-side candidate exchange of the node-sharded persistent pipeline (ksched_xchg_*)
     void *d_rx = nullptr;          // this rank's receive ring (rx_prepare)

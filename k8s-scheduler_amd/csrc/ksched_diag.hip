@@ -28,6 +28,7 @@ void read_env(ksched_diag *d) {
     d->no_screen = env_int("KSCHED_NO_SCREEN", 0) != 0;
     d->no_pairs = env_int("KSCHED_NO_PAIRS", 0) != 0;
     d->touch_screen = env_int("KSCHED_NO_TOUCH_SCREEN", 0) == 0;
+    d->early_inh = env_int("KSCHED_NO_EARLY_INH", 0) == 0;
     d->poison = env_int("KSCHED_POISON", 0) != 0;
     if (const std::string f = env_str("KSCHED_LDS_FILL"); !f.empty()) d->lds_fill = (uint32_t)std::strtoul(f.c_str(), nullptr, 0);
     d->lds_role = env_int("KSCHED_LDS_ROLE", 7);
@@ -109,9 +110,9 @@ void print_persist_trace(ksched_ctx *c) {
                     (long long)hd[20], (double)hd[21] / std::max<int64_t>(1, hd[20]), (long long)hd[22]);
         if (hd[14])
             fprintf(stderr, "persist commit: batches=%lld rounds/batch %.3f guess iterations/round %.2f failures %lld | "
-                    "cycles/batch: before the wait %.0f (other waves %.0f) entry to past the wait %.0f (poll %.0f, poll + barrier %.0f, early read sufficed %.3f) | prologue %.0f guess %.0f evaluate %.0f check %.0f total %.0f\n",
+                    "cycles/batch: before the wait %.0f (other waves %.0f) entry to past the wait %.0f (poll %.0f, poll + barrier %.0f, early read sufficed %.3f, early inh read sufficed %lld of %lld) | prologue %.0f guess %.0f evaluate %.0f check %.0f total %.0f\n",
                     (long long)hd[14], (double)hd[12] / hd[14], (double)hd[5] / std::max<int64_t>(1, hd[12]),
-                    (long long)hd[13], (double)hd[6] / hd[14], (double)hd[9] / hd[14] / 11.0, (double)hd[7] / hd[14], (double)hd[10] / hd[14], (double)hd[11] / hd[14], (double)hd[15] / hd[14], (double)hd[0] / hd[14],
+                    (long long)hd[13], (double)hd[6] / hd[14], (double)hd[9] / hd[14] / 11.0, (double)hd[7] / hd[14], (double)hd[10] / hd[14], (double)hd[11] / hd[14], (double)hd[15] / hd[14], (long long)hd[29], (long long)hd[30], (double)hd[0] / hd[14],
                     (double)hd[1] / hd[14], (double)hd[2] / hd[14], (double)hd[3] / hd[14], (double)hd[4] / hd[14]);
         if (hd[14])  // a step whose commit made some lane's best touched slot worse rescanned before the rb2 bound
             fprintf(stderr, "persist commit rescans: steps with a worsened holder %lld, every holder kept %lld | plain rescans "

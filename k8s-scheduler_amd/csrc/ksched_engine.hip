@@ -338,6 +338,7 @@ int enqueue_persistent(ksched_ctx *c) {
     a.rescue_cap = c->diag.rescue_cap;
     a.rescue_low = c->diag.rescue_low;
     a.touch_screen = c->diag.touch_screen ? 1 : 0;
+    a.early_inh = c->diag.early_inh ? 1 : 0;
     if (c->diag.jitter) a.jitter = c->diag.jitter * 2654435761u + (uint32_t)(++c->jitter_calls) * 40503u + 1u;
     a.inh = reinterpret_cast<char *>(a.prog) + prog_b + resc_b;
     c->d_prog = a.prog;
@@ -734,6 +735,7 @@ static int sync_impl(ksched_ctx *c) {
         c->st.rescues = h->stats[4];
         c->st.pair_evals = (h->stats[0] + h->stats[3]) * c->persist_B * c->n_local;
         c->persist_stats = false;
+        if (c->d->dbg) HIPCHK(c, hipMemcpy(c->commit_dbg, c->d->dbg, sizeof(c->commit_dbg), hipMemcpyDeviceToHost));
         if (c->d_prog) {  // the score workgroups' exact / scanned row counts (progress words 4, 5)
             std::vector<uint64_t> w((size_t)kProgWords * c->prog_G);
             HIPCHK(c, hipMemcpy(w.data(), c->d_prog, w.size() * 8, hipMemcpyDeviceToHost));
@@ -761,6 +763,12 @@ int ksched_sync(ksched_ctx *c) {
 int ksched_get_stats(const ksched_ctx *c, ksched_stats *out) {
     if (!c || !out) return KSCHED_E_INVALID;
     *out = c->st;
+    return KSCHED_OK;
+}
+
+int ksched_get_commit_stamps(const ksched_ctx *c, int32_t n, int64_t *out) {
+    if (!c || !out || n < 0 || n > 32) return KSCHED_E_INVALID;
+    for (int i = 0; i < n; ++i) out[i] = c->commit_dbg[i];
     return KSCHED_OK;
 }
 

@@ -159,6 +159,9 @@ struct alignas(128) Ctl {
     // granules, each tagged b + 1: {tag, export count, cursor} and {tag, rescue requests, plan of b + 3}; commit(b + 1)
     // polls them instead of Ctl::committed and a second round of loads
     CtlLine hrec;
+    // merger slots done with their inherit_x2_keys stores of active batch a: counted like merged (slot a % 4, B per
+    // use), so commit(a) can load the key columns before its merges' wait instead of after it
+    CtlLine inh_done[4];
 };
 // The rescue request the commit writes (PersistArgs::rescue; sc1 stores, then Ctl::rescue_req) and the merger
 // slots' results after it: {rc, rm, rp, sel, nT} and the touched set's node indices, then Rec res[B].
@@ -477,6 +480,8 @@ struct PersistArgs {
     // the merger slots' keys of their pod against the entries of export(b - 2), which commit(b) inherits:
     // [4 batches][B] summaries {sum of predicate deltas, best key, best idx | entry << 32, -} then [4][B][64] keys
     char *inh;
+    int32_t early_inh;      // the commit loads those keys before its merges' wait when Ctl::inh_done shows them
+                            // (KSCHED_NO_EARLY_INH=1: always after the wait)
 };
 constexpr size_t inh_bytes(int B) { return (size_t)4 * B * 32 + (size_t)4 * B * 64 * 8; }
 // progress phases (PersistArgs::prog); kProgWords 8-byte words per workgroup
@@ -580,7 +585,8 @@ hipError_t launch_xchg_min(const PersistArgs &a, int32_t mine, int32_t *out, hip
 // trace columns: score start (WG 0 past its wait), last arrival, last merge done, commit start, commit end
 // trace row: 0-15 stamps (col 13: exact rows), 16 the commit's counters, 17 its rescue waits; with
 // KSCHED_COMMIT_STAMPS 18-21 its prologue / guess / evaluate / check cycles, 22-23 prologue marks (lists hashed, all
-// waves past), 24 before the wait, 25 entry -> past the wait, 26-30 the check step's split (update, probe, commit,
+// waves past), 24 before the wait, 25 entry -> past the wait, 26 the inherited keys loaded early (0: after the wait),
+// 27 P1 done, 30 the lists hashed; 26-30 the check step's split (update, probe, commit,
 // rescan, state load), 31-32 the guess step's (set-up, fixpoint), 33-36 the wave-0 state's (26-36: builds with
 // KSCHED_COMMIT_SPLIT only)
 constexpr int kTraceCols = 54;  // + 37-48: score WG 0's waves' pass-1 ends; 49-53: the commit's rounds

@@ -637,7 +637,7 @@ __global__ void k_ctl_init(Ctl *ctl, int B, int64_t P, int lag) {
     for (int i = 0; i < 5; ++i) ctl->stats[i] = 0;
     ctl->scored = 0;
     ctl->committed = 0;
-    for (int i = 0; i < 4; ++i) { ctl->arrive[i].v = 0; ctl->merged[i].v = 0; }
+    for (int i = 0; i < 4; ++i) { ctl->arrive[i].v = 0; ctl->merged[i].v = 0; ctl->inh_done[i].v = 0; }
     for (int i = 0; i < kCtlReplicas; ++i) ctl->committed_x[i].v = 0;
     ctl->rescue_req.v = 0;
     ctl->rescue_done.v = 0;

@@ -1353,6 +1353,17 @@ __device__ __forceinline__ void merge_role(const PersistArgs &P, char *sbase, co
             for (int m = g; m < P.B; m += kMS * P.M)
                 if (p0 + m < NP) inherit_x2_keys<PRIO, DOM, LAB, F53>(P, b, m, p0 + m, mtid);
         }
+        // ... and their own readiness count: commit(b) loads the columns before its merges' wait once every slot's
+        // stores are drained (Ctl::inh_done; one count per pod slot of every active batch, as Ctl::merged)
+        if (P.inh && P.early_inh) {
+            if (mtid < 64) drain_stores();  // inherit_x2_keys stores from the slot's wave 0 only
+            jitter_at(P.jitter, b, 110);
+            if (mtid == 0) {
+                unsigned long long cnt = 0;
+                for (int m = g; m < P.B; m += kMS * P.M) ++cnt;
+                __hip_atomic_fetch_add(&ctl->inh_done[slot].v, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
         if (!mwait(b, &ctl->arrive[slot].v, (use + 1) * (unsigned long long)G, kErrWaitArrive, kProgWaitArrive)) return;
         if (mtid == 0 && g == 0) trace_at(P, b, 7);
         const size_t part_elems = (size_t)P.B * G;
@@ -1470,6 +1481,7 @@ __device__ __forceinline__ void commit_role(const PersistArgs &P, char *smem, co
     __shared__ int s_stop;
     __shared__ HandoffRes s_ho;
     __shared__ int s_hr;
+    __shared__ int s_inh;
     Ctl *ctl = P.ctl;
     // k_ctl_init ran before this kernel on the stream: the call's initial cursor
     if (threadIdx.x == 0) {
@@ -1513,7 +1525,7 @@ __device__ __forceinline__ void commit_role(const PersistArgs &P, char *smem, co
         }
         if (threadIdx.x == 0) trace_at(P, b, 15);
         LanePods pre{0, 0, 0, 0};
-        unsigned long long early_m = 0;
+        unsigned long long early_m = 0, early_i = 0;
         if (act) {
             idle = 0;
             // the pods' requests: their loads overlap the prologue (a batch voided by commit(b - 1) discards them)
@@ -1521,10 +1533,54 @@ __device__ __forceinline__ void commit_role(const PersistArgs &P, char *smem, co
             // the merge count, read now: its latency hides behind the prologue (the merges are usually done)
             if (threadIdx.x == kPoller)
                 early_m = __hip_atomic_load(&ctl->merged[(nact - 1) % 4].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            // ... and the count of the mergers' inherited keys (Ctl::inh_done)
+            if (threadIdx.x == kPoller && P.early_inh)
+                early_i = __hip_atomic_load(&ctl->inh_done[(nact - 1) % 4].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+        // The commit's first wait, with the mergers' keys of export(b - 2) (inherit_x2_keys) in the batch: its poller
+        // watches both counts until the keys are all stored (Ctl::inh_done; the mergers store them before they wait for
+        // the score arrivals) or the merges are done (Ctl::merged).  Every thread calls it (a workgroup barrier).  True:
+        // the keys are there and merges are still out -- the commit loads the key columns now, off the merge ->
+        // hand-off path, and then waits for the merges as before.  False: the merges are done (wait_merged returns at
+        // once) or the part is off, and the columns are loaded after the wait.  A timeout is left to wait_merged.
+        bool merges_seen = false;
+        auto inh_ready = [&]() -> bool {
+            if (!act || !P.early_inh) return false;
+            if (threadIdx.x == kPoller) {
+                const int slot = (int)((nact - 1) % 4);
+                const unsigned long long want = (unsigned long long)((nact - 1) / 4 + 1) * (unsigned long long)P.B;
+                jitter_at(P.jitter, b, 111);
+                int r = early_m >= want ? 2 : early_i >= want ? 1 : 0;
+                if (!r) {
+                    prog_at(P, cslot, b, kProgWaitMerged, 0);
+                    const uint64_t t0 = wall_clock64();
+                    for (int it = 1;; ++it) {
+                        if ((it & 1023) == 0) {  // (as poll_ge: a read at the coherence point now and then)
+                            early_m = (unsigned long long)ld_rmw(&ctl->merged[slot].v);
+                            early_i = (unsigned long long)ld_rmw(&ctl->inh_done[slot].v);
+                        } else {
+                            early_m = __hip_atomic_load(&ctl->merged[slot].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            early_i = __hip_atomic_load(&ctl->inh_done[slot].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                        r = early_m >= want ? 2 : early_i >= want ? 1 : 0;
+                        if (r || ((it & 1023) == 0 && (int64_t)(wall_clock64() - t0) > P.timeout_ticks)) break;
+                        __builtin_amdgcn_s_sleep(1);
+                    }
+                }
+                s_inh = r;
+                if (P.cdbg) {  // diagnostics: the early inh read sufficed / was tried
+                    if (r == 1) atomicAdd(reinterpret_cast<unsigned long long *>(&P.cdbg[29]), 1ull);
+                    atomicAdd(reinterpret_cast<unsigned long long *>(&P.cdbg[30]), 1ull);
+                }
+            }
+            __syncthreads();
+            const int r = s_inh;
+            merges_seen = r == 2;
+            return r == 1;
+        };
         // the batch's merges (everything of the commit that needs no candidate list runs before this)
         auto wait_merged = [&]() -> bool {
-            if (act) {
+            if (act && !merges_seen) {
                 const uint64_t tw0 = P.cdbg ? __builtin_amdgcn_s_memtime() : 0;
                 if (threadIdx.x == kPoller) {
                     const int slot = (int)((nact - 1) % 4);
@@ -1636,7 +1692,7 @@ __device__ __forceinline__ void commit_role(const PersistArgs &P, char *smem, co
         ca.inh = P.inh;
         ca.timeout_ticks = P.timeout_ticks;
         ca.err = P.err;
-        const int rc = commit_spc_batch<K, PRIO, DOM, LAB, F53, true, kPipeThreads>(ca, cs, &pre, wait_merged, handoff);
+        const int rc = commit_spc_batch<K, PRIO, DOM, LAB, F53, true, kPipeThreads>(ca, cs, &pre, wait_merged, handoff, inh_ready);
         if (rc == 2) return;  // the call ended (or failed) elsewhere
         if (rc == 0) {
             if (threadIdx.x == 0) atomicCAS(P.err, 0, kErrWaitMerged);

@@ -130,6 +130,7 @@ SIGNATURES = [
     ("ksched_sync", C.c_int, [CTX]),
     ("ksched_download_results", C.c_int, [CTX, C.c_int64, I32P, F64P, I32P]),
     ("ksched_get_stats", C.c_int, [CTX, C.POINTER(Stats)]),
+    ("ksched_get_commit_stamps", C.c_int, [CTX, C.c_int32, I64P]),
     ("ksched_set_timing", C.c_int, [CTX, C.c_int32, C.c_int32]),
     ("ksched_set_timeout", C.c_int, [CTX, C.c_int32]),
     ("ksched_selftest_fastdiv", C.c_int, [CTX, C.c_int64, F64P, F64P, F64P, F64P]),

@@ -282,6 +282,13 @@ class Engine:
                     pipeline=PIPELINES.get(int(s.pipeline), str(int(s.pipeline))), rescues=s.rescues,
                     exact_rows=s.exact_rows, scan_rows=s.scan_rows)
 
+    def commit_stamps(self) -> dict:
+        """The persistent commit's counts of the last run (zeros unless KSCHED_COMMIT_STAMPS was set at create)."""
+        w = (C.c_int64 * 32)()
+        self._chk(L.lib().ksched_get_commit_stamps(self._ctx, 32, w), "get_commit_stamps")
+        return dict(rounds=w[12], failed_guesses=w[13], batches=w[14], early_merged=w[15], early_inh=w[29],
+                    early_inh_tried=w[30])
+
     def set_timing(self, on: bool, every: int = 0):
         """Sampled per-kernel HIP-event timing for the following calls (every: one batch in N)."""
         self._chk(L.lib().ksched_set_timing(self._ctx, int(bool(on)), int(every)), "set_timing")

@@ -33,6 +33,14 @@ def main():
     }
     if (t[b, 22] > 0).all():  # two commit workgroups: P1, the hand-off, the rest
         ph["P1: past merges' wait -> past the hand-off"] = t[b, 22] - t[b, 3]
+        p1 = b[(t[b, 27] > 0) & (t[b, 30] > 0)]
+        if len(p1) == len(b):  # P1's split: the lists loaded and hashed, the rest of P1, the hand-off itself
+            ph["  past the wait -> lists hashed"] = t[b, 30] - t[b, 3]
+            ph["  -> P1 done (key columns, thresholds)"] = t[b, 27] - t[b, 30]
+            ph["  -> past the hand-off"] = t[b, 22] - t[b, 27]
+            ei = t[b, 26] > 0
+            print(f"inherited keys loaded before the merges' wait in {ei.sum()} of {len(b)} batches, "
+                  f"{0.01 * (t[b, 3] - t[b, 26])[ei].mean() if ei.any() else 0:.2f} us before its end")
         ph["commit(b-1) end -> past the hand-off"] = t[b, 22] - t[b - 1, 4]
         ph["past the hand-off -> commit end"] = t[b, 4] - t[b, 22]
     sub = {}
@@ -115,11 +123,11 @@ def main():
     for lo, hi in ((0, 1), (1, 2), (2, 3), (3, 5), (5, 10), (10, 1 << 16)):
         s = (rounds >= lo) & (rounds < hi)
         if s.any():
-            kc = [t[b[s], c].mean() / 1e3 for c in (18, 19, 20, 21, 26, 27, 28, 29, 30, 31, 32)]
+            # (columns 26, 27 and 30 hold P1's stamps now: the check step's update / probe / commit / state-load split is gone)
+            kc = [t[b[s], c].mean() / 1e3 for c in (18, 19, 20, 21, 29, 31, 32)]
             print(f"  rounds [{lo},{hi}): {s.sum()} batches, commit mean {cm[s].mean():.1f} max {cm[s].max():.1f} us, total"
                   f" {cm[s].sum() / 1e3:.2f} ms | {kc[0]:.1f} / {kc[1]:.1f} / {kc[2]:.1f} / {kc[3]:.1f}"
-                  f" (guess: set-up {kc[9]:.1f} fixpoint {kc[10]:.1f}; check: update {kc[4]:.1f} probe {kc[5]:.1f}"
-                  f" commit {kc[6]:.1f} [state load {kc[8]:.1f}] rescan {kc[7]:.1f})")
+                  f" (guess: set-up {kc[5]:.1f} fixpoint {kc[6]:.1f}; check: rescan {kc[4]:.1f})")
     # which phase of the chain is the long one when the period is long
     chain = us((t[b, 4] - t[b - lag, 4]).astype(np.float64))
     print(f"chain (commit(b-L) end -> commit(b) end): mean {chain.mean():.1f} p50 {np.median(chain):.1f} us = "
