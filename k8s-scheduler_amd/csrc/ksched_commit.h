@@ -29,7 +29,7 @@
 #define KSCHED_XCHG_DEBUG 0  // the exchange diagnostics of tests/diag/xchg_ring_experiment.py (a separate build)
 #endif
 
-#include "ksched_kernels.h"
+#include "ksched_pipe.h"  // the persistent (COH) paths: PersistArgs, the tagged records, the rescue request
 
 namespace ksched {
 
@@ -299,7 +299,7 @@ __device__ __forceinline__ bool commit_rescue(const CommitArgs &A, int f, int64_
 
 // One batch's ordered commit by the whole workgroup (kSpcThreads).  COH: the lists arrive from other
 // workgroups of a running persistent kernel (sc1 loads), and what the score workgroups read back --
-// the XBuf export, the next plans, the cursor -- leaves as sc1 stores (ksched_persist.hip).
+// the XBuf export, the next plans, the cursor -- leaves as sc1 stores (ksched_pipe.hip).
 // a batch's pod requests, lane = pod (loaded early by the persistent commit, before its wait)
 struct LanePods {
     int64_t rc, rm, rp;

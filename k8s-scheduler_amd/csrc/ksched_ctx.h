@@ -20,6 +20,8 @@
 #include "ksched.h"
 #include "ksched_exact.h"
 #include "ksched_kernels.h"
+#include "ksched_pipe.h"
+#include "ksched_stream.h"
 
 // In-process rank group (include/ksched.h).  The all-gather is host-coordinated and synchronous:
 // every rank waits for its own send block, the ranks meet, each copies every rank's block into its

@@ -1,5 +1,5 @@
-// ksched_merge.h -- device code shared by the stream pipeline (ksched_kernels.hip) and the persistent
-// pipeline (ksched_persist.hip): per-lane sorted top-K insert and the per-pod rank merge of the score
+// ksched_merge.h -- device code shared by the stream pipeline (ksched_stream.hip) and the persistent
+// pipeline (ksched_pipe.hip): per-lane sorted top-K insert and the per-pod rank merge of the score
 // workgroups' lists.  The ranked dry run (ksched_rank.hip) builds its 64-entry lists on the wave sort below.
 #pragma once
 

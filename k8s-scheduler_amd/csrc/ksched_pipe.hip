@@ -1,18 +1,20 @@
 // ksched_pipe.hip -- the batched pipeline as ONE persistent kernel.
 //
-// k_pipe, 1 + G + M workgroups of 768 threads, one per CU (its LDS request excludes a second one), every
+// k_pipe (interface: ksched_pipe.h), kCommitWGs + G + M workgroups of 768 threads, one per CU (its LDS request
+// excludes a second one), every
 // workgroup resident for the whole call -- guaranteed by the launch itself: a cooperative launch of a
 // grid that the occupancy query admits (nothing of the call runs beside it), so no protocol below
 // assumes a dispatch order, a co-location or a second kernel.  Roles come from blockIdx:
 //
-//   workgroup 0          the COMMIT (all 12 waves): per active batch, wait for its B merges, replay the
-//                        batch in pod order against the exact current state (commit_spc_batch), export
-//                        the touched nodes, plan batch b + kPipeLag, publish Ctl::committed = b + 1.
-//   workgroup 1 + g      SCORE (g < G, 12 waves): the rows j = g (mod G) of this rank's nodes live in LDS
+//   workgroups 0, 1      the COMMITs (kCommitWGs = 2, all 12 waves; they alternate batches): per active batch,
+//                        wait for its B merges, replay the batch in pod order against the exact current state
+//                        (commit_spc_batch), export the touched nodes, plan batch b + kPipeLag, hand over to
+//                        the other commit workgroup, publish Ctl::committed = b + 1.
+//   workgroup 2 + g      SCORE (g < G, 12 waves): the rows j = g (mod G) of this rank's nodes live in LDS
 //                        for the whole call; per batch wait for commit(b - kPipeLag), apply its export to
 //                        the rows, score 64 pods x the rows (lane = pod; the screened scan), fold the wave
 //                        lists to one top-KC list per pod, store it, arrive.
-//   workgroup 1 + G + i  MERGE (kMS slots of kMT threads): slot id merges pods id, id + kMS M, ... of
+//   workgroup 2 + G + i  MERGE (kMS slots of kMT threads): slot id merges pods id, id + kMS M, ... of
 //                        every batch: wait for the G arrivals, merge the G lists into the pod's K-entry
 //                        Rec list [R > 1: exchange with the peer ranks + rank merge], count the merge.
 //

@@ -186,7 +186,7 @@ def test_xchg_sharded_rescue(gpu_available, oracle_mod, world):
 
 
 def test_xchg_tags_wrap_across_calls(gpu_available, oracle_mod, monkeypatch):
-    """Granule tags keep 15 bits (ksched_kernels.h gran_tag).  Tags started just below 2^15 (KSCHED_XCHG_EPOCH_BASE)
+    """Granule tags keep 15 bits (ksched_pipe.h gran_tag).  Tags started just below 2^15 (KSCHED_XCHG_EPOCH_BASE)
     cross the wrap during these calls, and calls with rescues alternate with short calls that write only some
     message slots and no rescue area: every call zeroes its ring's message and rescue areas before the rank barrier
     (ksched_xchg.hip rx_zero_regions), so no wait can take an earlier call's granule.  Bit-exact."""
