@@ -537,6 +537,47 @@ int ksched_set_timing(ksched_ctx *ctx, int32_t timing, int32_t every);
  * check of the division used by every score kernel). */
 int ksched_selftest_fastdiv(ksched_ctx *ctx, int64_t n, const double *a, const double *b, double *out_native,
                             double *out_fast);
+/* Diagnostics (added within ABI 6: probe with dlsym): the device's own score, screen, record and wave primitives,
+ * run in isolation on arrays of operands.  They prove the primitives' source semantics under the library's
+ * compile flags, not the instruction stream of the kernels that inline them.  Arrays are structure-of-arrays:
+ * "[k][n]" is k rows of n elements.  req / alloc: [3][n] (cpu, memory, pods).
+ *   score:     out_score [3][n] resource_score, resource_score_fast<false>, <true>; out_upper [2][n]
+ *              resource_score_upper<false>, <true>; out_recip [3][n] recip((double)alloc); out_flags [n]: bit 0 / 1
+ *              near1 of the two upper bounds, bit 2 / 3 eligible (resource priority) in the all-node / feasible
+ *              domain, bit 4 the fit predicate.
+ *   price_key: out_key[i] = the best-price key of price[i].
+ *   screen:    out_f32 [13][n] screen_req x3, screen_recip x3, screen_y x3, screen_pair from screen_recip, from
+ *              screen_y, screen_fast's v and mx; out_u32 [8][n] lo_ok of the two screen_pair, amb, rf, pass 1's
+ *              record: all-node domain by screen_rec / screen_rec_nf, by the packed conversion, feasible domain
+ *              likewise (no labels).
+ *   rec_w:     out [4][n] screen_rec_w(w), screen_rec_w(w2), low and high half of the packed conversion of (w, w2).
+ *   threshold: out [4][n] screen_rec_threshold(L), screen_rec_threshold_nf(L), screen_rec_needed(rec, those two),
+ *              screen_rec_needed(rec, -1, -1).
+ *   wave:      ncases cases of 64 lanes.  sort_code / sort_idx [6][64 ncases]: the pairs in aligned sorted runs of
+ *              1, 2, 4, 8, 16, 32; key / idx / aux [64 ncases]; cut / nv [ncases].  out_u64 [12][64 ncases]: the six
+ *              sorted codes, wave_max_u64 and wave_sum_i64 of arrangement 0's codes, the key bits of wave_argbest and
+ *              wave_argbest_fast, key_code(key), wave_or_u64 of arrangement 0's codes.  out_i32 [13][64 ncases]: the
+ *              six sorted idx, wave_rank of the lane's own pair and wave_min_i32(idx) (arrangement 0), the two
+ *              arg-bests' idx, their aux, list_thr_bits(cut, lanes < nv, key_code(key)).
+ *   list:      key / idx [steps][n]: one sequence per element (idx 0x7fffffff: skipped) through
+ *              list_insert_ordered<2, 4, 8, 16>; out_key / out_idx [30][n]: the four lists one after the other.
+ *   slots:     x [2][steps][4][n]: two sets of steps of four lower bounds per element through bound_slots<KC> into
+ *              KC slots, sort_desc_u32 of each set, topk_merge_u32 of the two.  out [60][n]: for KC = 4 (bound_slots'
+ *              maximum form; 20 rows) then KC = 8 (its insertion form; 40 rows) the raw slots of set 0, of set 1, the
+ *              sorted slots of set 0, of set 1, the merged list. */
+int ksched_selftest_score(ksched_ctx *ctx, int64_t n, const int64_t *req, const int64_t *alloc, double *out_score,
+                          double *out_upper, double *out_recip, int32_t *out_flags);
+int ksched_selftest_price_key(ksched_ctx *ctx, int64_t n, const float *price, double *out_key);
+int ksched_selftest_screen(ksched_ctx *ctx, int64_t n, const int64_t *req, const int64_t *alloc, float *out_f32,
+                           uint32_t *out_u32);
+int ksched_selftest_rec_w(ksched_ctx *ctx, int64_t n, const float *w, const float *w2, uint32_t *out);
+int ksched_selftest_threshold(ksched_ctx *ctx, int64_t n, const float *L, const uint32_t *rec, int32_t *out);
+int ksched_selftest_wave(ksched_ctx *ctx, int64_t ncases, const uint64_t *sort_code, const int32_t *sort_idx,
+                         const double *key, const int32_t *idx, const int32_t *aux, const int32_t *cut,
+                         const int32_t *nv, uint64_t *out_u64, int32_t *out_i32);
+int ksched_selftest_list(ksched_ctx *ctx, int64_t n, int32_t steps, const double *key, const int32_t *idx,
+                         double *out_key, int32_t *out_idx);
+int ksched_selftest_slots(ksched_ctx *ctx, int64_t n, int32_t steps, const uint32_t *x, uint32_t *out);
 
 /* ---- host packer: Go-exact Kubernetes quantity parsing ----
  * s == NULL means the key is absent from the ResourceList.  KSCHED_E_PARSE on the reference's

@@ -58,6 +58,39 @@ bool ksched::build_bound_table(int64_t n, int64_t nb, const int32_t *node_idx, c
     return true;
 }
 
+// The primitive self-tests (ksched_selftest.hip), all in ksched_selftest_fastdiv's pattern: copy in, launch on c->stream, copy out.
+// One device block holds every array (256-byte aligned); launch(in, out) gets their device pointers in order.
+namespace {
+struct StBuf {
+    const void *in;  // host source (inputs), or nullptr
+    void *out;       // host destination (outputs), or nullptr
+    size_t bytes;
+};
+template <typename Launch>
+int selftest_run(ksched_ctx *c, const char *what, const std::vector<StBuf> &bufs, Launch launch) {
+    for (const StBuf &b : bufs)
+        if (b.bytes > 0 && !b.in && !b.out) return KSCHED_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->dev));
+    std::vector<size_t> off(bufs.size());
+    size_t total = 0;
+    for (size_t k = 0; k < bufs.size(); ++k) { off[k] = total; total += (bufs[k].bytes + 255) / 256 * 256; }
+    char *d = nullptr;
+    HIPCHK(c, hipMalloc(&d, total ? total : 256));
+    std::vector<void *> p(bufs.size());
+    for (size_t k = 0; k < bufs.size(); ++k) p[k] = d + off[k];
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < bufs.size() && e == hipSuccess; ++k)
+        if (bufs[k].in && bufs[k].bytes) e = hipMemcpyAsync(p[k], bufs[k].in, bufs[k].bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch(p);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    for (size_t k = 0; k < bufs.size() && e == hipSuccess; ++k)
+        if (bufs[k].out && bufs[k].bytes) e = hipMemcpy(bufs[k].out, p[k], bufs[k].bytes, hipMemcpyDeviceToHost);
+    hipFree(d);
+    if (e != hipSuccess) return fail(c, KSCHED_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    return KSCHED_OK;
+}
+}  // namespace
+
 extern "C" {
 
 int ksched_load_nodes(ksched_ctx *c, int64_t n, const int64_t *ac, const int64_t *am, const int64_t *ap,
@@ -330,6 +363,122 @@ int ksched_selftest_fastdiv(ksched_ctx *c, int64_t n, const double *a, const dou
     hipFree(d);
     if (e != hipSuccess) return fail(c, KSCHED_E_DEVICE, std::string("selftest_fastdiv: ") + hipGetErrorString(e));
     return KSCHED_OK;
+}
+
+// The primitive self-tests (ksched_selftest.hip), all in the pattern above (selftest_run).
+int ksched_selftest_score(ksched_ctx *c, int64_t n, const int64_t *req, const int64_t *alloc, double *out_score,
+                          double *out_upper, double *out_recip, int32_t *out_flags) {
+    if (!c || n < 0 || (n > 0 && (!req || !alloc || !out_score || !out_upper || !out_recip || !out_flags)))
+        return KSCHED_E_INVALID;
+    if (n == 0) return KSCHED_OK;
+    const size_t q = (size_t)n;
+    return selftest_run(c, "selftest_score",
+                        {{req, nullptr, q * 24}, {alloc, nullptr, q * 24}, {nullptr, out_score, q * 24},
+                         {nullptr, out_upper, q * 16}, {nullptr, out_recip, q * 24}, {nullptr, out_flags, q * 4}},
+                        [&](const std::vector<void *> &p) {
+                            return launch_selftest_score(n, (const int64_t *)p[0], (const int64_t *)p[1], (double *)p[2],
+                                                         (double *)p[3], (double *)p[4], (int32_t *)p[5], c->stream);
+                        });
+}
+
+int ksched_selftest_price_key(ksched_ctx *c, int64_t n, const float *price, double *out_key) {
+    if (!c || n < 0 || (n > 0 && (!price || !out_key))) return KSCHED_E_INVALID;
+    if (n == 0) return KSCHED_OK;
+    const size_t q = (size_t)n;
+    return selftest_run(c, "selftest_price_key", {{price, nullptr, q * 4}, {nullptr, out_key, q * 8}},
+                        [&](const std::vector<void *> &p) {
+                            return launch_selftest_price(n, (const float *)p[0], (double *)p[1], c->stream);
+                        });
+}
+
+int ksched_selftest_screen(ksched_ctx *c, int64_t n, const int64_t *req, const int64_t *alloc, float *out_f32,
+                           uint32_t *out_u32) {
+    if (!c || n < 0 || (n > 0 && (!req || !alloc || !out_f32 || !out_u32))) return KSCHED_E_INVALID;
+    if (n == 0) return KSCHED_OK;
+    const size_t q = (size_t)n;
+    return selftest_run(c, "selftest_screen",
+                        {{req, nullptr, q * 24}, {alloc, nullptr, q * 24}, {nullptr, out_f32, q * 13 * 4},
+                         {nullptr, out_u32, q * 8 * 4}},
+                        [&](const std::vector<void *> &p) {
+                            return launch_selftest_screen(n, (const int64_t *)p[0], (const int64_t *)p[1], (float *)p[2],
+                                                          (uint32_t *)p[3], c->stream);
+                        });
+}
+
+int ksched_selftest_rec_w(ksched_ctx *c, int64_t n, const float *w, const float *w2, uint32_t *out) {
+    if (!c || n < 0 || (n > 0 && (!w || !w2 || !out))) return KSCHED_E_INVALID;
+    if (n == 0) return KSCHED_OK;
+    const size_t q = (size_t)n;
+    return selftest_run(c, "selftest_rec_w", {{w, nullptr, q * 4}, {w2, nullptr, q * 4}, {nullptr, out, q * 16}},
+                        [&](const std::vector<void *> &p) {
+                            return launch_selftest_rec_w(n, (const float *)p[0], (const float *)p[1], (uint32_t *)p[2],
+                                                         c->stream);
+                        });
+}
+
+int ksched_selftest_threshold(ksched_ctx *c, int64_t n, const float *L, const uint32_t *rec, int32_t *out) {
+    if (!c || n < 0 || (n > 0 && (!L || !rec || !out))) return KSCHED_E_INVALID;
+    if (n == 0) return KSCHED_OK;
+    const size_t q = (size_t)n;
+    return selftest_run(c, "selftest_threshold", {{L, nullptr, q * 4}, {rec, nullptr, q * 4}, {nullptr, out, q * 16}},
+                        [&](const std::vector<void *> &p) {
+                            return launch_selftest_threshold(n, (const float *)p[0], (const uint32_t *)p[1],
+                                                             (int32_t *)p[2], c->stream);
+                        });
+}
+
+int ksched_selftest_wave(ksched_ctx *c, int64_t ncases, const uint64_t *sort_code, const int32_t *sort_idx,
+                         const double *key, const int32_t *idx, const int32_t *aux, const int32_t *cut,
+                         const int32_t *nv, uint64_t *out_u64, int32_t *out_i32) {
+    if (!c || ncases < 0 || ncases > (1 << 20) ||
+        (ncases > 0 && (!sort_code || !sort_idx || !key || !idx || !aux || !cut || !nv || !out_u64 || !out_i32)))
+        return KSCHED_E_INVALID;
+    if (ncases == 0) return KSCHED_OK;
+    const size_t l = (size_t)ncases * 64;
+    return selftest_run(c, "selftest_wave",
+                        {{sort_code, nullptr, l * 6 * 8}, {sort_idx, nullptr, l * 6 * 4}, {key, nullptr, l * 8},
+                         {idx, nullptr, l * 4}, {aux, nullptr, l * 4}, {cut, nullptr, (size_t)ncases * 4},
+                         {nv, nullptr, (size_t)ncases * 4}, {nullptr, out_u64, l * 12 * 8}, {nullptr, out_i32, l * 13 * 4}},
+                        [&](const std::vector<void *> &p) {
+                            WaveTestArgs a{};
+                            a.ncases = ncases;
+                            a.scode = (const uint64_t *)p[0]; a.sidx = (const int32_t *)p[1];
+                            a.key = (const double *)p[2]; a.kidx = (const int32_t *)p[3]; a.aux = (const int32_t *)p[4];
+                            a.cut = (const int32_t *)p[5]; a.nv = (const int32_t *)p[6];
+                            uint64_t *u = (uint64_t *)p[7];
+                            int32_t *v = (int32_t *)p[8];
+                            a.ocode = u; a.red_max = u + 6 * l; a.red_sum = (int64_t *)(u + 7 * l);
+                            a.ab_key = u + 8 * l; a.kcode = u + 10 * l; a.red_or = u + 11 * l;
+                            a.oidx = v; a.rank = v + 6 * l; a.red_min = v + 7 * l; a.ab_idx = v + 8 * l;
+                            a.ab_aux = v + 10 * l; a.thr = v + 12 * l;
+                            return launch_selftest_wave(a, c->stream);
+                        });
+}
+
+int ksched_selftest_list(ksched_ctx *c, int64_t n, int32_t steps, const double *key, const int32_t *idx,
+                         double *out_key, int32_t *out_idx) {
+    if (!c || n < 0 || steps < 0 || steps > 4096 || (n > 0 && (!out_key || !out_idx)) ||
+        (n > 0 && steps > 0 && (!key || !idx)))
+        return KSCHED_E_INVALID;
+    if (n == 0) return KSCHED_OK;
+    const size_t q = (size_t)n;
+    return selftest_run(c, "selftest_list",
+                        {{key, nullptr, q * (size_t)steps * 8}, {idx, nullptr, q * (size_t)steps * 4},
+                         {nullptr, out_key, q * 30 * 8}, {nullptr, out_idx, q * 30 * 4}},
+                        [&](const std::vector<void *> &p) {
+                            return launch_selftest_list(n, steps, (const double *)p[0], (const int32_t *)p[1],
+                                                        (double *)p[2], (int32_t *)p[3], c->stream);
+                        });
+}
+
+int ksched_selftest_slots(ksched_ctx *c, int64_t n, int32_t steps, const uint32_t *x, uint32_t *out) {
+    if (!c || n < 0 || steps < 0 || steps > 4096 || (n > 0 && !out) || (n > 0 && steps > 0 && !x)) return KSCHED_E_INVALID;
+    if (n == 0) return KSCHED_OK;
+    const size_t q = (size_t)n;
+    return selftest_run(c, "selftest_slots", {{x, nullptr, q * (size_t)steps * 2 * 4 * 4}, {nullptr, out, q * 60 * 4}},
+                        [&](const std::vector<void *> &p) {
+                            return launch_selftest_slots(n, steps, (const uint32_t *)p[0], (uint32_t *)p[1], c->stream);
+                        });
 }
 
 // Ranked dry run (ksched_rank.hip).  Touches nothing a schedule call left behind: its pods, span lists and

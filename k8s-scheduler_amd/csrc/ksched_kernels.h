@@ -241,6 +241,38 @@ hipError_t launch_zero_sys(void *p, size_t bytes, hipStream_t s);
 // diagnostics: qdiv(a, b, recip(b)) against the native a / b, bit for bit
 hipError_t launch_selftest_div(int64_t n, const double *a, const double *b, double *native, double *fast,
                                hipStream_t s);
+// diagnostics: the score, screen, record and wave primitives on arrays of operands (ksched_selftest.hip; device
+// pointers, layouts at each kernel there)
+struct WaveTestArgs {
+    int64_t ncases;           // one 64-lane workgroup each; per-lane arrays hold ncases * 64 elements
+    const uint64_t *scode;    // [6][lanes] (code, idx) pairs in sorted runs of 1, 2, 4, 8, 16, 32
+    const int32_t *sidx;
+    const double *key;        // [lanes] the arg-bests' (key, idx, aux)
+    const int32_t *kidx, *aux;
+    const int32_t *cut, *nv;  // [ncases] list_thr_bits: the list is cut; its valid entries are lanes < nv
+    uint64_t *ocode;          // [6][lanes] wave_sort_desc<RUN>
+    int32_t *oidx;
+    int32_t *rank;            // [lanes] wave_rank of the lane's own pair (arrangement 0)
+    uint64_t *red_max;        // [lanes] wave_max_u64(code), wave_sum_i64(code), wave_min_i32(idx) (arrangement 0)
+    int64_t *red_sum;
+    int32_t *red_min;
+    uint64_t *red_or;         // [lanes] wave_or_u64(code) (arrangement 0)
+    uint64_t *ab_key;         // [2][lanes] wave_argbest, wave_argbest_fast
+    int32_t *ab_idx, *ab_aux;
+    uint64_t *kcode;          // [lanes] key_code(key)
+    int32_t *thr;             // [lanes] list_thr_bits
+};
+hipError_t launch_selftest_score(int64_t n, const int64_t *req, const int64_t *alloc, double *score, double *upper,
+                                 double *rcp, int32_t *flags, hipStream_t s);
+hipError_t launch_selftest_price(int64_t n, const float *price, double *key, hipStream_t s);
+hipError_t launch_selftest_screen(int64_t n, const int64_t *req, const int64_t *alloc, float *f, uint32_t *u,
+                                  hipStream_t s);
+hipError_t launch_selftest_rec_w(int64_t n, const float *w, const float *w2, uint32_t *out, hipStream_t s);
+hipError_t launch_selftest_threshold(int64_t n, const float *L, const uint32_t *rec, int32_t *out, hipStream_t s);
+hipError_t launch_selftest_wave(const WaveTestArgs &a, hipStream_t s);
+hipError_t launch_selftest_list(int64_t n, int S, const double *key, const int32_t *idx, double *okey, int32_t *oidx,
+                                hipStream_t s);
+hipError_t launch_selftest_slots(int64_t n, int steps, const uint32_t *x, uint32_t *out, hipStream_t s);
 
 // (priority, domain, labels, fast53) -> instantiation.  Best-price always ranges over feasible nodes
 // and never divides (fast53 irrelevant).

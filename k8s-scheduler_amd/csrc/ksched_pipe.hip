@@ -72,16 +72,6 @@ __device__ __forceinline__ int wave_incl_sum(int v) {
     }
     return v;
 }
-// OR over the wave's lanes (DPP butterfly; every lane ends with the result)
-template <int S>
-__device__ __forceinline__ uint64_t or_stage(uint64_t v) {
-    return v | (((uint64_t)wpartner<S>((uint32_t)(v >> 32)) << 32) | wpartner<S>((uint32_t)v));
-}
-__device__ __forceinline__ uint64_t wave_or_u64(uint64_t v) {
-    v = or_stage<0>(v); v = or_stage<1>(v); v = or_stage<2>(v);
-    v = or_stage<3>(v); v = or_stage<4>(v); v = or_stage<5>(v);
-    return v;
-}
 // ---- barrier of ONE role's waves (LDS counter; s_barrier would wait for the other role too) ----------
 __device__ __forceinline__ void role_sync(unsigned *ctr, unsigned &target, unsigned nwaves) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -202,67 +192,6 @@ __device__ __forceinline__ void set_row(NodeRec *nd, int64_t a0, int64_t a1, int
     nd->af[0] = f0; nd->af[1] = f1; nd->af[2] = f2;
     nd->y[0] = recip_or_zero(a0, f0); nd->y[1] = recip_or_zero(a1, f1); nd->y[2] = recip_or_zero(a2, f2);
     nd->ys[0] = screen_recip(a0); nd->ys[1] = screen_recip(a1); nd->ys[2] = screen_recip(a2);
-}
-
-// Pass 1's lower bounds of one step of kSPU rows into the wave's KC slots.  When kSPU is a multiple of KC,
-// row u of the step goes to slot u % KC, which keeps the MAXIMUM of its rows (one v_max per pair instead of
-// an insertion into a sorted list): the KC slots of a wave, and of the 12 waves, are lower bounds of keys of
-// DISTINCT rows, so the KC-th largest of them is at most the KC-th largest key of the workgroup -- a valid
-// L, at most slightly weaker than the KC-th largest of all the rows' bounds (tests/diag/screen_sim.py: c4 exact
-// rows +4 %).  Otherwise a sorted top-KC insertion.
-template <int KC, int SPU>
-__device__ __forceinline__ void bound_slots(uint32_t (&t)[KC], const uint32_t (&xs)[SPU]) {
-    if constexpr (SPU % KC == 0) {
-#pragma unroll
-        for (int u = 0; u < SPU; ++u) t[u % KC] = t[u % KC] > xs[u] ? t[u % KC] : xs[u];
-    } else {
-#pragma unroll
-        for (int u = 0; u < SPU; ++u) {
-            uint32_t xv = xs[u];
-#pragma unroll
-            for (int q = 0; q < KC; ++q) {
-                const uint32_t hi = t[q] > xv ? t[q] : xv;
-                xv = t[q] > xv ? xv : t[q];
-                t[q] = hi;
-            }
-        }
-    }
-}
-
-// descending order of KC values (once per batch, before the cross-wave merge)
-template <int KC>
-__device__ __forceinline__ void sort_desc_u32(uint32_t (&t)[KC]) {
-#pragma unroll
-    for (int i = 1; i < KC; ++i) {
-#pragma unroll
-        for (int j = i; j >= 1; --j) {
-            const uint32_t a = t[j - 1], c = t[j];
-            t[j - 1] = a > c ? a : c;
-            t[j] = a > c ? c : a;
-        }
-    }
-}
-
-// t (sorted descending) <- the KC largest of t and u (both sorted descending): the element-wise max of t
-// and reversed u holds them as a bitonic sequence, which half-cleaners sort
-template <int KC>
-__device__ __forceinline__ void topk_merge_u32(uint32_t (&t)[KC], const uint32_t (&u)[KC]) {
-    uint32_t v[KC];
-#pragma unroll
-    for (int q = 0; q < KC; ++q) v[q] = t[q] > u[KC - 1 - q] ? t[q] : u[KC - 1 - q];
-#pragma unroll
-    for (int d = KC / 2; d >= 1; d >>= 1) {
-#pragma unroll
-        for (int i = 0; i < KC; ++i) {
-            if ((i & d) == 0) {
-                const uint32_t a = v[i], b = v[i + d];
-                v[i] = a > b ? a : b;
-                v[i + d] = a > b ? b : a;
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < KC; ++q) t[q] = v[q];
 }
 
 // One butterfly stage of the fold: this lane's sorted (key desc, idx asc) list and its DPP partner's (stage S

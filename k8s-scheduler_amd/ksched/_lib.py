@@ -76,6 +76,7 @@ _lib = None
 I64P = C.POINTER(C.c_int64)
 U64P = C.POINTER(C.c_uint64)
 I32P = C.POINTER(C.c_int32)
+U32P = C.POINTER(C.c_uint32)
 F64P = C.POINTER(C.c_double)
 F32P = C.POINTER(C.c_float)
 U8P = C.POINTER(C.c_uint8)
@@ -134,6 +135,14 @@ SIGNATURES = [
     ("ksched_set_timing", C.c_int, [CTX, C.c_int32, C.c_int32]),
     ("ksched_set_timeout", C.c_int, [CTX, C.c_int32]),
     ("ksched_selftest_fastdiv", C.c_int, [CTX, C.c_int64, F64P, F64P, F64P, F64P]),
+    ("ksched_selftest_score", C.c_int, [CTX, C.c_int64, I64P, I64P, F64P, F64P, F64P, I32P]),
+    ("ksched_selftest_price_key", C.c_int, [CTX, C.c_int64, F32P, F64P]),
+    ("ksched_selftest_screen", C.c_int, [CTX, C.c_int64, I64P, I64P, F32P, U32P]),
+    ("ksched_selftest_rec_w", C.c_int, [CTX, C.c_int64, F32P, F32P, U32P]),
+    ("ksched_selftest_threshold", C.c_int, [CTX, C.c_int64, F32P, U32P, I32P]),
+    ("ksched_selftest_wave", C.c_int, [CTX, C.c_int64, U64P, I32P, F64P, I32P, I32P, I32P, I32P, U64P, I32P]),
+    ("ksched_selftest_list", C.c_int, [CTX, C.c_int64, C.c_int32, F64P, I32P, F64P, I32P]),
+    ("ksched_selftest_slots", C.c_int, [CTX, C.c_int64, C.c_int32, U32P, U32P]),
     ("ksched_parse_cpu", C.c_int, [C.c_char_p, I64P]),
     ("ksched_parse_memory", C.c_int, [C.c_char_p, I64P]),
     ("ksched_parse_pods", C.c_int, [C.c_char_p, I64P]),

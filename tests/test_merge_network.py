@@ -4,7 +4,8 @@ bit HB clear keeps the better pair -- sorts any 64 (code, idx) pairs best first 
 tail (the stages above block size RUN) merges lanes that hold sorted runs of RUN.  The device builds every partner
 from DPP / permlane moves; the identities it relies on (xor 4 = xor 7 then xor 3, xor 31 = 15 then 16, xor 63 =
 15, 16 then 32; the row mirrors are xor 7 and xor 15) are checked here too.  The device code itself is covered by
-every GPU parity test (the merged lists decide every batched result)."""
+every GPU parity test (the merged lists decide every batched result) and run alone, against a plain sort, by
+tests/test_gpu_primitives.py."""
 import random
 
 import pytest

@@ -5,34 +5,13 @@ node is scored exactly only when that upper bound can reach the decision thresho
   (1) upper >= exact score whenever the balanced branch is not flagged "near 1", and
   (2) outside the flag, the branch (fraction >= 1) taken with approximate fractions equals the exact one.
 This mirrors the device arithmetic in numpy (float64 ops, no FMA) with the reciprocals perturbed by up
-to +-4 ulp -- the device's rcp + two Newton steps is within 1 ulp -- and checks both properties against
+to +-4 ulp -- the device's rcp + two Newton steps is within 1 ulp (tests/test_gpu_primitives.py measures it on
+the device: correctly rounded on every integer-valued divisor it draws) -- and checks both properties against
 the oracle's exact score (oracle/cpu_ref.c:or_score, anchor/scores.go)."""
 import numpy as np
 import pytest
 
-
-def _wsub(a, b):
-    return (a.astype(np.uint64) - b.astype(np.uint64)).view(np.int64)  # Go int64 wrap-around
-
-
-def _upper(rc, rm, rp, ac, am, ap, yc, ym, yp, y3):
-    with np.errstate(all="ignore"):
-        rcf, rmf, rpf = (x.astype(np.float64) for x in (rc, rm, rp))
-        c = np.where(ac == 0, 1.0, rcf * yc)
-        m = np.where(am == 0, 1.0, rmf * ym)
-        p = np.where(ap == 0, 1.0, rpf * yp)
-        near1 = ((ac != 0) & (np.abs(c - 1.0) < 1e-12)) | ((am != 0) & (np.abs(m - 1.0) < 1e-12)) | \
-                ((ap != 0) & (np.abs(p - 1.0) < 1e-12))
-        mean = ((c + m) + p) * y3
-        var = (((c - mean) * (c - mean) + (m - mean) * (m - mean)) + (p - mean) * (p - mean)) * y3
-        b = np.where((c >= 1.0) | (m >= 1.0) | (p >= 1.0), 0.0, (1.0 - var) * 10.0)
-        dc, dm, dp = (_wsub(a, r).astype(np.float64) for a, r in ((ac, rc), (am, rm), (ap, rp)))
-        lc = np.where((ac == 0) | (rc > ac), 0.0, dc * 10.0 * yc)
-        lm = np.where((am == 0) | (rm > am), 0.0, dm * 10.0 * ym)
-        lp = np.where((ap == 0) | (rp > ap), 0.0, dp * 10.0 * yp)
-        l = ((lc + lm) + lp) * y3
-        s = (b + l) * 0.5
-        return s + 1e-9 * (np.abs(b) + np.abs(l) + 1.0), near1, (c >= 1) | (m >= 1) | (p >= 1)
+from screen_ref import _upper
 
 
 def _cases(rng, n):

@@ -6,51 +6,15 @@ bound (screen - kScreenEps) of KC eligible keys of the same workgroup.  That is 
 |screen - score| < kScreenEps wherever the screen serves as a lower bound (resource-fitting pairs whose
 fractions are all < 0.999, and non-fitting pairs), and screen + kScreenEps >= score everywhere.  numpy's
 float32 arithmetic is IEEE round-to-nearest like the device's (no contraction: the library builds with
--ffp-contract=off), so the emulation below is the device computation bit for bit.
+-ffp-contract=off), so the emulation (tests/screen_ref.py) is meant to be the device computation bit for bit;
+tests/test_gpu_primitives.py checks that against the device's own primitives.
 """
 import numpy as np
 import pytest
 
-EPS = np.float32(4e-5)      # kScreenEps
-BOUND = 1.3e-5              # the polynomial's error bound ksched_device.h derives
-BOUND_NF = 2e-6             # the non-fitting form's
-F = np.float32
-
-
-def screen_req(r):
-    r = np.asarray(r, dtype=np.int64)
-    out = r.astype(np.float32)
-    out[(r < 0) | (r >= (1 << 52))] = np.nan
-    return out
-
-
-def screen_recip(a):
-    a = np.asarray(a, dtype=np.int64)
-    with np.errstate(divide="ignore"):
-        out = (1.0 / a.astype(np.float64)).astype(np.float32)
-    out[(a <= 0) | (a >= (1 << 52))] = np.nan
-    return out
-
-
-def screen_pair(rc, rm, rp, ac, am, ap):
-    """(value, lo_ok) as screen_pair computes them; ok_k = a_k >= r_k exactly."""
-    rc, rm, rp, ac, am, ap = (np.asarray(x, np.int64) for x in (rc, rm, rp, ac, am, ap))
-    qc, qm, qp = screen_req(rc), screen_req(rm), screen_req(rp)
-    yc, ym, yp = screen_recip(ac), screen_recip(am), screen_recip(ap)
-    okc, okm, okp = ac >= rc, am >= rm, ap >= rp
-    with np.errstate(all="ignore"):
-        c, m, p = qc * yc, qm * ym, qp * yp
-        rf = okc & okm & okp
-        fmax = np.fmax(np.fmax(c, m), p)
-        S = (c + m) + p
-        Q = (c * c + m * m) + p * p
-        poly = ((F(10.0) - (F(5.0) / F(3.0)) * S) - (F(5.0) / F(3.0)) * Q) + (F(5.0) / F(9.0)) * (S * S)
-        one = F(1.0)
-        nf = (F(5.0) / F(3.0)) * ((np.where(okc, one - c, F(0)) + np.where(okm, one - m, F(0))) + np.where(okp, one - p, F(0)))
-        nf = nf + F(0.0) * S
-        v = np.where(rf, poly, nf).astype(np.float32)
-        lo_ok = np.where(rf, fmax < F(0.999), True) & (v > EPS)
-    return v, lo_ok
+from screen_ref import (BOUND, BOUND_NF, EPS, NF_BASE, F, exact_score, fma32, needed, rec_value, screen_fast,  # noqa: F401
+                        screen_pair, screen_rec, screen_rec_nf, screen_rec_threshold, screen_rec_threshold_nf,
+                        screen_recip, screen_req)
 
 
 def screen_score(rc, rm, rp, ac, am, ap):
@@ -60,24 +24,6 @@ def screen_score(rc, rm, rp, ac, am, ap):
     with np.errstate(all="ignore"):
         c, m, p = qc * screen_recip(ac), qm * screen_recip(am), qp * screen_recip(ap)
     return v, np.fmax(np.fmax(c, m), p)
-
-
-def exact_score(rc, rm, rp, ac, am, ap):
-    """anchor/priorities.go:5-23,45-50 + scores.go:3-25 in the reference's f64 operation order."""
-    rcf, rmf, rpf = (np.asarray(x, np.int64).astype(np.float64) for x in (rc, rm, rp))
-    acf, amf, apf = (np.asarray(x, np.int64).astype(np.float64) for x in (ac, am, ap))
-    with np.errstate(all="ignore"):
-        c = np.where(acf == 0, 1.0, rcf / acf)
-        m = np.where(amf == 0, 1.0, rmf / amf)
-        p = np.where(apf == 0, 1.0, rpf / apf)
-        mean = ((c + m) + p) / 3.0
-        var = (((c - mean) * (c - mean) + (m - mean) * (m - mean)) + (p - mean) * (p - mean)) / 3.0
-        b = np.where((c >= 1) | (m >= 1) | (p >= 1), 0.0, (1.0 - var) * 10.0)
-        lc = np.where((acf == 0) | (rcf > acf), 0.0, ((acf - rcf) * 10.0) / acf)
-        lm = np.where((amf == 0) | (rmf > amf), 0.0, ((amf - rmf) * 10.0) / amf)
-        lp = np.where((apf == 0) | (rpf > apf), 0.0, ((apf - rpf) * 10.0) / apf)
-        l = ((lc + lm) + lp) / 3.0
-        return ((0.0 + b) + l) / 2.0
 
 
 def _pairs(rng, n):
@@ -161,28 +107,6 @@ def test_unscreenable_values_are_nan():
 
 
 
-def screen_rec(v):
-    """ksched_device.h screen_rec: the f16 pattern of w = max(RN(10 - v), 0) rounded down (NaN -> 0)."""
-    v = np.asarray(v, np.float32)
-    with np.errstate(invalid="ignore"):
-        w = np.fmax(F(10.0) - v, F(0.0))
-    h = w.astype(np.float16)  # round to nearest even, like v_cvt_f16_f32
-    hb = h.view(np.uint16).astype(np.int64)
-    return hb - (h.astype(np.float32) > w)
-
-
-def rec_value(hb):
-    return np.asarray(hb, np.int64).astype(np.uint16).view(np.float16).astype(np.float64)
-
-
-def screen_rec_threshold(L):
-    """ksched_device.h screen_rec_threshold."""
-    L = np.asarray(L, np.float32)
-    T = 11.0 + np.float64(EPS) + 2.0 ** -20 - L.astype(np.float64)
-    h = T.astype(np.float32).astype(np.float16)
-    return np.where(T >= 0, h.view(np.uint16).astype(np.int64) + 1, -1)
-
-
 def test_screen_record_is_an_upper_bound():
     rng = np.random.default_rng(7)
     v = np.concatenate([rng.uniform(0, 10, 2_000_000), 10 - rng.uniform(0, 0.5, 500_000) ** 2]).astype(np.float32)
@@ -218,32 +142,6 @@ def test_pass2_integer_threshold_is_a_superset():
 
 
 # ---- the non-fitting records (ksched_device.h screen_rec_nf / screen_rec_threshold_nf) -------------------------
-NF_BASE = F(3.375)  # kNfBase
-
-
-def screen_rec_nf(v):
-    """0x8000 | the f16 pattern of w = max(RN(kNfBase - v), 0) rounded down."""
-    v = np.asarray(v, np.float32)
-    with np.errstate(invalid="ignore"):
-        w = np.fmax(NF_BASE - v, F(0.0))
-    h = w.astype(np.float16)
-    hb = h.view(np.uint16).astype(np.int64)
-    return 0x8000 | (hb - (h.astype(np.float32) > w))
-
-
-def screen_rec_threshold_nf(L):
-    L = np.asarray(L, np.float32)
-    T = np.float64(NF_BASE) + 1.0 + np.float64(EPS) + 2.0 ** -20 - L.astype(np.float64)
-    h = T.astype(np.float32).astype(np.float16)
-    return np.where(T >= 0, h.view(np.uint16).astype(np.int64) + 1, -1)
-
-
-def needed(hb, tq, tqn):
-    """ksched_device.h screen_rec_needed"""
-    hb = np.asarray(hb, np.int64)
-    return np.where(hb & 0x8000, (hb & 0x7FFF) <= tqn, hb <= tq)
-
-
 def test_non_fitting_values_below_the_record_base():
     """Every non-fitting screen value stays below kNfBase (at most two (1 - f) terms of (5/3))."""
     rng = np.random.default_rng(21)
@@ -296,30 +194,6 @@ def test_pass2_two_form_threshold_is_a_superset():
 
 
 # ---- pass 1's VALU form (ksched_device.h screen_fast) ------------------------------------------------------------
-def fma32(a, b, c):
-    """f32 fused multiply-add: a * b + c rounded once (the product is exact in long double, the sum to 64 bits)"""
-    L = np.longdouble
-    return (np.asarray(a, np.float32).astype(L) * np.asarray(b, np.float32).astype(L) + np.asarray(c, np.float32).astype(L)).astype(np.float32)
-
-
-def screen_fast(rc, rm, rp, ac, am, ap):
-    """(v, mx, amb, rf) as screen_fast computes them from pass 1's f32 fractions."""
-    rc, rm, rp, ac, am, ap = (np.asarray(x, np.int64) for x in (rc, rm, rp, ac, am, ap))
-    with np.errstate(all="ignore"):
-        c, m, p = screen_req(rc) * screen_recip(ac), screen_req(rm) * screen_recip(am), screen_req(rp) * screen_recip(ap)
-        S = (c + m) + p
-        mx = np.fmax(np.fmax(c, m), p)
-        d = np.fmin(np.fmin(np.abs(c - F(1)), np.abs(m - F(1))), np.abs(p - F(1)))
-        amb = ~(fma32(F(0), S, d) > F(2.0 ** -20))
-        rf = mx < F(1)
-        Q = fma32(c, c, fma32(m, m, p * p))
-        poly = fma32(F(5.0 / 9.0), S * S, fma32(F(-5.0 / 3.0), S + Q, F(10)))
-        sat = lambda x: np.clip(x, F(0), F(1))  # noqa: E731
-        nf = F(5.0 / 3.0) * ((sat(F(1) - c) + sat(F(1) - m)) + sat(F(1) - p))
-        v = np.where(rf, poly, nf).astype(np.float32)
-    return v, mx, amb, rf
-
-
 @pytest.mark.parametrize("seed", [41, 42, 43])
 def test_screen_fast_matches_the_bounds(seed):
     """screen_fast: the same ambiguity and fit classes as screen_q's compares, and the same error bounds: the
