@@ -528,6 +528,12 @@ int ksched_get_stats(const ksched_ctx *ctx, ksched_stats *out);
  * sufficed, [29] batches whose inherited keys were loaded before the merges' wait, [30] batches that tried (those with an
  * older export to inherit, voided ones included); the others are cycle sums (ksched_diag.hip prints them). */
 int ksched_get_commit_stamps(const ksched_ctx *ctx, int32_t n, int64_t *out);
+/* Diagnostics (added within ABI 6: probe with dlsym): the seeded score scan's counters of the last synced persistent
+ * run, summed over the score workgroups, into out[5]: [0] (workgroup, batch) scans whose bound was seeded from the
+ * previous batch's needed rows, [1] seed rows, [2] scans whose bound was 0 (everything passes) for some active pod,
+ * [3] scans seeded from all rows because the batch before ran unscreened (it left no masks), [4] ... because its
+ * needed rows passed the cap.  (A call's first scans and KSCHED_NO_SEED runs seed from all rows too.) */
+int ksched_get_seed_stats(const ksched_ctx *ctx, int64_t *out);
 /* Turns the sampled per-kernel HIP-event timing (opts.timing / opts.timing_every) on or off for the
  * following calls (every = 0: keep the current sampling period). */
 int ksched_set_timing(ksched_ctx *ctx, int32_t timing, int32_t every);
@@ -572,6 +578,10 @@ int ksched_selftest_screen(ksched_ctx *ctx, int64_t n, const int64_t *req, const
                            uint32_t *out_u32);
 int ksched_selftest_rec_w(ksched_ctx *ctx, int64_t n, const float *w, const float *w2, uint32_t *out);
 int ksched_selftest_threshold(ksched_ctx *ctx, int64_t n, const float *L, const uint32_t *rec, int32_t *out);
+/* seed (added within ABI 6): flags bit 0 amb, bit 1 el; x [6][n] lower bounds.  out [5][n]: screen_need(v, amb, el, L),
+ * then the sorted top-4 list after six bound_insert<4>. */
+int ksched_selftest_seed(ksched_ctx *ctx, int64_t n, const float *v, const float *L, const uint32_t *flags,
+                         const uint32_t *x, uint32_t *out);
 int ksched_selftest_wave(ksched_ctx *ctx, int64_t ncases, const uint64_t *sort_code, const int32_t *sort_idx,
                          const double *key, const int32_t *idx, const int32_t *aux, const int32_t *cut,
                          const int32_t *nv, uint64_t *out_u64, int32_t *out_i32);

@@ -133,6 +133,7 @@ struct ksched_bufs {
 //   KSCHED_DEBUG                 0        launch decisions to stderr
 //   KSCHED_NO_SCREEN             0        the exact scan everywhere (A/B of the screened scan)
 //   KSCHED_NO_PAIRS              0        the screened scan's exact phase by rows (A/B of the pair lists)
+//   KSCHED_NO_SEED               0        the seeded scan's bound from all rows in every batch (A/B of the seed masks)
 //   KSCHED_NO_TOUCH_SCREEN       0        the commit keys every touched node exactly
 //   KSCHED_NO_EARLY_INH          0        the commit loads the mergers' inherited keys only after its merges' wait
 //   KSCHED_POISON                0        workspace and LDS filled with 0xff before every persistent run
@@ -157,6 +158,7 @@ struct ksched_diag {
     bool debug = false;           // KSCHED_DEBUG
     bool no_screen = false;       // KSCHED_NO_SCREEN
     bool no_pairs = false;        // KSCHED_NO_PAIRS
+    bool no_seed = false;         // KSCHED_NO_SEED
     bool touch_screen = true;     // off with KSCHED_NO_TOUCH_SCREEN
     bool early_inh = true;        // off with KSCHED_NO_EARLY_INH
     bool poison = false;          // KSCHED_POISON
@@ -231,6 +233,8 @@ struct ksched_ctx {
     bool persist_stats = false;  // stats come from the Ctl copy queued behind the run
     int64_t commit_dbg[32] = {};  // KSCHED_COMMIT_STAMPS: the last persistent run's words (ksched_get_commit_stamps)
     int64_t persist_B = 0;
+    bool seed_counted = false;    // the last persistent launch ran a kernel that writes the seeded scan's counters
+    int64_t seed_stats[5] = {};   // the last persistent run's seeded-scan counters (ksched_get_seed_stats)
     // device-side candidate exchange of the node-sharded persistent pipeline (ksched_xchg_*)
     void *d_rx = nullptr;          // this rank's receive ring (rx_prepare)
     size_t rx_bytes = 0;

@@ -427,6 +427,20 @@ int ksched_selftest_threshold(ksched_ctx *c, int64_t n, const float *L, const ui
                         });
 }
 
+int ksched_selftest_seed(ksched_ctx *c, int64_t n, const float *v, const float *L, const uint32_t *flags,
+                         const uint32_t *x, uint32_t *out) {
+    if (!c || n < 0 || (n > 0 && (!v || !L || !flags || !x || !out))) return KSCHED_E_INVALID;
+    if (n == 0) return KSCHED_OK;
+    const size_t q = (size_t)n;
+    return selftest_run(c, "selftest_seed",
+                        {{v, nullptr, q * 4}, {L, nullptr, q * 4}, {flags, nullptr, q * 4}, {x, nullptr, q * 24},
+                         {nullptr, out, q * 20}},
+                        [&](const std::vector<void *> &p) {
+                            return launch_selftest_seed(n, (const float *)p[0], (const float *)p[1], (const uint32_t *)p[2],
+                                                        (const uint32_t *)p[3], (uint32_t *)p[4], c->stream);
+                        });
+}
+
 int ksched_selftest_wave(ksched_ctx *c, int64_t ncases, const uint64_t *sort_code, const int32_t *sort_idx,
                          const double *key, const int32_t *idx, const int32_t *aux, const int32_t *cut,
                          const int32_t *nv, uint64_t *out_u64, int32_t *out_i32) {

@@ -340,6 +340,14 @@ __device__ __forceinline__ ScreenV screen_fast(float c, float m, float p) {
     return o;
 }
 
+// The seeded scan's test of one pair against its pod's bound L (shifted by +1; 0 = fewer than KC bounds: everything
+// passes): the pair is needed unless its screen proves it below L -- v + eps bounds its key from above, L - 1 is a
+// lower bound (already less eps) of KC eligible keys of the workgroup.  An ambiguous pair (a fraction within 2^-20 of
+// 1, or NaN: v may be anything and el is not known) is always needed.  tests/seed_ref.py states it bit for bit.
+__device__ __forceinline__ bool screen_need(float v, bool amb, bool el, float L) {
+    return amb || (el && !(v + (1.0f + kScreenEps) < L));
+}
+
 // The screened scan's per-pair record (pass 1 -> pass 2): a 16-bit upper bound of a screen value v (NaN allowed),
 // in two forms by the pair's screen form (screen_q's rf):
 //   resource-fitting (polynomial, v <= 10): the f16 bit pattern h of w = RN(10 - v) rounded DOWN (round toward

@@ -27,6 +27,7 @@ void read_env(ksched_diag *d) {
     d->debug = env_int("KSCHED_DEBUG", 0) != 0;
     d->no_screen = env_int("KSCHED_NO_SCREEN", 0) != 0;
     d->no_pairs = env_int("KSCHED_NO_PAIRS", 0) != 0;
+    d->no_seed = env_int("KSCHED_NO_SEED", 0) != 0;
     d->touch_screen = env_int("KSCHED_NO_TOUCH_SCREEN", 0) == 0;
     d->early_inh = env_int("KSCHED_NO_EARLY_INH", 0) == 0;
     d->poison = env_int("KSCHED_POISON", 0) != 0;
@@ -64,7 +65,9 @@ void print_persist_trace(ksched_ctx *c) {
     if (!c->diag.trace_dump.empty()) write_u64(c->diag.trace_dump, nullptr, 0, t);
     auto at = [&](int64_t b, int col) { return t[(size_t)b * kTraceCols + col]; };
     double sum[16] = {};
-    double scr[5] = {};  // WG 0 wave 0, screened batches: pass 1, bound merge, pass 2, exact phase (sums), exact rows
+    // WG 0 wave 0, screened batches: pass 1 (seeded scan: the seed pass), bound merge, pass 2 (seeded scan: the single
+    // pass), exact phase (sums), exact rows, and the wait for the other waves' pass 1 (stamp 37, behind the barrier)
+    double scr[6] = {};
     int64_t nscr = 0, npair = 0;
     double pairs_sum = 0;  // WG 0: batches whose exact phase ran over the pair lists, and their pairs
     int64_t cnt = 0, first = -1, last = -1;
@@ -93,7 +96,9 @@ void print_persist_trace(ksched_ctx *c) {
         if (at(b, 11) && at(b, 12)) {  // a screened batch (ksched_pipe.hip score_role)
             ++nscr;
             scr[0] += (double)(int64_t)(at(b, 11) - at(b, 0));
-            scr[1] += (double)(int64_t)(at(b, 12) - at(b, 11));
+            const uint64_t bar = at(b, 37) ? at(b, 37) : at(b, 11);
+            scr[5] += (double)(int64_t)(bar - at(b, 11));
+            scr[1] += (double)(int64_t)(at(b, 12) - bar);
             scr[2] += (double)(int64_t)(at(b, 14) - at(b, 12));
             scr[3] += (double)(int64_t)(at(b, 8) - at(b, 14));
             scr[4] += (double)(uint32_t)at(b, 13);
@@ -139,10 +144,10 @@ void print_persist_trace(ksched_ctx *c) {
             sum[0] * us, sum[1] * us, sum[2] * us, sum[3] * us, sum[4] * us, sum[5] * us, sum[14] * us, sum[15] * us, sum[6] * us, sum[7] * us,
             sum[8] * us, sum[10] * us, sum[11] * us, sum[12] * us, sum[13] * us, sum[9] * us);
     if (nscr)
-        fprintf(stderr, "persist screen (WG 0 wave 0): %lld of %lld batches screened | pass 1 %.2f us, bound %.2f us, "
-                "pass 2 %.2f us, exact phase %.2f us (%.2f of the workgroup's %d rows needed; pair lists in %lld batches, "
+        fprintf(stderr, "persist screen (WG 0 wave 0): %lld of %lld batches screened | pass 1 / seed pass %.2f us, other waves "
+                "%.2f us, bound %.2f us, pass 2 / single pass %.2f us, exact phase %.2f us (%.2f of the workgroup's %d rows needed; pair lists in %lld batches, "
                 "%.1f pairs each)\n", (long long)nscr, (long long)cnt,
-                0.01 * scr[0] / nscr, 0.01 * scr[1] / nscr, 0.01 * scr[2] / nscr, 0.01 * scr[3] / nscr, scr[4] / nscr,
+                0.01 * scr[0] / nscr, 0.01 * scr[5] / nscr, 0.01 * scr[1] / nscr, 0.01 * scr[2] / nscr, 0.01 * scr[3] / nscr, scr[4] / nscr,
                 c->prog_rows, (long long)npair, npair ? pairs_sum / (double)npair : 0.0);
 }
 

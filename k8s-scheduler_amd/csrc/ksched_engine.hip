@@ -313,7 +313,7 @@ int enqueue_persistent(ksched_ctx *c) {
     const size_t part_b = align_up((size_t)kPipeLag * B * G * KC * sizeof(Cand), 256);
     const size_t lists_b = align_up((size_t)B * K * sizeof(Rec) + (size_t)B * sizeof(int64_t), 256);
     const size_t xb = align_up(xbuf_bytes_pipe(B), 256);
-    const size_t prog_b = align_up((size_t)(G + B + kCommitWGs) * kProgWords * 8, 256);
+    const size_t prog_b = align_up((prog_seed_off(G, B, kCommitWGs) + (size_t)G * kSeedWords) * 8, 256);
     const size_t resc_b = align_up(rescue_bytes(B), 256);
     const size_t inh_b = align_up(inh_bytes(B), 256);
     const size_t need = part_b + 4 * lists_b + 5 * xb + prog_b + resc_b + inh_b;
@@ -353,6 +353,7 @@ int enqueue_persistent(ksched_ctx *c) {
     a.timeout_ticks = c->diag.persist_timeout_ms * 100000;
     a.no_screen = c->diag.no_screen ? 1 : 0;
     a.no_pairs = c->diag.no_pairs ? 1 : 0;
+    a.no_seed = c->diag.no_seed ? 1 : 0;
     if (c->diag.trace) {
         const int64_t cap = 4 * (c->p / B) + 64;
         HIPCHK(c, c->d->trace.reserve((size_t)cap * kTraceCols * 8));
@@ -400,7 +401,9 @@ int enqueue_persistent(ksched_ctx *c) {
     HIPCHK(c, launch_ctl_init(a.ctl, B, c->p, kPipeLag, sS));
     // the export ring whole: its records carry batch tags (store_xrec), which an earlier call's must never match
     HIPCHK(c, hipMemsetAsync(a.xring, 0, 5 * xb, sS));
-    HIPCHK(c, hipMemsetAsync(a.prog, 0, (size_t)(G + B + kCommitWGs) * kProgWords * 8, sS));
+    // (the seeded scan's counters behind them: only the screened KC <= 4 kernels write and the sync then reads them)
+    c->seed_counted = c->o.priority == KSCHED_PRIORITY_RESOURCE && f53 && KC <= 4;
+    HIPCHK(c, hipMemsetAsync(a.prog, 0, (prog_seed_off(G, B, kCommitWGs) + (c->seed_counted ? (size_t)G * kSeedWords : 0)) * 8, sS));
     // score -> merge records carry 16-bit batch tags (1 + batch): no record of an earlier call may look current
     HIPCHK(c, hipMemsetAsync(a.part, 0, part_b, sS));
     // timing: the kernel (family 0) is bracketed by events on its stream -- one launch per call, so the
@@ -739,9 +742,23 @@ static int sync_impl(ksched_ctx *c) {
         if (c->d_prog) {  // the score workgroups' exact / scanned row counts (progress words 4, 5)
             std::vector<uint64_t> w((size_t)kProgWords * c->prog_G);
             HIPCHK(c, hipMemcpy(w.data(), c->d_prog, w.size() * 8, hipMemcpyDeviceToHost));
+            for (int i = 0; i < 5; ++i) c->seed_stats[i] = 0;
             for (int g = 0; g < c->prog_G; ++g) {
                 c->st.exact_rows += (int64_t)w[(size_t)kProgWords * g + 4];
                 c->st.scan_rows += (int64_t)w[(size_t)kProgWords * g + 5];
+            }
+            if (c->seed_counted) {  // ... and the seeded scan's counters behind the progress words
+                std::vector<uint64_t> sw((size_t)kSeedWords * c->prog_G);
+                HIPCHK(c, hipMemcpy(sw.data(), c->d_prog + prog_seed_off(c->prog_G, c->prog_B, kCommitWGs), sw.size() * 8,
+                                    hipMemcpyDeviceToHost));
+                for (int g = 0; g < c->prog_G; ++g) {
+                    const uint64_t sc = sw[(size_t)kSeedWords * g], sr = sw[(size_t)kSeedWords * g + 1];
+                    c->seed_stats[0] += (int64_t)(sc & 0x1fffff);
+                    c->seed_stats[1] += (int64_t)(sr & 0xffffffffffull);
+                    c->seed_stats[2] += (int64_t)(sr >> 40);
+                    c->seed_stats[3] += (int64_t)((sc >> 21) & 0x1fffff);
+                    c->seed_stats[4] += (int64_t)(sc >> 42);
+                }
             }
         }
     }
@@ -769,6 +786,12 @@ int ksched_get_stats(const ksched_ctx *c, ksched_stats *out) {
 int ksched_get_commit_stamps(const ksched_ctx *c, int32_t n, int64_t *out) {
     if (!c || !out || n < 0 || n > 32) return KSCHED_E_INVALID;
     for (int i = 0; i < n; ++i) out[i] = c->commit_dbg[i];
+    return KSCHED_OK;
+}
+
+int ksched_get_seed_stats(const ksched_ctx *c, int64_t *out) {
+    if (!c || !out) return KSCHED_E_INVALID;
+    for (int i = 0; i < 5; ++i) out[i] = c->seed_stats[i];
     return KSCHED_OK;
 }
 

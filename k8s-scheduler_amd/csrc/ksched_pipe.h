@@ -132,7 +132,8 @@ struct PersistArgs {
     int32_t no_screen;      // diagnostics (KSCHED_NO_SCREEN): the exact scan in every batch
     int32_t no_pairs;       // diagnostics (KSCHED_NO_PAIRS): the screened scan's exact phase by rows, never by pairs
     int32_t screen_ok;      // the screened scan's reciprocals fit in a score workgroup's LDS
-    int32_t screen_h;       // ... and so do pass 1's per-pair records
+    int32_t screen_h;       // ... and so do pass 1's per-pair records (KC = 8 kernels); KC <= 4 kernels: a wave's rows fit
+                            // one 64-bit mask (the seeded scan, which keeps no records)
     // optional (KSCHED_PERSIST_TRACE): wall-clock stamps per batch, [trace_cap][kTraceCols]
     uint64_t *trace;
     int64_t trace_cap;
@@ -175,10 +176,17 @@ struct PersistArgs {
     char *inh;
     int32_t early_inh;      // the commit loads those keys before its merges' wait when Ctl::inh_done shows them
                             // (KSCHED_NO_EARLY_INH=1: always after the wait)
+    int32_t no_seed;        // diagnostics (KSCHED_NO_SEED): the seeded scan's bound from all rows in every batch
 };
 constexpr size_t inh_bytes(int B) { return (size_t)4 * B * 32 + (size_t)4 * B * 64 * 8; }
 // progress phases (PersistArgs::prog); kProgWords 8-byte words per workgroup
 constexpr int kProgWords = 6;  // 0 phase, 1 where/seen, 2 heartbeat, 3 busy, 4 rows scored exactly, 5 rows scanned
+// Behind the progress words of every workgroup: the seeded scan's counters, two words per score workgroup, written by
+// the screened KC <= 4 kernels only (the layout the other kernels and the host's per-call path see is unchanged) --
+// 0: scans seeded from a mask | seeded from all rows after an unscreened batch << 21 | ... because the mask passed
+// the cap << 42; 1: seed rows | scans whose bound was 0 ("everything passes") for some active pod << 40
+constexpr int kSeedWords = 2;
+__host__ __device__ inline size_t prog_seed_off(int G, int B, int commit_wgs) { return (size_t)(G + B + commit_wgs) * kProgWords; }
 enum : int { kProgWaitCommit = 1, kProgScan = 2, kProgArrived = 3, kProgWaitArrive = 4, kProgMerged = 5,
              kProgWaitMerged = 6, kProgCommitted = 7, kProgIdle = 8, kProgRescue = 9, kProgWaitRescue = 10,
              kProgTimedOut = 0x80 };
@@ -275,7 +283,8 @@ hipError_t launch_xchg_min(const PersistArgs &a, int32_t mine, int32_t *out, hip
 // 27 P1 done, 30 the lists hashed; 26-30 the check step's split (update, probe, commit,
 // rescan, state load), 31-32 the guess step's (set-up, fixpoint), 33-36 the wave-0 state's (26-36: builds with
 // KSCHED_COMMIT_SPLIT only)
-constexpr int kTraceCols = 54;  // + 37-48: score WG 0's waves' pass-1 ends; 49-53: the commit's rounds
+constexpr int kTraceCols = 54;  // + 37: score WG 0 behind the bound's barrier (every wave's pass 1 / seed pass done);
+                                // 49-53: the commit's rounds
 // KSCHED_JITTER (race hunting): at one in four (workgroup, batch, site) triples, sleep the wave for up to ~50 us,
 // chosen by a hash of the seed -- a protocol that depends on timing then fails often instead of rarely
 __device__ __forceinline__ void jitter_at(uint32_t seed, int64_t b, int site) {
@@ -363,6 +372,17 @@ __device__ __forceinline__ void bound_slots(uint32_t (&t)[KC], const uint32_t (&
                 t[q] = hi;
             }
         }
+    }
+}
+
+// One lower bound into a sorted (descending) top-KC list
+template <int KC>
+__device__ __forceinline__ void bound_insert(uint32_t (&t)[KC], uint32_t xv) {
+#pragma unroll
+    for (int q = 0; q < KC; ++q) {
+        const uint32_t hi = t[q] > xv ? t[q] : xv;
+        xv = t[q] > xv ? xv : t[q];
+        t[q] = hi;
     }
 }
 

@@ -360,6 +360,21 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
     int64_t scr_off_until = 0;  // wave 0: batches before this one scan unscreened
     int64_t ex_rows = 0, scan_rows = 0;  // tid 0: rows scored exactly / rows scanned (progress words 4, 5)
     const int64_t Rvalid = (n - g + G - 1) / G;  // rows of this workgroup that hold a node
+    // The seeded scan (kMasks kernels): this wave's seed rows of the next screened batch, one bit per row k of the wave
+    // (r = wave + k kSW) -- the rows some pod of the last batch needed, or all of the wave's rows (seed_all) at the
+    // start of every call, after an unscreened batch, past the cap, and with KSCHED_NO_SEED.  Every
+    // condition is workgroup-uniform.  Kept in registers: the value is the same on every lane of the wave
+    const int nr_w = Rvalid > wave ? (int)((Rvalid - wave + kSW - 1) / kSW) : 0;
+    const uint64_t seed_all = nr_w >= 64 ? ~0ull : (1ull << nr_w) - 1ull;
+    uint64_t seed_m = seed_all;
+    int64_t seed_tot = Rvalid;   // the workgroup's seed rows behind seed_m
+    int seed_why = 1;            // 0: seed_m is a mask of needed rows; all rows: 1 the call's first scan, 2 after a batch
+                                 // without masks (unscreened), 3 the mask passed the cap, 4 KSCHED_NO_SEED
+    // a mask past a quarter of the rows costs the seed pass more than it saves, and says the last bound was weak
+    constexpr int kSeedCapDiv = 4;
+    // tid 0, the seed words behind the progress words (prog_seed_off): scans seeded from a mask | after an unscreened batch << 21 | past the cap << 42; seed
+    // rows | scans with an L of 0 for some active pod << 40
+    uint64_t sd_scans = 0, sd_rows = 0;
     int64_t nact = 0;
     int idle = 0;
     unsigned long long early_c = 0;  // wave 0 lane 0: Ctl::committed as read before the last fold
@@ -480,6 +495,8 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
         if (tid < 64) s_cnt[tid] = 0;
         if (kPairs && tid < 64) { pr.cnt[tid] = 0; pr.nel[tid] = 0; }
         bool pairs = false;          // this batch's exact phase runs over the pair lists
+        uint64_t seed_next = 0;      // the seeded scan: this wave's needed rows of this batch ...
+        bool seed_ok = false;        // ... when it took the single pass
         int pT = 0, pincl = 0, pexcl = 0;  // ... pairs in all, and lane (pod) p's range [pexcl, pincl)
         // the pair this thread scored, kept for the rank: its pod, the pod's range of pairs, its row and key
         int hp = 0, hex = 0, hin = 0, hr = 0;
@@ -503,7 +520,9 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
             const float qc = screen_req(rc), qm = screen_req(rm), qp = screen_req(rp);
             const int Rv = (int)((n - g + G - 1) / G);  // rows of this workgroup that hold a node
             const int QW = (R + kSW - 1) / kSW;
-            const bool keep_h = P.screen_h != 0;      // pass 1 leaves a record per pair for pass 2
+            // KC = 8 kernels: pass 1 leaves a record per pair for pass 2.  KC <= 4 kernels (masks): the seeded scan -- the
+            // bound first, from the rows the previous batch needed, then ONE pass over all rows against it
+            const bool keep_h = P.screen_h != 0;
             const bool masks = keep_h && kMasks;
             // the records of a wave's rows k (r = wave + k kSW): rows 2i and 2i + 1 share a 32-bit word per lane
             uint32_t *hw = reinterpret_cast<uint32_t *>(hrec) + (size_t)wave * (ScoreLayout<KC, K>::hrec_qw(R) / 2) * 64 + lane;
@@ -534,7 +553,45 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
             uint16_t *qrow = reinterpret_cast<uint16_t *>(qcnt + kSW);         // [kSW][QW] rows for the exact phase
             uint16_t *arow = qrow + kSW * QW;                                  // [kSW][QW] rows with an ambiguous fraction
             int na = 0;
-            if (keep_h) {
+            if (masks) {
+                if constexpr (kMasks) {
+                // ---- seed pass: the lower bounds of this wave's seed rows only (seed_m: the rows some pod of the
+                // previous batch needed, or every row), at their current state and for this batch's pods, into the
+                // wave's sorted top-KC list.  No record, no predicate count: any set of distinct rows gives a valid L ----
+                if (tid == 0) {
+                    sd_scans += seed_why == 0 ? 1ull : seed_why == 2 ? 1ull << 21 : seed_why == 3 ? 1ull << 42 : 0ull;
+                    sd_rows += (uint64_t)seed_tot;
+                }
+                for (uint64_t mm = seed_m; mm;) {  // wave-uniform
+                    int kk[kSPU];
+                    bool has[kSPU];
+#pragma unroll
+                    for (int u = 0; u < kSPU; ++u) {
+                        has[u] = mm != 0;
+                        kk[u] = (u == 0 || has[u]) ? __builtin_ctzll(mm) : kk[0];  // (a step's first bit is always there)
+                        mm &= mm - 1ull;
+                    }
+                    float4 yv[kSPU];
+                    uint64_t lb[kSPU];
+#pragma unroll
+                    for (int u = 0; u < kSPU; ++u) {
+                        const int r = wave + kk[u] * kSW;
+                        yv[u] = ysq[r];
+                        lb[u] = LAB ? rows[r].labels : 0ull;
+                    }
+#pragma unroll
+                    for (int u = 0; u < kSPU; ++u) {
+                        const ScreenV sv = screen_fast(qc * yv[u].x, qm * yv[u].y, qp * yv[u].z);
+                        const bool f = sv.rf && (!LAB || (lb[u] & sel) == sel);
+                        const bool el = DOM == kDomAll || f;
+                        const bool lo_ok = !(sv.rf && sv.mx >= 0.999f) && sv.v > kScreenEps;
+                        bound_insert<KC>(t, (has[u] && active && el && lo_ok && !sv.amb)
+                                                ? __float_as_uint(sv.v + (1.0f - kScreenEps)) : 0u);
+                    }
+                }
+                }
+            } else if (keep_h) {
+                if constexpr (!kMasks) {
                 // branch-free: a pair whose fraction is ambiguous (within 2^-20 of 1, or NaN) contributes no
                 // bound, gets a NaN record (scored exactly if it can matter) and its predicate is counted
                 // exactly after the loop, from its row's int64 values
@@ -604,6 +661,7 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                                      !(p < kFracLo || p > kFracHi);
                     cnt += (amb && fits(rc, rm, rp, sel, nd.a[0], nd.a[1], nd.a[2], nd.labels, LAB)) ? 1 : 0;
                 }
+                }
             } else {
                 for (int r0 = wave; r0 < Rv; r0 += kSW * kSPU) {
                     float4 yv[kSPU];
@@ -628,10 +686,11 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
             if (g == 0 && tid == 0) trace_at(P, b, 11);
             // ---- the workgroup's bound: the KC-th largest lower bound over every wave's list (the fold
             // area is free until the scan ends) ----
-            sort_desc_u32<KC>(t);
+            if (!masks) sort_desc_u32<KC>(t);  // (the seed pass inserts in order)
 #pragma unroll
             for (int q = 0; q < KC; ++q) sl[(wave * KC + q) * 64 + lane] = t[q];
             sync();
+            if (kMasks && masks && g == 0 && tid == 0) trace_at(P, b, 37);  // every wave's seed pass is done
             for (int w = 1; w < kSW; ++w) {
                 const int ow = (wave + w) % kSW;
                 uint32_t u[KC];
@@ -641,6 +700,10 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
             }
             const float L = __uint_as_float(t[KC - 1]);  // + 1; 0 = fewer than KC bounds: everything passes
             if (g == 0 && tid == 0) trace_at(P, b, 12);
+            if (kMasks && masks && wave == 0) {
+                const bool l0 = __ballot(active && t[KC - 1] == 0u) != 0;
+                if (lane == 0) sd_rows += l0 ? 1ull << 40 : 0ull;
+            }
             // the predicate counts (s_cnt was zeroed before pass 1, and that write is ordered by the barrier above)
             if (cnt) atomicAdd(&s_cnt[lane], cnt);
             // ---- pass 2: a row needs its exact scores when some pod's upper bound reaches L (a pair below
@@ -657,27 +720,56 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
             };
             if (keep_h) {
                 const int nr = (Rv - wave + kSW - 1) / kSW;  // this wave's rows
-                // in the records' own units: the pair is needed when its bound + 1 + eps reaches L; -1: an
-                // inactive lane
-                const int tq = active ? screen_rec_threshold(L) : -1;
-                const int tqn = active ? screen_rec_threshold_nf(L) : -1;
                 if constexpr (kMasks) {
-                // the rows of this wave that this lane's pod needs, one bit per row (nr <= 64: pipe_one) -- no
-                // ballot and no queue here: the pair path never reads the row queue
+                // ---- the single pass: every row -- the predicate count, the ambiguous-row queue, and the rows of
+                // this wave that this lane's pod needs, one bit per row (nr <= 64: pipe_one): the f32 screen
+                // against L directly (screen_need).  No ballot and no queue: the pair path never reads the row queue
                 uint64_t mine = 0;
-                for (int i0 = 0; i0 < nr; i0 += 16) {
-                    uint32_t x[8];
+                int k0 = 0;
+                for (int r0 = wave; r0 < Rv; r0 += kSW * kSPU, k0 += kSPU) {
+                    float4 yv[kSPU];
+                    uint64_t lb[kSPU];
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) x[u] = hw[(size_t)((i0 + 2 * u < nr ? i0 + 2 * u : i0) / 2) * 64];
-                    uint32_t m16 = 0;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        m16 |= (screen_rec_needed(x[u] & 0xffffu, tq, tqn) ? 1u : 0u) << (2 * u);
-                        m16 |= (screen_rec_needed(x[u] >> 16, tq, tqn) ? 1u : 0u) << (2 * u + 1);
+                    for (int u = 0; u < kSPU; ++u) {
+                        const int r = r0 + u * kSW;
+                        yv[u] = ysq[r < Rv ? r : r0];
+                        lb[u] = LAB ? rows[r < Rv ? r : r0].labels : 0ull;
                     }
-                    mine |= (uint64_t)m16 << i0;
+                    uint32_t m4 = 0;    // rows of this group this lane's pod needs
+                    uint32_t ambm = 0;  // ... and the ones with an ambiguous fraction for it
+#pragma unroll
+                    for (int u = 0; u < kSPU; ++u) {
+                        const bool valid = r0 + u * kSW < Rv;
+                        const ScreenV sv = screen_fast(qc * yv[u].x, qm * yv[u].y, qp * yv[u].z);
+                        const bool f = sv.rf && (!LAB || (lb[u] & sel) == sel);
+                        const bool el = DOM == kDomAll || f;
+                        cnt += (valid && f && !sv.amb) ? 1 : 0;
+                        m4 |= (screen_need(sv.v, sv.amb, el, L) ? 1u : 0u) << u;
+                        ambm |= (valid && sv.amb) ? 1u << u : 0u;
+                    }
+                    if (__ballot(ambm != 0)) {  // wave-uniform, rare: queue the rows with an ambiguous pair
+#pragma unroll
+                        for (int u = 0; u < kSPU; ++u) {
+                            const bool anya = __ballot((ambm >> u) & 1u) != 0;
+                            if (lane == 0 && na < QW) arow[wave * QW + na] = (uint16_t)(r0 + u * kSW);  // kept when anya
+                            na += anya ? 1 : 0;
+                        }
+                    }
+                    mine |= (uint64_t)m4 << k0;
                 }
+                // the ambiguous pairs' predicate, exactly (from their rows' int64 values)
+                for (int e = 0; e < na; ++e) {
+                    const int r = arow[wave * QW + e];
+                    const NodeRec &nd = rows[r];
+                    const float4 y = ysq[r];
+                    const float c = qc * y.x, m = qm * y.y, p = qp * y.z;
+                    const bool amb = !(c < kFracLo || c > kFracHi) || !(m < kFracLo || m > kFracHi) ||
+                                     !(p < kFracLo || p > kFracHi);
+                    cnt += (amb && fits(rc, rm, rp, sel, nd.a[0], nd.a[1], nd.a[2], nd.labels, LAB)) ? 1 : 0;
+                }
+                if (cnt) atomicAdd(&s_cnt[lane], cnt);
                 if (nr < 64) mine &= (1ull << nr) - 1ull;  // rows past the wave's last
+                if (!active) mine = 0;
                 // one slot reservation per lane for all of the wave's rows its pod needs
                 const int c = __builtin_popcountll(mine);
                 uint32_t s = c ? atomicAdd(&pr.cnt[lane], (uint32_t)c) : 0u;
@@ -687,7 +779,16 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
                 // the wave's rows some pod needs: the count of distinct needed rows, and the row path's queue
                 const uint64_t wm = wave_or_u64(mine);
                 if (lane == 0) pr.wmask[wave] = wm;
+                // ... and the next batch's seed rows (scalar: the seed loop is wave-uniform)
+                // (readfirstlane returns an int: each half goes through uint32_t, or bit 31 would fill the high half)
+                seed_next = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(wm >> 32)) << 32 |
+                            (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wm);
+                seed_ok = true;
                 } else {  // one ballot per row: the wave queues its needed rows as it goes
+                // in the records' own units: the pair is needed when its bound + 1 + eps reaches L; -1: an
+                // inactive lane
+                const int tq = active ? screen_rec_threshold(L) : -1;
+                const int tqn = active ? screen_rec_threshold_nf(L) : -1;
                 for (int i0 = 0; i0 < nr; i0 += 8) {
                     uint16_t hv[8];
 #pragma unroll
@@ -868,6 +969,14 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
             pre_c = __hip_atomic_load(&ctl->committed_x[g % kCtlReplicas].v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         sync();  // every wave's scan is done (the fold area is free); s_cnt was zeroed
         if (g == 0 && tid == 0) trace_at(P, b, 9);
+        if constexpr (kMasks && kScreen) {  // (the unscreened kernels carry none of the seed state)
+            // the next screened batch's seeds (workgroup-uniform: s_ex is the workgroup's count of needed rows)
+            const int64_t ex_tot = pc->s_ex;
+            // (a row-path batch leaves its masks too: only a mask past the cap -- every row, when a pod tied on all -- is dropped)
+            seed_why = P.no_seed ? 4 : !seed_ok ? 2 : kSeedCapDiv * ex_tot > Rvalid ? 3 : 0;
+            seed_m = seed_why == 0 ? (seed_next & seed_all) : seed_all;  // (never a row past the wave's last)
+            seed_tot = seed_why == 0 ? ex_tot : Rvalid;
+        }
         // ---- the next batch's loads and export apply by wave kSW - 1, while the others fold (or rank the pairs): a
         // workgroup still busy with this batch when commit(b + 1 - kPipeLag) is published starts the next scan right
         // after its arrival.  Only when that commit is already out: this wave never waits for it ----
@@ -1028,7 +1137,13 @@ __device__ __forceinline__ void score_role(const PersistArgs &P, char *smem, con
         }
         // the next batch's first barrier orders s_cnt / fold reuse after wave 0's reads
     }
-    if (tid == 0 && P.prog) { P.prog[kProgWords * g + 4] = (uint64_t)ex_rows; P.prog[kProgWords * g + 5] = (uint64_t)scan_rows; }
+    if (tid == 0 && P.prog) {
+        P.prog[kProgWords * g + 4] = (uint64_t)ex_rows; P.prog[kProgWords * g + 5] = (uint64_t)scan_rows;
+        if constexpr (kMasks && kScreen) {
+            uint64_t *sw = P.prog + prog_seed_off(P.G, P.B, kCommitWGs) + (size_t)kSeedWords * g;
+            sw[0] = sd_scans; sw[1] = sd_rows;
+        }
+    }
     // every pod is resolved: this workgroup's rows go back to HBM whole (allocatable, cached doubles,
     // reciprocals) for the next call and for ksched_read_nodes
     for (int e = tid; e < R * 6; e += kST) {
@@ -1698,12 +1813,15 @@ hipError_t pipe_one(const PipeLaunch &L0, int launch, PipeInfo *info, hipStream_
     constexpr size_t kLds = (size_t)160 * 1024;
     int R = 0;
     for (int r = 0; r < L.R; ++r) R = L.P[r].rows_per_wg > R ? L.P[r].rows_per_wg : R;
-    // (pass 2 holds a wave's needed rows in one 64-bit mask per lane: records that fit leave a wave fewer rows anyway)
-    const int sh = ScoreLayout<KC, K>::total_with_hrec(R) <= kLds && ScoreLayout<KC, K>::hrec_qw(R) <= 64 ? 1 : 0;
+    // (pass 2 holds a wave's needed rows in one 64-bit mask per lane: records that fit leave a wave fewer rows anyway.
+    // The KC <= 4 kernels' seeded scan keeps no records: it only needs a wave's rows in one mask)
+    constexpr bool kSeeded = KC <= 4;
     const int so = ScoreLayout<KC, K>::total_screen(R) <= kLds ? 1 : 0;
+    const int sh = (kSeeded ? so != 0 : ScoreLayout<KC, K>::total_with_hrec(R) <= kLds) &&
+                           ScoreLayout<KC, K>::hrec_qw(R) <= 64 ? 1 : 0;
     for (int r = 0; r < L.R; ++r) { L.P[r].screen_h = sh; L.P[r].screen_ok = so; }
-    const size_t sl = sh ? ScoreLayout<KC, K>::total_with_hrec(R)
-                         : (so ? ScoreLayout<KC, K>::total_screen(R) : ScoreLayout<KC, K>::total(R));
+    const size_t sl = sh && !kSeeded ? ScoreLayout<KC, K>::total_with_hrec(R)
+                                     : (so ? ScoreLayout<KC, K>::total_screen(R) : ScoreLayout<KC, K>::total(R));
     const size_t cl = commit_total_bytes<K>(), ml = MergeLayout<KC, K>::total;
     const size_t lds = sl > cl ? (sl > ml ? sl : ml) : (cl > ml ? cl : ml);
     if (info) {

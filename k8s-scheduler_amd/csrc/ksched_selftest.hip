@@ -147,6 +147,19 @@ __global__ void k_selftest_threshold(int64_t n, const float *L, const uint32_t *
     out[3 * n + i] = screen_rec_needed(rec[i], -1, -1) ? 1 : 0;
 }
 
+// The seeded scan's primitives.  flags: bit 0 amb, bit 1 el.  x [6][n]: six lower bounds per element, inserted one by
+// one into a sorted top-4 list (bound_insert<4>).  out [5][n]: screen_need(v, amb, el, L), then the list.
+__global__ void k_selftest_seed(int64_t n, const float *v, const float *L, const uint32_t *flags, const uint32_t *x,
+                                uint32_t *out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = screen_need(v[i], (flags[i] & 1u) != 0, (flags[i] & 2u) != 0, L[i]) ? 1u : 0u;
+    uint32_t t[4] = {0u, 0u, 0u, 0u};
+    for (int s = 0; s < 6; ++s) bound_insert<4>(t, x[s * n + i]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) out[(1 + q) * n + i] = t[q];
+}
+
 // ---- the wave primitives: one 64-lane workgroup per case, lane = element ------------------------------------------
 template <int RUN>
 __device__ __forceinline__ void sort_case(const WaveTestArgs &A, int r, int64_t nl, int64_t i, int lane) {
@@ -291,6 +304,13 @@ hipError_t launch_selftest_screen(int64_t n, const int64_t *req, const int64_t *
 hipError_t launch_selftest_rec_w(int64_t n, const float *w, const float *w2, uint32_t *out, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_selftest_rec_w, grid_of(n), dim3(256), 0, s, n, w, w2, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_selftest_seed(int64_t n, const float *v, const float *L, const uint32_t *flags, const uint32_t *x,
+                                uint32_t *out, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_selftest_seed, grid_of(n), dim3(256), 0, s, n, v, L, flags, x, out);
     return hipGetLastError();
 }
 

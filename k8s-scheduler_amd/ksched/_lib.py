@@ -132,6 +132,7 @@ SIGNATURES = [
     ("ksched_download_results", C.c_int, [CTX, C.c_int64, I32P, F64P, I32P]),
     ("ksched_get_stats", C.c_int, [CTX, C.POINTER(Stats)]),
     ("ksched_get_commit_stamps", C.c_int, [CTX, C.c_int32, I64P]),
+    ("ksched_get_seed_stats", C.c_int, [CTX, I64P]),
     ("ksched_set_timing", C.c_int, [CTX, C.c_int32, C.c_int32]),
     ("ksched_set_timeout", C.c_int, [CTX, C.c_int32]),
     ("ksched_selftest_fastdiv", C.c_int, [CTX, C.c_int64, F64P, F64P, F64P, F64P]),
@@ -140,6 +141,7 @@ SIGNATURES = [
     ("ksched_selftest_screen", C.c_int, [CTX, C.c_int64, I64P, I64P, F32P, U32P]),
     ("ksched_selftest_rec_w", C.c_int, [CTX, C.c_int64, F32P, F32P, U32P]),
     ("ksched_selftest_threshold", C.c_int, [CTX, C.c_int64, F32P, U32P, I32P]),
+    ("ksched_selftest_seed", C.c_int, [CTX, C.c_int64, F32P, F32P, U32P, U32P, U32P]),
     ("ksched_selftest_wave", C.c_int, [CTX, C.c_int64, U64P, I32P, F64P, I32P, I32P, I32P, I32P, U64P, I32P]),
     ("ksched_selftest_list", C.c_int, [CTX, C.c_int64, C.c_int32, F64P, I32P, F64P, I32P]),
     ("ksched_selftest_slots", C.c_int, [CTX, C.c_int64, C.c_int32, U32P, U32P]),

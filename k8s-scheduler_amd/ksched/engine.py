@@ -282,6 +282,12 @@ class Engine:
                     pipeline=PIPELINES.get(int(s.pipeline), str(int(s.pipeline))), rescues=s.rescues,
                     exact_rows=s.exact_rows, scan_rows=s.scan_rows)
 
+    def seed_stats(self) -> dict:
+        """The seeded score scan's counters of the last persistent run, summed over the score workgroups."""
+        w = (C.c_int64 * 5)()
+        self._chk(L.lib().ksched_get_seed_stats(self._ctx, w), "get_seed_stats")
+        return dict(seeded_scans=w[0], seed_rows=w[1], zero_bound_scans=w[2], after_unscreened=w[3], past_cap=w[4])
+
     def commit_stamps(self) -> dict:
         """The persistent commit's counts of the last run (zeros unless KSCHED_COMMIT_STAMPS was set at create)."""
         w = (C.c_int64 * 32)()

@@ -76,10 +76,21 @@ def main():
     if len(sc):  # WG 0 wave 0's stamps of the screened scan (score_role)
         pairs = (t[sc, 13] >> 32) & 0xffffffff
         onp = pairs != 0xffffffff
+        if (t[sc, 37] > 0).all():  # the seeded scan (KC <= 4 kernels): stamp 37 is behind the bound's barrier
+            head = {
+                "  seed pass (start -> 11)": t[sc, 11] - t[sc, 0],
+                "  the other waves' seed pass (11 -> 37)": t[sc, 37] - t[sc, 11],
+                "  bound (37 -> 12)": t[sc, 12] - t[sc, 37],
+                "  single pass (12 -> 14)": t[sc, 14] - t[sc, 12],
+            }
+        else:
+            head = {
+                "  pass 1 (start -> 11)": t[sc, 11] - t[sc, 0],
+                "  bound (11 -> 12)": t[sc, 12] - t[sc, 11],
+                "  pass 2 (12 -> 14)": t[sc, 14] - t[sc, 12],
+            }
         scan = {
-            "  pass 1 (start -> 11)": t[sc, 11] - t[sc, 0],
-            "  bound (11 -> 12)": t[sc, 12] - t[sc, 11],
-            "  pass 2 (12 -> 14)": t[sc, 14] - t[sc, 12],
+            **head,
             "  exact phase (14 -> 8)": t[sc, 8] - t[sc, 14],
             "  barrier after the exact phase (8 -> 9)": t[sc, 9] - t[sc, 8],
             "  rank and entry stores (9 -> 10)": t[sc, 10] - t[sc, 9],
