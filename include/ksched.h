@@ -588,6 +588,32 @@ int ksched_selftest_wave(ksched_ctx *ctx, int64_t ncases, const uint64_t *sort_c
 int ksched_selftest_list(ksched_ctx *ctx, int64_t n, int32_t steps, const double *key, const int32_t *idx,
                          double *out_key, int32_t *out_idx);
 int ksched_selftest_slots(ksched_ctx *ctx, int64_t n, int32_t steps, const uint32_t *x, uint32_t *out);
+/* Diagnostics (added within ABI 6: probe with dlsym): the stream pipeline's list-consuming stages, each as ONE launch
+ * of the engine's own kernel on lists the caller built.  Neither reads node rows: a context without loaded nodes works.
+ * A list entry ("Rec", 56 bytes) is {f64 key; i32 idx; i32 valid; i64 a[3]; u64 labels; f32 price; i32 pad}; a pod's
+ * list is K entries, best first, the invalid ones last; entry 0's pad is the list's cut flag (candidates exist that
+ * the list does not hold, all ranking below its last valid entry).  An export is a 16-byte header {i32 count; 12
+ * bytes 0} and count records ("XRec", 80 bytes) {i32 idx; i32 0; i64 cur[3]; i64 sb[3]; u64 labels; f32 price; 12
+ * bytes 0}.  Results nobody wrote keep the byte 0xa5.
+ *   rank_merge: blocks is R rank blocks in the all-gather layout, each {Rec [nb][K]; i64 fc [nb]}; one launch of
+ *               the rank merge at cursor 0 over nb pods.  out_rec [nb][K], out_fc [nb].  K in {4, 8, 16},
+ *               1 <= R <= 64, 1 <= nb <= 1024, else KSCHED_E_INVALID.
+ *   commit:     ONE commit, by the kernel impl names (KSCHED_COMMIT_SEQUENTIAL or KSCHED_COMMIT_SPECULATIVE), of
+ *               batch 0 of a call of nb pods at batch size B: requests rc / rm / rp / sel [nb] (sel may be NULL
+ *               without labels), lists Rec [nb][K], fc0 [nb] the lists' feasible counts, xin the export the batch
+ *               inherits.  out_idx / out_score / out_feas [nb] (pods at or past the new cursor are unspecified);
+ *               out_x: this batch's export, room for 16 + 160 B bytes; out_ctl [5]: the cursor, the batches
+ *               committed, truncated, the pods placed, and the plan of batch 2.  KSCHED_E_INVALID without a launch,
+ *               as the engine would refuse: K outside {4, 8, 16}, nb outside [1, B], B over 128 (speculative: 64),
+ *               xin's count over 64 (speculative, whatever B: the kernel's inherited slots) or over B (sequential:
+ *               its table holds 2 B nodes), a (B, K) over the sequential commit's LDS (none within these limits). */
+int ksched_selftest_rank_merge(ksched_ctx *ctx, int32_t K, int32_t R, int32_t nb, const void *blocks, void *out_rec,
+                               int64_t *out_fc);
+int ksched_selftest_commit(ksched_ctx *ctx, int32_t impl, int32_t K, int32_t B, int32_t priority, int32_t domain,
+                           int32_t use_labels, int32_t fast53, int32_t nb, const int64_t *rc, const int64_t *rm,
+                           const int64_t *rp, const uint64_t *sel, const void *lists, const int64_t *fc0,
+                           const void *xin, int32_t *out_idx, double *out_score, int32_t *out_feas, void *out_x,
+                           int64_t *out_ctl);
 
 /* ---- host packer: Go-exact Kubernetes quantity parsing ----
  * s == NULL means the key is absent from the ResourceList.  KSCHED_E_PARSE on the reference's

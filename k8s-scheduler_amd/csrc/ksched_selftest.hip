@@ -4,11 +4,16 @@
 // flags, so the results are the source semantics of the primitives under those flags (-ffp-contract=off, ...), not
 // the instruction stream of the kernels that inline them.  Element-wise kernels, or one wave per case; every loop
 // bound is a launch argument.  tests/test_gpu_primitives.py compares the outputs with tests/screen_ref.py and the
-// oracle's score.
+// oracle's score.  At the end of the file, one level up: the stream pipeline's list-consuming stages (rank merge,
+// both commits) launched alone on hand-built lists (ksched_selftest_rank_merge, ksched_selftest_commit).
 #include <hip/hip_runtime.h>
 
+#include <cstring>
+
 #include "ksched_commit.h"
+#include "ksched_ctx.h"
 #include "ksched_merge.h"
+#include "ksched_stream.h"
 
 namespace ksched {
 
@@ -340,3 +345,140 @@ hipError_t launch_selftest_slots(int64_t n, int steps, const uint32_t *x, uint32
 }
 
 }  // namespace ksched
+
+// ------------------------------------------------------------------------------------------------
+// The list-consuming stages alone: the stream pipeline's rank merge and its two commits, each as ONE launch of the
+// engine's own launcher (launch_rank_merge, launch_commit, launch_commit_spc; the control block by launch_ctl_init)
+// on lists the caller built.  No kernel is restated or instantiated here.  Copy in, launch on c->stream, copy out,
+// as the primitive self-tests do (ksched_data.hip).  tests/test_gpu_commit_alone.py compares with tests/commit_ref.py.
+// ------------------------------------------------------------------------------------------------
+using namespace ksched;
+
+namespace {
+
+// one device block of 256-byte aligned parts, freed with the object
+struct StageBlock {
+    char *d = nullptr;
+    size_t total = 0;
+    size_t take(size_t bytes) { const size_t o = total; total += (bytes + 255) / 256 * 256; return o; }
+    hipError_t alloc() { return hipMalloc((void **)&d, total ? total : 256); }
+    template <class T> T *at(size_t off) const { return reinterpret_cast<T *>(d + off); }
+    ~StageBlock() { if (d) hipFree(d); }
+};
+
+// k_commit's admitted LDS, checked for either kernel as enqueue_batched checks it.  With B <= 128 and K <= 16 (at most
+// 150528 bytes) it cannot trip: it stands for the day one of those limits moves.
+constexpr size_t kStageSeqCommitMaxLds = 160 * 1024 - 4096;
+constexpr int kStageSentinel = 0xa5;                         // every byte of a result nobody wrote
+
+int stage_fail(ksched_ctx *c, const char *what, hipError_t e) {
+    (void)hipGetLastError();
+    return fail(c, KSCHED_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+}  // namespace
+
+extern "C" {
+
+int ksched_selftest_rank_merge(ksched_ctx *c, int32_t K, int32_t R, int32_t nb, const void *blocks, void *out_rec,
+                               int64_t *out_fc) {
+    if (!c) return KSCHED_E_INVALID;
+    if ((K != 4 && K != 8 && K != 16) || R < 1 || R > 64 || nb < 1 || nb > 1024 || !blocks || !out_rec || !out_fc)
+        return fail(c, KSCHED_E_INVALID, "selftest_rank_merge: K in {4, 8, 16}, 1 <= R <= 64, 1 <= nb <= 1024");
+    HIPCHK(c, hipSetDevice(c->dev));
+    const size_t rec_bytes = (size_t)nb * K * sizeof(Rec), fc_bytes = (size_t)nb * sizeof(int64_t);
+    const size_t stride = rec_bytes + fc_bytes;
+    StageBlock blk;
+    const size_t o_in = blk.take(stride * R), o_cur = blk.take(8), o_rec = blk.take(rec_bytes), o_fc = blk.take(fc_bytes);
+    HIPCHK(c, blk.alloc());
+    hipStream_t s = c->stream;
+    hipError_t e = hipMemcpyAsync(blk.d + o_in, blocks, stride * R, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(blk.d + o_cur, 0, 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(blk.d + o_rec, kStageSentinel, rec_bytes, s);
+    if (e == hipSuccess) e = hipMemsetAsync(blk.d + o_fc, kStageSentinel, fc_bytes, s);
+    if (e == hipSuccess) {
+        MergeArgs mr{};
+        mr.in = blk.d + o_in; mr.rank_stride = (int64_t)stride; mr.C_in = R; mr.C_out = 1;
+        mr.cursor = blk.at<int64_t>(o_cur); mr.P = nb; mr.B = nb;
+        mr.out_rec = blk.at<Rec>(o_rec); mr.out_fc = blk.at<int64_t>(o_fc);
+        e = launch_rank_merge(K, mr, s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(out_rec, blk.d + o_rec, rec_bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_fc, blk.d + o_fc, fc_bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return stage_fail(c, "selftest_rank_merge", e);
+    return KSCHED_OK;
+}
+
+int ksched_selftest_commit(ksched_ctx *c, int32_t impl, int32_t K, int32_t B, int32_t prio, int32_t dom, int32_t lab,
+                           int32_t f53, int32_t nb, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                           const uint64_t *sel, const void *lists, const int64_t *fc0, const void *xin,
+                           int32_t *out_idx, double *out_score, int32_t *out_feas, void *out_x, int64_t *out_ctl) {
+    if (!c) return KSCHED_E_INVALID;
+    if (!rc || !rm || !rp || !lists || !fc0 || !xin || !out_idx || !out_score || !out_feas || !out_x || !out_ctl)
+        return fail(c, KSCHED_E_INVALID, "selftest_commit: null argument");
+    const bool spc = impl == KSCHED_COMMIT_SPECULATIVE;
+    if (!spc && impl != KSCHED_COMMIT_SEQUENTIAL) return fail(c, KSCHED_E_INVALID, "selftest_commit: impl");
+    if ((K != 4 && K != 8 && K != 16) || B < 1 || B > 128 || nb < 1 || nb > B || (spc && B > 64) ||
+        (prio != kPrioResource && prio != kPrioPrice) || (dom != kDomAll && dom != kDomFeasible))
+        return fail(c, KSCHED_E_INVALID, "selftest_commit: K in {4, 8, 16}, 1 <= nb <= batch <= 128 (speculative: 64)");
+    if (commit_lds_bytes(B, K) > kStageSeqCommitMaxLds)
+        return fail(c, KSCHED_E_INVALID, "selftest_commit: B*(328+48K) <= ~150 KB of LDS");
+    int32_t nin = 0;
+    memcpy(&nin, xin, sizeof(nin));  // XBuf::count
+    if (nin < 0 || nin > (spc ? 64 : B))
+        return fail(c, KSCHED_E_INVALID, "selftest_commit: inherited export over 64 (speculative) or the batch (sequential)");
+    HIPCHK(c, hipSetDevice(c->dev));
+    const size_t q = (size_t)nb, xb = xbuf_bytes(B), list_bytes = q * K * sizeof(Rec);
+    // the inherited export may hold 64 records whatever B (speculative kernel): its part is sized for the larger of
+    // the engine's buffer (2 B records) and 64 records.  A batch exports at most one record per pod (<= B).
+    const size_t xin_room = std::max(xb, 16 + (size_t)64 * sizeof(XRec));
+    StageBlock blk;
+    const size_t o_rc = blk.take(q * 8), o_rm = blk.take(q * 8), o_rp = blk.take(q * 8), o_sel = blk.take(q * 8);
+    const size_t o_lists = blk.take(list_bytes), o_fc0 = blk.take(q * 8), o_xin = blk.take(xin_room), o_xout = blk.take(xb);
+    const size_t o_idx = blk.take(q * 4), o_sc = blk.take(q * 8), o_feas = blk.take(q * 4), o_ctl = blk.take(sizeof(Ctl));
+    HIPCHK(c, blk.alloc());
+    hipStream_t s = c->stream;
+    const size_t xin_bytes = 16 + (size_t)nin * sizeof(XRec);
+    if (xin_bytes > xin_room) return fail(c, KSCHED_E_INVALID, "selftest_commit: inherited export over its buffer");
+    hipError_t e = hipMemcpyAsync(blk.d + o_rc, rc, q * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk.d + o_rm, rm, q * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk.d + o_rp, rp, q * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = sel ? hipMemcpyAsync(blk.d + o_sel, sel, q * 8, hipMemcpyHostToDevice, s) : hipMemsetAsync(blk.d + o_sel, 0, q * 8, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk.d + o_lists, lists, list_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk.d + o_fc0, fc0, q * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(blk.d + o_xin, 0, xin_room, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(blk.d + o_xin, xin, xin_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(blk.d + o_xout, kStageSentinel, xb, s);
+    if (e == hipSuccess) e = hipMemsetAsync(blk.d + o_idx, kStageSentinel, q * 4, s);
+    if (e == hipSuccess) e = hipMemsetAsync(blk.d + o_sc, kStageSentinel, q * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(blk.d + o_feas, kStageSentinel, q * 4, s);
+    Ctl *ctl = blk.at<Ctl>(o_ctl);
+    if (e == hipSuccess) e = hipMemsetAsync(ctl, 0, sizeof(Ctl), s);
+    if (e == hipSuccess) e = launch_ctl_init(ctl, B, nb, 2, s);  // as enqueue_batched: plan[0] = 0, plan[1] = -1 (nb <= B)
+    if (e == hipSuccess) {
+        CommitArgs ca{};  // every persistent-pipeline field stays null / zero
+        ca.lists = blk.at<Rec>(o_lists); ca.fc0 = blk.at<int64_t>(o_fc0);
+        ca.pods = PodArgs{blk.at<int64_t>(o_rc), blk.at<int64_t>(o_rm), blk.at<int64_t>(o_rp), blk.at<uint64_t>(o_sel), nb};
+        ca.plan = &ctl->plan[0]; ca.plan1 = &ctl->plan[1]; ca.plan2 = &ctl->plan[2];
+        ca.ctl = ctl; ca.B = B;
+        ca.xin = blk.at<XBuf>(o_xin); ca.xout = blk.at<XBuf>(o_xout);
+        ca.out = OutArgs{blk.at<int32_t>(o_idx), blk.at<double>(o_sc), blk.at<int32_t>(o_feas)};
+        ca.batch = 0;
+        e = spc ? launch_commit_spc(K, prio, dom, lab != 0, f53 != 0, ca, s)
+                : launch_commit(K, prio, dom, lab != 0, f53 != 0, ca, commit_lds_bytes(B, K), s);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    Ctl h{};
+    if (e == hipSuccess) e = hipMemcpy(&h, ctl, sizeof(Ctl), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_idx, blk.d + o_idx, q * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_score, blk.d + o_sc, q * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_feas, blk.d + o_feas, q * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_x, blk.d + o_xout, xb, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return stage_fail(c, "selftest_commit", e);
+    out_ctl[0] = h.cursor; out_ctl[1] = h.stats[0]; out_ctl[2] = h.stats[1]; out_ctl[3] = h.stats[2]; out_ctl[4] = h.plan[2];
+    return KSCHED_OK;
+}
+
+}  // extern "C"

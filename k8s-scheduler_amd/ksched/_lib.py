@@ -145,6 +145,9 @@ SIGNATURES = [
     ("ksched_selftest_wave", C.c_int, [CTX, C.c_int64, U64P, I32P, F64P, I32P, I32P, I32P, I32P, U64P, I32P]),
     ("ksched_selftest_list", C.c_int, [CTX, C.c_int64, C.c_int32, F64P, I32P, F64P, I32P]),
     ("ksched_selftest_slots", C.c_int, [CTX, C.c_int64, C.c_int32, U32P, U32P]),
+    ("ksched_selftest_rank_merge", C.c_int, [CTX, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, I64P]),
+    ("ksched_selftest_commit", C.c_int, [CTX] + [C.c_int32] * 8 + [I64P, I64P, I64P, U64P, C.c_void_p, I64P, C.c_void_p,
+                                         I32P, F64P, I32P, C.c_void_p, I64P]),
     ("ksched_parse_cpu", C.c_int, [C.c_char_p, I64P]),
     ("ksched_parse_memory", C.c_int, [C.c_char_p, I64P]),
     ("ksched_parse_pods", C.c_int, [C.c_char_p, I64P]),
