@@ -582,6 +582,14 @@ int ksched_selftest_threshold(ksched_ctx *ctx, int64_t n, const float *L, const 
  * then the sorted top-4 list after six bound_insert<4>. */
 int ksched_selftest_seed(ksched_ctx *ctx, int64_t n, const float *v, const float *L, const uint32_t *flags,
                          const uint32_t *x, uint32_t *out);
+/* touch_screen (added within ABI 6): the persistent commit's touched-node column, element = one (pod, column) pair:
+ * req the pod's request, alloc the column's node state, thr the pod's list threshold, active != 0: the pod may use the
+ * column.  out_f32 [4][n]: the column's staged f32 reciprocals x3 (touch_stage), the pod's screen value; out_u32 [2][n]:
+ * the pod needs the exact key (touch_need), some element of its wave -- 64 consecutive elements -- does; out_key [n]:
+ * touch_column's key (resource priority, all-node domain): exact where the wave needs it (-inf: not eligible), the
+ * skip NaN 0x7ff8000000000bad otherwise. */
+int ksched_selftest_touch_screen(ksched_ctx *ctx, int64_t n, const int64_t *req, const int64_t *alloc, const float *thr,
+                                 const uint32_t *active, float *out_f32, uint32_t *out_u32, double *out_key);
 int ksched_selftest_wave(ksched_ctx *ctx, int64_t ncases, const uint64_t *sort_code, const int32_t *sort_idx,
                          const double *key, const int32_t *idx, const int32_t *aux, const int32_t *cut,
                          const int32_t *nv, uint64_t *out_u64, int32_t *out_i32);

@@ -61,6 +61,46 @@ __device__ __forceinline__ float screen_y(int64_t a, double y) {
     return (a > 0 && a < (1ll << 52)) ? (float)y : __builtin_nanf("");
 }
 
+// A touched-node column's screen constants: screen_y of its three resources.  They depend on the column alone, so the
+// lane that stages the column computes them once (P2's slot step for export(b - 1), wave 0's staging of a round's
+// guesses) and the screen loops load them (16 bytes per column in LDS; w pads)
+struct alignas(16) TouchY {
+    float c, m, p, w;
+};
+__device__ __forceinline__ TouchY touch_stage(int64_t a0, int64_t a1, int64_t a2, double y0, double y1, double y2) {
+    return TouchY{screen_y(a0, y0), screen_y(a1, y1), screen_y(a2, y2), 0.0f};
+}
+// One pod (f32 requests q*, threshold thr) against one column (staged ty, state n*): the f32 screen value *v, and whether
+// the pod needs the column's exact key -- it may use the column (active) and the screen does not prove the key below
+// thr (a NaN screen never does).  tests/touch_screen_ref.py states it bit for bit.
+__device__ __forceinline__ bool touch_need(float qc, float qm, float qp, float thr, const TouchY &ty, int64_t rc, int64_t rm,
+                                           int64_t rp, int64_t n0, int64_t n1, int64_t n2, bool active, float *v) {
+    bool lo;
+    *v = screen_pair(qc, qm, qp, ty.c, ty.m, ty.p, n0 >= rc, n1 >= rm, n2 >= rp, &lo);
+    return active && !(*v < thr);
+}
+// The touched-node column, the one statement the commit's three screen loops share (every lane of the wave: lane = pod).
+// Returns whether some lane needs the column; *key is then every lane's exact key (-inf: not eligible) in the
+// reference's operation order, from the column's staged doubles fy = {(double)n[3], recip_or_zero(n)[3]}, which are
+// read only then; kSkipKey otherwise.
+template <int PRIO, int DOM, bool F53>
+__device__ __forceinline__ bool touch_column(float qc, float qm, float qp, float thr, const TouchY &ty, bool active,
+                                             bool feas, int64_t rc, int64_t rm, int64_t rp, double rcf, double rmf,
+                                             double rpf, int64_t n0, int64_t n1, int64_t n2, const double *fy, double y3,
+                                             float pr, double *key) {
+    float v;
+    const bool need = touch_need(qc, qm, qp, thr, ty, rc, rm, rp, n0, n1, n2, active, &v);
+    if (__ballot(need) == 0) {
+        *key = skip_key();
+        return false;
+    }
+    double k;
+    const bool el = pair_key_fast<PRIO, DOM, F53>(feas, rc, rm, rp, rcf, rmf, rpf, n0, n1, n2, fy[0], fy[1], fy[2], fy[3],
+                                                  fy[4], fy[5], y3, pr, &k);
+    *key = el ? k : -__builtin_inf();
+    return true;
+}
+
 struct alignas(8) SpcSlot {
     int32_t idx;
     int32_t mine;     // committed by this batch (exported)
@@ -76,6 +116,7 @@ struct SpcSmem {
     int32_t *hk;      // open-addressed table: node index per position (-1 = empty)
     int64_t *s0;      // prologue only (aliases D): [inherited slot][3] state at this batch's score snapshot
     double *iy;       // prologue only (aliases GS): [inherited slot][6] current state as doubles, reciprocals
+    TouchY *iyt;      // prologue only, the screened commit (aliases GS behind iy's 128 rows): [entry of export(b - 1)]
     int32_t *HP;      // [K][64] table position of list entry (q, pod); kSpcInvalid for no entry
     uint32_t *tkc;    // [64] words: bit = position taken by a CONFIRMED touch (T)
     int32_t *ti;      // node index per slot
@@ -95,7 +136,9 @@ struct SpcSmem {
     int32_t *own;     // [kSpcHash] lowest pod proposing each position in a guess iteration (64 = none);
                       // step 1 only (aliases pbk/pbx, which steps 2-3 use)
     uint64_t *GS;     // [64 pods][kGS] each pod's guessed entry: state a[3], labels, price, and the state after
-                      // the pod's commit n[3] with its (double) and refined reciprocals (computed once, lane = pod)
+                      // the pod's commit n[3] with its (double) and refined reciprocals (computed once, lane = pod).
+                      // The screened commit keeps the states in the entry's slot T[gs] instead (written by the same
+                      // lane) and the column's TouchY in words 0-1; words 8-13 as above
     float *thr;       // [64] per pod: a touched node's key screens below this -> it cannot matter (kSkipKey)
     // persistent commit: the slots of the older export (batch b - 2) are keyed by the merger workgroups
     int16_t *x2s;     // [64] slot of that export's entry e (-1: the node is also in export(b - 1): no slot)
@@ -442,6 +485,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
         m.own = reinterpret_cast<int32_t *>(m.pbk);
         m.s0 = reinterpret_cast<int64_t *>(m.D);
         m.iy = reinterpret_cast<double *>(m.GS);
+        m.iyt = reinterpret_cast<TouchY *>(m.iy + 128 * 6);
         m.rb2 = reinterpret_cast<float *>(m.dfacc);
     }
     const int nb = (int)((A.pods.p - p0 < A.B) ? A.pods.p - p0 : A.B);  // <= 64 (host-checked)
@@ -498,31 +542,34 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
         const float thrf = SCR ? m.thr[lane] : 0.0f;
         const float qc = screen_req(rc), qm = screen_req(rm), qp = screen_req(rp);
         int64_t nex = 0;
-        for (int e = wave; e < ne; e += kSpcWaves) {
-            const int t = sl(e);
+        // SCR: the slots of all the wave's entries in one read (lane u: its u-th entry), no LDS trip per entry for them
+        int tv = 0;
+        if constexpr (SCR) {
+            const int ev = wave + lane * kSpcWaves;
+            tv = ev < ne ? sl(ev) : 0;
+        }
+        for (int e = wave, u = 0; e < ne; e += kSpcWaves, ++u) {
+            const int t = SCR ? __builtin_amdgcn_readlane(tv, u) : sl(e);
             const SpcSlot &x = m.T[t];
             const int64_t *x0 = m.s0 + e * 3;
             const bool f0 = fits(rc, rm, rp, sel, x0[0], x0[1], x0[2], x.labels, LAB);
             const bool f1 = fits(rc, rm, rp, sel, x.cur[0], x.cur[1], x.cur[2], x.labels, LAB);
             dfl += (int)f1 - (int)f0;
             const double *yy = m.iy + e * 6;  // the entry's state as doubles and its reciprocals, staged once
-            bool need = true;
-            if constexpr (SCR) {
-                bool lo;
-                const float v = screen_pair(qc, qm, qp, screen_y(x.cur[0], yy[3]), screen_y(x.cur[1], yy[4]),
-                                            screen_y(x.cur[2], yy[5]), x.cur[0] >= rc, x.cur[1] >= rm, x.cur[2] >= rp, &lo);
-                need = pj && !(v < thrf);
-            }
             double k;
-            if (!SCR || __ballot(need) != 0) {
+            if constexpr (SCR) {
+                const bool any = touch_column<PRIO, DOM, F53>(qc, qm, qp, thrf, m.iyt[e], pj, f1, rc, rm, rp, rcf, rmf, rpf,
+                                                              x.cur[0], x.cur[1], x.cur[2], yy, y3, x.price, &k);
+                Srow[t] = k;
+                if (!any) continue;  // kSkipKey never passes better()
+                ++nex;
+            } else {
                 ++nex;
                 const bool el = pair_key_fast<PRIO, DOM, F53>(f1, rc, rm, rp, rcf, rmf, rpf, x.cur[0], x.cur[1], x.cur[2],
                                                               yy[0], yy[1], yy[2], yy[3], yy[4], yy[5], y3, x.price, &k);
                 k = el ? k : -__builtin_inf();
-            } else {
-                k = skip_key();
+                Srow[t] = k;
             }
-            Srow[t] = k;
             const bool up = k != -__builtin_inf() && better(k, x.idx, pk, pi);
             pk = up ? k : pk; pi = up ? x.idx : pi; ps = up ? t : ps;
         }
@@ -719,7 +766,15 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                 x.labels = xi.labels; x.price = xi.price; x.pad = 0;
                 m.ti[slot] = xi.idx;
                 m.gs[lane] = slot;  // (gs is the guess step's; free until then)
-                stage_state(m.iy + lane * 6, xi.cur);
+                if constexpr (SCR) {  // with the entry's screen constants
+                    double st[6];
+                    stage_state(st, xi.cur);
+#pragma unroll
+                    for (int r = 0; r < 6; ++r) m.iy[lane * 6 + r] = st[r];
+                    m.iyt[lane] = touch_stage(xi.cur[0], xi.cur[1], xi.cur[2], st[3], st[4], st[5]);
+                } else {
+                    stage_state(m.iy + lane * 6, xi.cur);
+                }
                 if (dup) m.x2s[slot] = -1;
                 else atomicOr(&m.tkc[h >> 5], 1u << (h & 31));
             }
@@ -960,66 +1015,107 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                 const int64_t n0 = wsub((int64_t)v[0], rc), n1 = wsub((int64_t)v[1], rm), n2 = wsub((int64_t)v[2], 1);
                 const double nf0 = (double)n0, nf1 = (double)n1, nf2 = (double)n2;
                 uint64_t *o = m.GS + (size_t)lane * kGS;
+                if constexpr (SCR) {
+                    // the guess's slot record, by its own lane (the evaluation loads the states from it), and the
+                    // column's screen constants
+                    const double ny0 = recip_or_zero(n0, nf0), ny1 = recip_or_zero(n1, nf1), ny2 = recip_or_zero(n2, nf2);
+                    SpcSlot &x = m.T[my_s];
+                    x.idx = my_g; x.mine = 1;
+                    x.sb[0] = (int64_t)v[0]; x.sb[1] = (int64_t)v[1]; x.sb[2] = (int64_t)v[2];  // untouched before this batch
+                    x.cur[0] = n0; x.cur[1] = n1; x.cur[2] = n2;
+                    x.labels = v[3]; x.price = __uint_as_float((uint32_t)v[4]); x.pad = 0;
+                    m.ti[my_s] = my_g;
+                    *reinterpret_cast<TouchY *>(o) = touch_stage(n0, n1, n2, ny0, ny1, ny2);
+                    o[8] = (uint64_t)__double_as_longlong(nf0); o[9] = (uint64_t)__double_as_longlong(nf1);
+                    o[10] = (uint64_t)__double_as_longlong(nf2);
+                    o[11] = (uint64_t)__double_as_longlong(ny0);
+                    o[12] = (uint64_t)__double_as_longlong(ny1);
+                    o[13] = (uint64_t)__double_as_longlong(ny2);
+                } else {
 #pragma unroll
-                for (int w = 0; w < 5; ++w) o[w] = v[w];
-                o[5] = (uint64_t)n0; o[6] = (uint64_t)n1; o[7] = (uint64_t)n2;
-                o[8] = (uint64_t)__double_as_longlong(nf0); o[9] = (uint64_t)__double_as_longlong(nf1);
-                o[10] = (uint64_t)__double_as_longlong(nf2);
-                o[11] = (uint64_t)__double_as_longlong(recip_or_zero(n0, nf0));
-                o[12] = (uint64_t)__double_as_longlong(recip_or_zero(n1, nf1));
-                o[13] = (uint64_t)__double_as_longlong(recip_or_zero(n2, nf2));
+                    for (int w = 0; w < 5; ++w) o[w] = v[w];
+                    o[5] = (uint64_t)n0; o[6] = (uint64_t)n1; o[7] = (uint64_t)n2;
+                    o[8] = (uint64_t)__double_as_longlong(nf0); o[9] = (uint64_t)__double_as_longlong(nf1);
+                    o[10] = (uint64_t)__double_as_longlong(nf2);
+                    o[11] = (uint64_t)__double_as_longlong(recip_or_zero(n0, nf0));
+                    o[12] = (uint64_t)__double_as_longlong(recip_or_zero(n1, nf1));
+                    o[13] = (uint64_t)__double_as_longlong(recip_or_zero(n2, nf2));
+                }
             }
             __syncthreads();
             const float thrf = SCR ? m.thr[lane] : 0.0f;
             const float qc = screen_req(rc), qm = screen_req(rm), qp = screen_req(rp);
             int64_t nev = 0, nex = 0;
-            for (int k = rc0 + wave; k < rce; k += kSpcWaves) {
-                const int32_t g = __builtin_amdgcn_readfirstlane(m.gn[k]);
-                if (g < 0) continue;  // wave-uniform
-                const int s = __builtin_amdgcn_readfirstlane(m.gs[k]);
-                const uint64_t *gsk = m.GS + (size_t)k * kGS;
-                const int64_t a0 = (int64_t)gsk[0], a1 = (int64_t)gsk[1], a2 = (int64_t)gsk[2];
-                const uint64_t lab = gsk[3];
-                const float pr = __uint_as_float((uint32_t)gsk[4]);
-                const int64_t n0 = (int64_t)gsk[5], n1 = (int64_t)gsk[6], n2 = (int64_t)gsk[7];
-                const bool fo = fits(rc, rm, rp, sel, a0, a1, a2, lab, LAB);
-                const bool fn = fits(rc, rm, rp, sel, n0, n1, n2, lab, LAB);
-                const int d = (int)fn - (int)fo;
-                const double ny0 = __longlong_as_double((long long)gsk[11]), ny1 = __longlong_as_double((long long)gsk[12]),
-                             ny2 = __longlong_as_double((long long)gsk[13]);
-                bool need = true;
-                if constexpr (SCR) {  // only the pods after the guessing one use its column
-                    bool lo;
-                    const float v = screen_pair(qc, qm, qp, screen_y(n0, ny0), screen_y(n1, ny1), screen_y(n2, ny2),
-                                                n0 >= rc, n1 >= rm, n2 >= rp, &lo);
-                    need = lane > k && pj && !(v < thrf);
-                }
-                double kv;
-                ++nev;
-                if (!SCR || __ballot(need) != 0) {
+            // SCR: the slots of all the wave's columns in one read (lane u: its u-th column; -1 where gn < 0), no LDS
+            // trip per column for them; the guessed node comes with the slot's record
+            int32_t sv = -1;
+            if constexpr (SCR) {
+                const int kk = rc0 + wave + lane * kSpcWaves;
+                if (kk < rce) sv = m.gs[kk];
+            }
+            for (int k = rc0 + wave, u = 0; k < rce; k += kSpcWaves, ++u) {
+                if constexpr (SCR) {
+                    const int s = __builtin_amdgcn_readlane(sv, u);
+                    if (s < 0) continue;  // wave-uniform
+                    const SpcSlot &x = m.T[s];
+                    const uint64_t *gsk = m.GS + (size_t)k * kGS;
+                    const int64_t n0 = x.cur[0], n1 = x.cur[1], n2 = x.cur[2];
+                    const bool fo = fits(rc, rm, rp, sel, x.sb[0], x.sb[1], x.sb[2], x.labels, LAB);
+                    const bool fn = fits(rc, rm, rp, sel, n0, n1, n2, x.labels, LAB);
+                    const int d = (int)fn - (int)fo;
+                    double kv;
+                    ++nev;
+                    // only the pods after the guessing one use its column
+                    const bool any = touch_column<PRIO, DOM, F53>(
+                        qc, qm, qp, thrf, *reinterpret_cast<const TouchY *>(gsk), lane > k && pj, fn, rc, rm, rp, rcf, rmf,
+                        rpf, n0, n1, n2, reinterpret_cast<const double *>(gsk + 8), y3, x.price, &kv);
+                    Srow[s] = kv;
+                    m.D[k * 64 + lane] = (int8_t)d;
+                    if (lane > k && d != 0) atomicAdd(&m.fcg[lane], d);
+                    if (!any) continue;  // kSkipKey never passes better()
+                    ++nex;
+                    if (lane > k) {
+                        const int32_t g = x.idx;
+                        const bool up = kv != -__builtin_inf() && better(kv, g, pk, pi);
+                        pk = up ? kv : pk; pi = up ? g : pi; ps = up ? s : ps;
+                    }
+                } else {
+                    const int32_t g = __builtin_amdgcn_readfirstlane(m.gn[k]);
+                    if (g < 0) continue;  // wave-uniform
+                    const int s = __builtin_amdgcn_readfirstlane(m.gs[k]);
+                    const uint64_t *gsk = m.GS + (size_t)k * kGS;
+                    const int64_t a0 = (int64_t)gsk[0], a1 = (int64_t)gsk[1], a2 = (int64_t)gsk[2];
+                    const uint64_t lab = gsk[3];
+                    const float pr = __uint_as_float((uint32_t)gsk[4]);
+                    const int64_t n0 = (int64_t)gsk[5], n1 = (int64_t)gsk[6], n2 = (int64_t)gsk[7];
+                    const bool fo = fits(rc, rm, rp, sel, a0, a1, a2, lab, LAB);
+                    const bool fn = fits(rc, rm, rp, sel, n0, n1, n2, lab, LAB);
+                    const int d = (int)fn - (int)fo;
+                    const double ny0 = __longlong_as_double((long long)gsk[11]), ny1 = __longlong_as_double((long long)gsk[12]),
+                                 ny2 = __longlong_as_double((long long)gsk[13]);
+                    double kv;
+                    ++nev;
                     ++nex;
                     const bool el = pair_key_fast<PRIO, DOM, F53>(
                         fn, rc, rm, rp, rcf, rmf, rpf, n0, n1, n2, __longlong_as_double((long long)gsk[8]),
                         __longlong_as_double((long long)gsk[9]), __longlong_as_double((long long)gsk[10]), ny0, ny1, ny2,
                         y3, pr, &kv);
                     kv = el ? kv : -__builtin_inf();
-                } else {
-                    kv = skip_key();
-                }
-                Srow[s] = kv;
-                m.D[k * 64 + lane] = (int8_t)d;
-                if (lane > k) {
-                    if (d != 0) atomicAdd(&m.fcg[lane], d);
-                    const bool up = kv != -__builtin_inf() && better(kv, g, pk, pi);
-                    pk = up ? kv : pk; pi = up ? g : pi; ps = up ? s : ps;
-                }
-                if (lane == 0) {
-                    SpcSlot &x = m.T[s];
-                    x.idx = g; x.mine = 1;
-                    x.sb[0] = a0; x.sb[1] = a1; x.sb[2] = a2;  // untouched before this batch
-                    x.cur[0] = n0; x.cur[1] = n1; x.cur[2] = n2;
-                    x.labels = lab; x.price = pr; x.pad = 0;
-                    m.ti[s] = g;
+                    Srow[s] = kv;
+                    m.D[k * 64 + lane] = (int8_t)d;
+                    if (lane > k) {
+                        if (d != 0) atomicAdd(&m.fcg[lane], d);
+                        const bool up = kv != -__builtin_inf() && better(kv, g, pk, pi);
+                        pk = up ? kv : pk; pi = up ? g : pi; ps = up ? s : ps;
+                    }
+                    if (lane == 0) {
+                        SpcSlot &x = m.T[s];
+                        x.idx = g; x.mine = 1;
+                        x.sb[0] = a0; x.sb[1] = a1; x.sb[2] = a2;  // untouched before this batch
+                        x.cur[0] = n0; x.cur[1] = n1; x.cur[2] = n2;
+                        x.labels = lab; x.price = pr; x.pad = 0;
+                        m.ti[s] = g;
+                    }
                 }
             }
             m.pbk[wave * 64 + lane] = pk;
@@ -1227,22 +1323,13 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                         fcc += (int32_t)fn - (int32_t)fo;
                         double kv;
                         if constexpr (SCR) {  // the pods after f use this column
-                            const double nf0 = (double)n0, nf1 = (double)n1, nf2 = (double)n2;
-                            const double ny0 = recip_or_zero(n0, nf0), ny1 = recip_or_zero(n1, nf1),
-                                         ny2 = recip_or_zero(n2, nf2);
-                            bool lo;
-                            const float v = screen_pair(screen_req(rc), screen_req(rm), screen_req(rp), screen_y(n0, ny0),
-                                                        screen_y(n1, ny1), screen_y(n2, ny2), n0 >= rc, n1 >= rm, n2 >= rp,
-                                                        &lo);
-                            const bool need = lane > f && pj && !(v < m.thr[lane]);
-                            const bool any = __ballot(need) != 0;
-                            if (any) {
-                                const bool el = pair_key_fast<PRIO, DOM, F53>(fn, rc, rm, rp, rcf, rmf, rpf, n0, n1, n2, nf0,
-                                                                              nf1, nf2, ny0, ny1, ny2, y3, pr, &kv);
-                                kv = el ? kv : -__builtin_inf();
-                            } else {
-                                kv = skip_key();
-                            }
+                            const int64_t nn[3] = {n0, n1, n2};
+                            double st[6];
+                            stage_state(st, nn);
+                            const bool any = touch_column<PRIO, DOM, F53>(
+                                screen_req(rc), screen_req(rm), screen_req(rp), m.thr[lane],
+                                touch_stage(n0, n1, n2, st[3], st[4], st[5]), lane > f && pj, fn, rc, rm, rp, rcf, rmf, rpf,
+                                n0, n1, n2, st, y3, pr, &kv);
                             if (A.dbg && lane == 0) {  // diagnostics: sequential columns keyed, exactly
                                 atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[20]), 1ull);
                                 if (any) atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[21]), 1ull);
@@ -1467,7 +1554,11 @@ static_assert(spc_lds_bytes<16>() <= 160 * 1024, "k_commit_spc LDS");
 static_assert(spc_lds_bytes<16, kPipeThreads, true>() == spc_small_bytes<16, kPipeThreads, true>() + 64 * 193 * 8,
               "SpcSmem: S last");
 // the prologue's aliases: the inherited snapshot states in D, their staged doubles in GS
-static_assert(64 * 64 >= 128 * 3 * 8 && 64 * kGS * 8 >= 128 * 6 * 8, "SpcSmem prologue aliases");
+// (and behind them, in the screened commit, the TouchY of export(b - 1)'s <= 64 entries)
+static_assert(64 * 64 >= 128 * 3 * 8 && 64 * kGS * 8 >= 128 * 6 * 8 + 64 * sizeof(TouchY), "SpcSmem prologue aliases");
+// a guessed entry's TouchY lies in words 0-1 of its GS row, 16-byte aligned (every array in front of GS is a multiple
+// of 16 bytes), in front of the doubles in words 8-13
+static_assert(sizeof(TouchY) == 16 && kGS * 8 % 16 == 0 && kGS >= 14, "SpcSmem::GS rows hold a TouchY");
 static_assert((size_t)(kSpcThreads / 64) * 64 * 16 >= kSpcHash * 4 && (kPipeThreads / 64) * 64 * 16 >= kSpcHash * 4,
               "SpcSmem::own aliases pbk/pbx");
 

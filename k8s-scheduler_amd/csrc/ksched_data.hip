@@ -441,6 +441,22 @@ int ksched_selftest_seed(ksched_ctx *c, int64_t n, const float *v, const float *
                         });
 }
 
+int ksched_selftest_touch_screen(ksched_ctx *c, int64_t n, const int64_t *req, const int64_t *alloc, const float *thr,
+                                 const uint32_t *active, float *out_f32, uint32_t *out_u32, double *out_key) {
+    if (!c || n < 0 || (n > 0 && (!req || !alloc || !thr || !active || !out_f32 || !out_u32 || !out_key)))
+        return KSCHED_E_INVALID;
+    if (n == 0) return KSCHED_OK;
+    const size_t q = (size_t)n;
+    return selftest_run(c, "selftest_touch_screen",
+                        {{req, nullptr, q * 24}, {alloc, nullptr, q * 24}, {thr, nullptr, q * 4}, {active, nullptr, q * 4},
+                         {nullptr, out_f32, q * 16}, {nullptr, out_u32, q * 8}, {nullptr, out_key, q * 8}},
+                        [&](const std::vector<void *> &p) {
+                            return launch_selftest_touch_screen(n, (const int64_t *)p[0], (const int64_t *)p[1],
+                                                                (const float *)p[2], (const uint32_t *)p[3], (float *)p[4],
+                                                                (uint32_t *)p[5], (double *)p[6], c->stream);
+                        });
+}
+
 int ksched_selftest_wave(ksched_ctx *c, int64_t ncases, const uint64_t *sort_code, const int32_t *sort_idx,
                          const double *key, const int32_t *idx, const int32_t *aux, const int32_t *cut,
                          const int32_t *nv, uint64_t *out_u64, int32_t *out_i32) {

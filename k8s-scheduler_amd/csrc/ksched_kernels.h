@@ -271,6 +271,8 @@ hipError_t launch_selftest_rec_w(int64_t n, const float *w, const float *w2, uin
 hipError_t launch_selftest_threshold(int64_t n, const float *L, const uint32_t *rec, int32_t *out, hipStream_t s);
 hipError_t launch_selftest_seed(int64_t n, const float *v, const float *L, const uint32_t *flags, const uint32_t *x,
                                 uint32_t *out, hipStream_t s);
+hipError_t launch_selftest_touch_screen(int64_t n, const int64_t *req, const int64_t *alloc, const float *thr,
+                                        const uint32_t *active, float *f, uint32_t *u, double *key, hipStream_t s);
 hipError_t launch_selftest_wave(const WaveTestArgs &a, hipStream_t s);
 hipError_t launch_selftest_list(int64_t n, int S, const double *key, const int32_t *idx, double *okey, int32_t *oidx,
                                 hipStream_t s);

@@ -165,6 +165,35 @@ __global__ void k_selftest_seed(int64_t n, const float *v, const float *L, const
     for (int q = 0; q < 4; ++q) out[(1 + q) * n + i] = t[q];
 }
 
+// The commit's touched-node column (ksched_commit.h), element = one (pod, column) pair: the column's constants as its
+// staging lane computes them (touch_stage on the state's recip_or_zero), the pod's screen value and decision
+// (touch_need), and the column itself (touch_column<resource, all-node>) over each wave of 64 consecutive elements.
+// f [4][n]: the staged reciprocals x3, the value; u [2][n]: needed, some element of the wave needed; key [n]: the
+// column's key (exact where the wave needed it, kSkipKey otherwise)
+__global__ void k_selftest_touch_screen(int64_t n, const int64_t *req, const int64_t *alloc, const float *thr,
+                                        const uint32_t *active, float *f, uint32_t *u, double *key) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = i < n;  // (every lane of a wave reaches touch_column's ballot)
+    const PairOps o = load_ops(n, in ? i : 0, req, alloc);
+    const TouchY ty = touch_stage(o.a[0], o.a[1], o.a[2], o.y[0], o.y[1], o.y[2]);
+    const float q0 = screen_req(o.r[0]), q1 = screen_req(o.r[1]), q2 = screen_req(o.r[2]);
+    const float th = in ? thr[i] : 0.0f;
+    const bool act = in && active[i] != 0;
+    float v;
+    const bool need = touch_need(q0, q1, q2, th, ty, o.r[0], o.r[1], o.r[2], o.a[0], o.a[1], o.a[2], act, &v);
+    const bool feas = fits(o.r[0], o.r[1], o.r[2], 0ull, o.a[0], o.a[1], o.a[2], 0ull, false);
+    const double fy[6] = {o.af[0], o.af[1], o.af[2], o.y[0], o.y[1], o.y[2]};
+    double k;
+    const bool any = touch_column<kPrioResource, kDomAll, false>(q0, q1, q2, th, ty, act, feas, o.r[0], o.r[1], o.r[2],
+                                                                 o.rf[0], o.rf[1], o.rf[2], o.a[0], o.a[1], o.a[2], fy, o.y3,
+                                                                 0.0f, &k);
+    if (!in) return;
+    f[i] = ty.c; f[n + i] = ty.m; f[2 * n + i] = ty.p; f[3 * n + i] = v;
+    u[i] = need ? 1u : 0u;
+    u[n + i] = any ? 1u : 0u;
+    key[i] = k;
+}
+
 // ---- the wave primitives: one 64-lane workgroup per case, lane = element ------------------------------------------
 template <int RUN>
 __device__ __forceinline__ void sort_case(const WaveTestArgs &A, int r, int64_t nl, int64_t i, int lane) {
@@ -303,6 +332,13 @@ hipError_t launch_selftest_screen(int64_t n, const int64_t *req, const int64_t *
                                   hipStream_t s) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_selftest_screen, grid_of(n), dim3(256), 0, s, n, req, alloc, f, u);
+    return hipGetLastError();
+}
+
+hipError_t launch_selftest_touch_screen(int64_t n, const int64_t *req, const int64_t *alloc, const float *thr,
+                                        const uint32_t *active, float *f, uint32_t *u, double *key, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_selftest_touch_screen, grid_of(n), dim3(256), 0, s, n, req, alloc, thr, active, f, u, key);
     return hipGetLastError();
 }
 

@@ -142,6 +142,7 @@ SIGNATURES = [
     ("ksched_selftest_rec_w", C.c_int, [CTX, C.c_int64, F32P, F32P, U32P]),
     ("ksched_selftest_threshold", C.c_int, [CTX, C.c_int64, F32P, U32P, I32P]),
     ("ksched_selftest_seed", C.c_int, [CTX, C.c_int64, F32P, F32P, U32P, U32P, U32P]),
+    ("ksched_selftest_touch_screen", C.c_int, [CTX, C.c_int64, I64P, I64P, F32P, U32P, F32P, U32P, F64P]),
     ("ksched_selftest_wave", C.c_int, [CTX, C.c_int64, U64P, I32P, F64P, I32P, I32P, I32P, I32P, U64P, I32P]),
     ("ksched_selftest_list", C.c_int, [CTX, C.c_int64, C.c_int32, F64P, I32P, F64P, I32P]),
     ("ksched_selftest_slots", C.c_int, [CTX, C.c_int64, C.c_int32, U32P, U32P]),
