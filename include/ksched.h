@@ -511,6 +511,108 @@ int ksched_schedule_constrained(ksched_ctx *ctx, int64_t p,
         const int64_t *req_ext /* n_ext * p, or NULL */,
         int32_t *out_idx, double *out_score, int32_t *out_feasible, int32_t *out_gang_placed);
 
+/* ---- inter-pod affinity and anti-affinity (added within ABI 6: probe with dlsym(lib, "ksched_schedule_affinity"); the version number did not move) ----
+ * Required inter-pod affinity and anti-affinity (podAffinity / podAntiAffinity with
+ * requiredDuringSchedulingIgnoredDuringExecution), resolved by ONE launch of the exact kernel whatever opts.mode says
+ * (stats.pipeline == KSCHED_PIPE_EXACT, stats.pair_evals == p * n).  A build extension: the reference knows no
+ * constraints.  The label bitset cannot express it -- the rule depends on where earlier pods of the same call landed --
+ * and neither can spread: its rule is a skew against a minimum, its domains stop at 1024 (hostname scope needs D = n),
+ * and it has no symmetric half ("an already-bound pod refuses me").
+ *
+ * Groups: at most KSCHED_AFF_MAX_GROUPS = 64.  A group is the set of pods that one term's label selector matches; group
+ * s is bit s of a uint64_t.
+ * Scopes: two.  host: every node is its own domain and always carries the key (kubernetes.io/hostname).  zone: ONE
+ * topology key; node_domain[j] in [-1, D), -1: node j does not carry the key; D in [0, KSCHED_SPREAD_MAX_DOMAINS].
+ * D == 0: there is no zone key -- node_domain may be NULL and every node counts as -1.  Every id in [0, D) must be
+ * carried by some node, as ksched_load_spread requires.
+ *
+ * The table (ksched_load_affinity, after ksched_load_nodes): three mask arrays of n_local uint64_t each, NULL = all zero.
+ *   node_member[j]     bit s: some pod bound on j belongs to group s
+ *   node_anti_host[j]  bit s: some pod bound on j carries a required anti-affinity term of host scope against group s
+ *   node_anti_zone[j]  the same for zone scope; on a node without the key the bits are kept and read back but act on
+ *                      nothing
+ * The library derives the rest:
+ *   zone_member[d] = OR of node_member over the nodes of domain d      any_host = OR of every node_member
+ *   zone_anti[d]   = OR of node_anti_zone over the nodes of domain d   any_zone = OR of every zone_member[d]
+ *
+ * Pods, all flat arrays (the cgo rule at the top of this file); any of them may be NULL, meaning zeros (-1 for aff_group):
+ *   member[i]                   the groups the pod belongs to
+ *   anti_host[i], anti_zone[i]  the groups its required anti-affinity terms name, per scope
+ *   aff_group[i] in [-1, 64), aff_zone[i] (0 = host, otherwise zone)   its ONE required affinity term; -1: none
+ * A pod carries at most one affinity term: kube-scheduler counts an existing pod towards affinity only if it matches ALL
+ * the pod's terms, which a per-group mask cannot state; with one term the two readings coincide.  It may carry any
+ * number of anti-affinity terms: kube treats those one by one.
+ *
+ * Per pod i, in order, with d = node_domain[j] and a the bit of aff_group[i]:
+ *   eligible(i, j) = fits(i, j) && all three of
+ *   1. own anti-affinity:    (node_member[j] & anti_host[i]) == 0 && (d < 0 || (zone_member[d] & anti_zone[i]) == 0)
+ *                            -- a node without the key cannot violate a zone term
+ *   2. bound pods' anti-affinity, the symmetric half:
+ *                            (node_anti_host[j] & member[i]) == 0 && (d < 0 || (zone_anti[d] & member[i]) == 0)
+ *   3. own affinity, when aff_group[i] >= 0:
+ *        waived when a is not in any_host (host scope) or not in any_zone (zone scope), and a is in member[i] -- kube's
+ *          first pod of a self-affine set; a waived pod passes this clause on every node
+ *        host scope otherwise: a is in node_member[j]
+ *        zone scope otherwise: d >= 0 and a is in zone_member[d]
+ * fits is the scheduler's predicate, with the label check under opts.use_labels.  Everything else is ksched_schedule in
+ * exact mode with eligible in the place of fits: out_feasible counts eligible nodes, zero eligible nodes is
+ * KSCHED_NO_FIT, the key, the tie-break and the commit alloc -= (req_cpu, req_mem, 1) are unchanged.  The constraint
+ * joins the predicate exactly as labels, spread and ext do: under KSCHED_DOMAIN_ALL an ineligible node can still win the
+ * argmax; callers who want enforcement use KSCHED_DOMAIN_FEASIBLE, or best-price.
+ *
+ * Commit: a pod placed on w, with dw = node_domain[w], does the following whether or not w was eligible:
+ *   node_member[w] |= member[i]; node_anti_host[w] |= anti_host[i]; node_anti_zone[w] |= anti_zone[i];
+ *   any_host |= member[i];
+ *   where dw >= 0: zone_member[dw] |= member[i]; zone_anti[dw] |= anti_zone[i]; any_zone |= member[i].
+ * Bound pods never leave during a call, so the words only gain bits: no counts, no minima, no recount.
+ *
+ * State: the table lives in the context and carries over from call to call; ksched_read_affinity returns the three node
+ * arrays (any pointer may be NULL).  ksched_load_nodes invalidates the table (ksched_schedule_affinity and
+ * ksched_read_affinity return KSCHED_E_STATE until it is loaded again); ksched_apply_delta and ksched_save_state /
+ * ksched_restore_state leave it alone, as with spread -- the caller reloads after deletions
+ * (FakeCluster.schedule_affinity reloads the table on every call).  No other call reads or moves the table.  After
+ * ksched_schedule_affinity, ksched_explain_batch / ksched_explain_pod return KSCHED_E_STATE: they know no affinity reason
+ * (KSCHED_NUM_REASONS did not change).
+ *
+ * KSCHED_E_INVALID (nothing changed; a table loaded earlier survives): D outside [0, KSCHED_SPREAD_MAX_DOMAINS], a node
+ * domain outside [-1, D), a domain id in [0, D) that no node carries, node_domain == NULL with D > 0 and n > 0,
+ * aff_group[i] outside [-1, 64), p outside [0, 2^30), opts.nranks > 1.
+ *
+ * Out of scope: affinity inside ksched_schedule_constrained and the gang rollback (the words only gain bits, so an undo
+ * needs a snapshot of the touched words); preferred (scored) terms; more than one affinity term per pod; more than one
+ * zone key; namespaceSelector, matchLabelKeys; pod removal without a reload; affinity reasons in the explain calls;
+ * ksched_rank and ksched_preempt under affinity; the batched pipelines and multi-rank; the one-workgroup exact kernel.
+ *
+ * Worked example (best-price, feasible domain, ample room): nodes n0 (zone A, price 0.1), n1 (B, 0.2), n2 (A, 0.3), n3
+ * (no key, 0.4); groups web = bit 0, cache = bit 1, db = bit 2; the table starts empty.  Pods: p0, p1: member web,
+ * anti_host web.  p2, p3, p4: member cache, anti_zone cache, affinity web at zone scope.  p5: as p0.  p6: member web, no
+ * terms.  p7: member db, affinity db at host scope.  p8: member db, affinity db at zone scope.
+ *   pod  eligible  goes to  why
+ *   p0   4         n0       nothing bound yet
+ *   p1   3         n1       n0 is barred
+ *   p2   3         n0       web is in A and B, and n3 has no key
+ *   p3   1         n1       zone A now holds a cache
+ *   p4   0         NO_FIT   both zones are barred
+ *   p5   2         n2       eligible n2 and n3
+ *   p6   1         n3       the web pods on n0-n2 refuse it: the symmetric half
+ *   p7   4         n0       waived
+ *   p8   2         n0       db is now in A: n0, n2
+ * out_idx = {0, 1, 0, 1, -1, 2, 3, 0, 0}, out_feasible = {4, 3, 3, 1, 0, 2, 1, 4, 2}, final node_member = {7, 3, 1, 1},
+ * node_anti_host = {1, 1, 1, 0}, node_anti_zone = {2, 2, 0, 0}.  ksched_schedule on the same input gives all 0. */
+#define KSCHED_AFF_MAX_GROUPS 64             /* one bit of a uint64_t per group */
+int ksched_load_affinity(ksched_ctx *ctx, int32_t n_domains, const int32_t *node_domain /* n_local, or NULL with n_domains 0 */,
+                         const uint64_t *node_member /* n_local, NULL = zeros */,
+                         const uint64_t *node_anti_host /* n_local, NULL = zeros */,
+                         const uint64_t *node_anti_zone /* n_local, NULL = zeros */);
+int ksched_read_affinity(ksched_ctx *ctx, uint64_t *out_member /* n_local, or NULL */,
+                         uint64_t *out_anti_host /* n_local, or NULL */, uint64_t *out_anti_zone /* n_local, or NULL */);
+int ksched_schedule_affinity(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,
+                             const int64_t *req_pods, const uint64_t *selector,
+                             const uint64_t *member /* p, or NULL */, const uint64_t *anti_host /* p, or NULL */,
+                             const uint64_t *anti_zone /* p, or NULL */, const int32_t *aff_group /* p, or NULL */,
+                             const uint8_t *aff_zone /* p, or NULL = host */,
+                             int32_t *out_idx, double *out_score, int32_t *out_feasible);
+
 /* Same, in two halves, with the pods staged in HBM: upload once, run many times (bench). */
 int ksched_upload_pods(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,
                        const int64_t *req_pods, const uint64_t *selector);

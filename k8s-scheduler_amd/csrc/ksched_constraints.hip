@@ -1,11 +1,13 @@
-// ksched_constraints.hip -- libksched: the three extensions of exact mode above the kernel.  The schedule calls
-// (ksched_schedule_gangs / _spread / _ext, and ksched_schedule_constrained for the three in one run) check and pack on
-// the host, stage what they packed and run k_exact with their extension (ExactRun, ksched_exact.h); the table calls load
-// and read the context's spread and extended-resource tables.
+// ksched_constraints.hip -- libksched: the extensions of exact mode above the kernel.  The schedule calls
+// (ksched_schedule_gangs / _spread / _ext, ksched_schedule_constrained for the three in one run, and
+// ksched_schedule_affinity) check and pack on the host, stage what they packed and run k_exact with their extension
+// (ExactRun, ksched_exact.h); the table calls load and read the context's spread, extended-resource and affinity tables.
 #include <cstring>
 
 #include <new>
+#include <utility>
 
+#include "ksched_affinity.h"
 #include "ksched_ctx.h"
 #include "ksched_ext.h"
 #include "ksched_gang.h"
@@ -243,6 +245,91 @@ int ksched_schedule_constrained(ksched_ctx *c, int64_t p, const int64_t *rc, con
                                   Staged<int64_t>{c->d->ereq, reqs.data(), reqs.size() * 8},
                                   Staged<int32_t>{c->d->eword, ewords.data(), (size_t)p * 4});
     return r != KSCHED_OK ? r : gang_results(c, ng, gang_off ? out_gang_placed : nullptr);
+}
+
+// The affinity table of ksched_schedule_affinity: checked on the host (ksched_affinity.h), and its zone and `any` words
+// derived there, before anything is allocated or staged; then uploaded in the stream of the kernel that reads it.
+// Touches no node row; the context holds the new table only once the last copy has landed, and the earlier one until the
+// checks have passed.
+int ksched_load_affinity(ksched_ctx *c, int32_t n_domains, const int32_t *node_domain, const uint64_t *node_member,
+                         const uint64_t *node_anti_host, const uint64_t *node_anti_zone) {
+    if (!c) return KSCHED_E_INVALID;
+    static_assert(KSCHED_AFF_MAX_GROUPS == kAffMaxGroups && kAffPodWords == kAffWords, "affinity constants");
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_affinity before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "load_affinity: affinity scheduling is single-GPU (the exact kernel)");
+    AffDerived der;
+    try {
+        if (const char *why = aff_check_table(c->n_local, n_domains, node_domain))
+            return fail(c, KSCHED_E_INVALID, std::string("load_affinity: ") + why);
+        aff_derive(c->n_local, n_domains, node_domain, node_member, node_anti_zone, &der);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "load_affinity: host allocation failed");
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->aff_valid = false;
+    ksched_bufs &d = *c->d;
+    const size_t n = (size_t)c->n_local, zb = der.zone.size() * 8;
+    HIPCHK(c, d.adom.reserve(n * 4)); HIPCHK(c, d.amem.reserve(n * 8)); HIPCHK(c, d.aanti_h.reserve(n * 8));
+    HIPCHK(c, d.aanti_z.reserve(n * 8)); HIPCHK(c, d.azone.reserve(zb)); HIPCHK(c, d.aany.reserve(16));
+    if (n > 0) {
+        // (node_domain may be null only where no node carries a zone: every domain -1, all bytes 0xff)
+        if (node_domain) HIPCHK(c, hipMemcpyAsync(d.adom, node_domain, n * 4, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(c, hipMemsetAsync(d.adom, 0xff, n * 4, c->stream));
+        const std::pair<uint64_t *, const uint64_t *> masks[] = {
+            {d.amem.p, node_member}, {d.aanti_h.p, node_anti_host}, {d.aanti_z.p, node_anti_zone}};
+        for (const auto &m : masks) {
+            if (m.second) HIPCHK(c, hipMemcpyAsync(m.first, m.second, n * 8, hipMemcpyHostToDevice, c->stream));
+            else HIPCHK(c, hipMemsetAsync(m.first, 0, n * 8, c->stream));
+        }
+    }
+    if (zb > 0) HIPCHK(c, hipMemcpyAsync(d.azone, der.zone.data(), zb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's arrays, and der, are free again
+    c->aff_D = n_domains;
+    c->aff_any[0] = der.any_host; c->aff_any[1] = der.any_zone;
+    c->aff_valid = true;
+    return KSCHED_OK;
+}
+
+int ksched_read_affinity(ksched_ctx *c, uint64_t *out_member, uint64_t *out_anti_host, uint64_t *out_anti_zone) {
+    if (!c) return KSCHED_E_INVALID;
+    if (!c->aff_valid) return fail(c, KSCHED_E_STATE, "read_affinity: no affinity table (ksched_load_affinity after every ksched_load_nodes)");
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t bytes = (size_t)c->n_local * 8;
+    if (bytes > 0) {
+        if (out_member) HIPCHK(c, hipMemcpy(out_member, c->d->amem, bytes, hipMemcpyDeviceToHost));
+        if (out_anti_host) HIPCHK(c, hipMemcpy(out_anti_host, c->d->aanti_h, bytes, hipMemcpyDeviceToHost));
+        if (out_anti_zone) HIPCHK(c, hipMemcpy(out_anti_zone, c->d->aanti_z, bytes, hipMemcpyDeviceToHost));
+    }
+    return KSCHED_OK;
+}
+
+int ksched_schedule_affinity(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                             const uint64_t *sel, const uint64_t *member, const uint64_t *anti_host,
+                             const uint64_t *anti_zone, const int32_t *aff_group, const uint8_t *aff_zone, int32_t *oi,
+                             double *os, int32_t *of) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_affinity before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_affinity is single-GPU (the exact kernel)");
+    if (!c->aff_valid)
+        return fail(c, KSCHED_E_STATE, "schedule_affinity: no affinity table (ksched_load_affinity after every ksched_load_nodes)");
+    // every group is checked, and the per-pod words are packed, before anything is written or allocated
+    std::vector<int32_t> words;
+    std::vector<uint64_t> pods;
+    try {
+        if (const char *why = aff_pack_pods(p, member, anti_host, anti_zone, aff_group, aff_zone, &words, &pods))
+            return fail(c, KSCHED_E_INVALID, std::string("schedule_affinity: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "schedule_affinity: host staging buffer");
+    }
+    const int r = schedule_staged(c, kRunAffinity, "schedule_affinity", p, rc, rm, rp, sel, oi, os, of,
+                                  Staged<int32_t>{c->d->aword, words.data(), (size_t)p * 4},
+                                  Staged<uint64_t>{c->d->apod, pods.data(), pods.size() * 8});
+    if (r != KSCHED_OK || p == 0) return r;  // (no pods: no launch, the any words stand)
+    // the run's final any words, for the next call's arguments (the sync above is behind the kernel that wrote them)
+    HIPCHK(c, hipMemcpy(c->aff_any, c->d->aany, sizeof(c->aff_any), hipMemcpyDeviceToHost));
+    return KSCHED_OK;
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // ksched_ctx.h -- the context behind the C-ABI (include/ksched.h) and what the host units share: ksched_engine.hip
 // (lifecycle, run / sync, the enqueue paths), ksched_data.hip (node / pod data calls), ksched_constraints.hip (the
-// gang / spread / extended-resource calls of exact mode), ksched_xchg.hip (ranks meeting) and ksched_diag.hip
+// gang / spread / extended-resource / affinity calls of exact mode), ksched_xchg.hip (ranks meeting) and ksched_diag.hip
 // (environment, traces, dumps, device error decoding).  Internal: not part of the ABI.
 #pragma once
 
@@ -110,6 +110,11 @@ struct ksched_bufs {
     DevBuf<int32_t> sword;                // ksched_schedule_spread: ExactArgs::sp_word per pod
     DevBuf<int64_t> etab, ereq;           // ksched_load_ext: the R x n table; ksched_schedule_ext: ExactArgs::ext_req
     DevBuf<int32_t> eword;                // ksched_schedule_ext: ExactArgs::ext_word per pod
+    DevBuf<int32_t> adom;                 // ksched_load_affinity: node -> zone domain (-1 everywhere without a zone key)
+    DevBuf<uint64_t> amem, aanti_h, aanti_z;  // ... node_member, node_anti_host, node_anti_zone
+    DevBuf<uint64_t> azone, aany;         // ... {zone_member, zone_anti} per domain; the run's final {any_host, any_zone}
+    DevBuf<int32_t> aword;                // ksched_schedule_affinity: ExactArgs::af_word per pod
+    DevBuf<uint64_t> apod;                // ... ExactArgs::af_pod, kAffWords per pod
     DevBuf<void> xws, xbuf;               // explain: workspace; counts + NO_FIT pod list, or one pod's state + counts
     DevBuf<void> rws;                     // ksched_rank: one chunk's pods, span lists and outputs (rank_geometry's bound)
     DevBuf<int64_t> bcpu, bmem, boff;     // ksched_load_bound: the bound-pod table (BoundTable, ksched_preempt.h)
@@ -203,6 +208,9 @@ struct ksched_ctx {
     bool bound_valid = false;    // ksched_load_bound's table describes the loaded nodes (every load_nodes clears it)
     int32_t spread_D = 0, spread_S = 0;  // ksched_load_spread's table; 0: none (every load_nodes clears it)
     int32_t ext_R = 0;           // ksched_load_ext's table: its resource columns; 0: none (every load_nodes clears it)
+    bool aff_valid = false;      // ksched_load_affinity's table describes the loaded nodes (every load_nodes clears it)
+    int32_t aff_D = 0;           // ... its zone domains (0: no zone key)
+    uint64_t aff_any[2] = {};    // ... any_host, any_zone: into every affinity run by value, back from d->aany behind it
     bool all_spread = false, all_ext = false;  // ksched_schedule_constrained: the tables its kRunAll launch is given
     // pods
     int64_t p = 0;

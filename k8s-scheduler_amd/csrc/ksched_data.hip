@@ -123,6 +123,7 @@ int ksched_load_nodes(ksched_ctx *c, int64_t n, const int64_t *ac, const int64_t
     c->bound_valid = false;  // ... and neither does the bound-pod table (ksched_load_bound)
     c->spread_D = c->spread_S = 0;  // ... nor the spread table (ksched_load_spread)
     c->ext_R = 0;  // ... nor the extended-resource table (ksched_load_ext)
+    c->aff_valid = false;  // ... nor the affinity table (ksched_load_affinity)
     HIPCHK(c, c->d->nodes.reserve((size_t)n * sizeof(NodeRec)));
     c->d->snap.release();
     // in the stream of the kernels that read it (a legacy hipMemcpy from pageable memory may return before its DMA

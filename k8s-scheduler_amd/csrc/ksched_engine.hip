@@ -467,7 +467,7 @@ int enqueue_persistent(ksched_ctx *c) {
 }
 
 // run (ExactRun, ksched_exact.h): a plain exact run, or the run of ksched_schedule_gangs / _spread / _ext /
-// _constrained over what that call staged -- always k_exact, the multi-slot kernel, under the same geometry and launch
+// _constrained / _affinity over what that call staged -- always k_exact, the multi-slot kernel, under the same geometry and launch
 // rule as a plain run
 int enqueue_exact(ksched_ctx *c, ExactRun run) {
     if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "exact mode is single-GPU; use batched mode across ranks");
@@ -540,6 +540,12 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
             }
             if (c->all_ext) { a.ext = c->d->etab; a.ext_req = c->d->ereq; a.n_ext = c->ext_R; }
             break;
+        case kRunAffinity:
+            a.af_dom = c->d->adom; a.af_member = c->d->amem; a.af_anti_host = c->d->aanti_h;
+            a.af_anti_zone = c->d->aanti_z; a.af_zone = c->d->azone; a.af_any = c->d->aany;
+            a.af_any_host = c->aff_any[0]; a.af_any_zone = c->aff_any[1]; a.af_D = c->aff_D;
+            a.af_word = c->d->aword; a.af_pod = c->d->apod;
+            break;
     }
     HIPCHK(c, launch_exact(run, npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
                            G > 1 && !c->diag.plain_launch, c->stream));
@@ -599,7 +605,7 @@ int ksched::run_impl(ksched_ctx *c, ExactRun run) {
     // FAST53 bound true of the state the NEXT call starts from
     if (r == KSCHED_OK) c->max_abs_alloc = sat_add(c->max_abs_alloc, c->sum_abs_req);
     // (a rolled-back gang leaves no final placements for ksched_explain_batch to rebuild a pod's state from)
-    // (and the explain calls know no spread or extended-resource reason)
+    // (and the explain calls know no spread, extended-resource or affinity reason)
     c->explain_valid = r == KSCHED_OK && run == kRunPlain;
     return r;
 }

@@ -1,5 +1,5 @@
-// ksched_exact.h -- exact mode (ksched_exact.hip): the arguments of k_exact / k_exact1, the constants of the three
-// extensions of k_exact (gangs, topology spread, extended resources) and the launchers.  ksched_ctx.h includes it
+// ksched_exact.h -- exact mode (ksched_exact.hip): the arguments of k_exact / k_exact1, the constants of the four
+// extensions of k_exact (gangs, topology spread, extended resources, inter-pod affinity) and the launchers.  ksched_ctx.h includes it
 // beside ksched_kernels.h, so the host units keep one include and no other device unit depends on it.
 #pragma once
 
@@ -14,9 +14,10 @@ namespace ksched {
 // kRunAll (ksched_schedule_constrained): all of these in one launch, a rejected gang undoing its extended-resource and
 // spread commits with its node rows.  No other pairing is instantiated: a kRunAll launch switches a constraint it does
 // not need off by uniform runtime values (sp_S == 0 with every sp_word -1; n_ext == 0 with every ext_word 0; gangs of
-// one).  Every run but kRunPlain is the multi-slot kernel k_exact whatever opts.mode, under the same geometry and launch
+// one).  kRunAffinity (ksched_schedule_affinity): the staged words in d->aword / d->apod and the context's affinity
+// table; it is paired with no other kind.  Every run but kRunPlain is the multi-slot kernel k_exact whatever opts.mode, under the same geometry and launch
 // rule as a plain exact run.
-enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3, kRunAll = 4 };
+enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3, kRunAll = 4, kRunAffinity = 5 };
 
 struct ExactArgs {
     NodeRec *nodes;
@@ -45,6 +46,18 @@ struct ExactArgs {
     const int64_t *ext_req;   // [p][kExtMax] requests, pod-major (columns at and beyond n_ext: 0)
     const int32_t *ext_word;  // per pod: bit r set where ext_req[i][r] != 0; the kernel reads it with the request
     int32_t n_ext;            // 1..kExtMax (kRunAll: 0 -- no table, every ext_word is 0)
+    // k_exact<AFF> (ksched_schedule_affinity): the context's affinity table and the staged pod words
+    const int32_t *af_dom;    // [n] node -> zone domain in [0, af_D), or -1: the node does not carry the zone key
+    uint64_t *af_member;      // [n] groups with a pod bound on the node: read at entry, written at exit
+    uint64_t *af_anti_host;   // [n] groups the node's bound pods refuse at host scope: read at entry, written at exit
+    uint64_t *af_anti_zone;   // [n] the same at zone scope: ORed into by the winner's owner lane only
+    uint64_t *af_zone;        // [af_D][2] per domain {zone_member, zone_anti}: read at entry, written at exit
+    uint64_t *af_any;         // out: [2] {any_host, any_zone} after the call's last pod
+    uint64_t af_any_host, af_any_zone;  // the OR of every af_member / of every zone_member before the first pod
+    int32_t af_D;             // 0..kSpreadMaxDomains (0: no zone key, every af_dom is -1)
+    const int32_t *af_word;   // per pod: 0 (no group, no term), or 1 | zone scope of its affinity term << 1; the kernel
+                              // reads it with the request
+    const uint64_t *af_pod;   // [p][kAffWords] member, anti_host, anti_zone, the affinity term's group bit (0: none)
 };
 constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
 constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
@@ -53,6 +66,9 @@ constexpr int kSpreadMaxGroups = 64;    // KSCHED_SPREAD_MAX_GROUPS
 constexpr int kSpreadMaxCells = 4096;   // KSCHED_SPREAD_MAX_CELLS: the LDS table of every workgroup, 16 KiB
 constexpr int kExtMax = 4;              // KSCHED_EXT_MAX: columns of the dynamic LDS table, kExtMax * 256 * 8 slots * 8 B = 64 KiB
 
+constexpr int kAffMaxGroups = 64;       // KSCHED_AFF_MAX_GROUPS: one bit of a 64-bit word per group
+constexpr int kAffWords = 4;            // ExactArgs::af_pod: words per pod
+
 constexpr int kExactBlock = 256;
 constexpr int kExact1Block = 1024;  // k_exact1: the whole node set in one workgroup
 
@@ -60,8 +76,9 @@ constexpr int kExact1Block = 1024;  // k_exact1: the whole node set in one workg
 // below 2^52 for the whole call (host-checked), enabling (double)(a-r) == (double)a - (double)r.
 // One launch of k_exact<run>.  kRunGang: a.gang_end set (a.gang_placed may be null); kRunSpread: a.sp_* set; kRunExt:
 // a.ext* set, dynamic LDS of a.n_ext * block * npt * 8 bytes; kRunAll: a.gang_end, a.sp_word and a.ext_word set, the
-// spread table's fields set or sp_S == 0, the extended-resource table's set or n_ext == 0.  (An
-// extension never runs k_exact1: the one-workgroup kernel knows no gang log, spread table or extended-resource table.)
+// spread table's fields set or sp_S == 0, the extended-resource table's set or n_ext == 0; kRunAffinity: a.af_* set,
+// dynamic LDS of block * npt * 20 bytes (two 8-byte words and the domain of every slot).  (An extension never runs
+// k_exact1: the one-workgroup kernel knows no gang log and no spread, extended-resource or affinity table.)
 hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
                         bool cooperative, hipStream_t s);
 // exact mode on one workgroup of bs threads, npt node slots each: bs 1024 with npt 1-4 (resource) or 1-6, 8, 12, 16

@@ -1,6 +1,9 @@
-// ksched_exact.hip -- CDNA4 (gfx950) kernels of exact mode: k_exact with its three extensions (gangs, topology
-// spread, extended resources; each alone, or all three composed), the one-workgroup k_exact1, and their launchers.
+// ksched_exact.hip -- CDNA4 (gfx950) kernels of exact mode: k_exact with its extensions (gangs, topology spread,
+// extended resources -- each alone, or all three composed -- and inter-pod affinity, alone), the one-workgroup k_exact1,
+// and their launchers.
 // Compiled with -ffp-contract=off: every double op rounds individually, exactly like the Go reference.
+// Two objects, as ksched_pipe.hip's three (-DKSCHED_EXACT_PART): part 0 is every kind but affinity, k_exact1 and the
+// launchers; part 1 is the affinity kind's 40 instantiations behind launch_exact_affinity.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -8,7 +11,14 @@
 #include "ksched_exact.h"
 #include "ksched_kernels.h"  // KSCHED_DISPATCH, kErrExactExchange
 
+#ifndef KSCHED_EXACT_PART
+#define KSCHED_EXACT_PART 0
+#endif
+
 namespace ksched {
+
+hipError_t launch_exact_affinity(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
+                                 hipStream_t s);  // part 1
 
 namespace {
 
@@ -78,6 +88,34 @@ __device__ __forceinline__ int32_t *dom_table() {
     }
 }
 
+// k_exact<AFF>: a workgroup's copy of the zone words of the affinity table, per domain {zone_member, zone_anti} side
+// by side (one 16-byte gather per slot), 16 KiB
+struct AffZone {
+    uint64_t member, anti;
+};
+template <bool AFF>
+__device__ __forceinline__ AffZone *aff_zone() {
+    if constexpr (AFF) {
+        __shared__ __attribute__((aligned(16))) AffZone s_zone[kSpreadMaxDomains];
+        return s_zone;
+    } else {
+        return nullptr;
+    }
+}
+
+// k_exact<AFF>: the per-slot words of a workgroup, in dynamic LDS: node_member of slot s = tid + k * kExactBlock at
+// [s], node_anti_host at [kExactBlock * NPT + s], and behind them the slots' domains (int32, laid out as dom_table is).
+// Consecutive lanes read consecutive words; only the owning thread ever touches a slot's words.
+template <bool AFF>
+__device__ __forceinline__ uint64_t *aff_table() {
+    if constexpr (AFF) {
+        extern __shared__ __attribute__((aligned(16))) uint64_t s_aff[];
+        return s_aff;
+    } else {
+        return nullptr;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Exact mode: one persistent launch schedules every pod in order.
 //   - workgroup g owns nodes [g*per_wg, (g+1)*per_wg); thread t holds nodes g*per_wg + t + k*256
@@ -127,10 +165,24 @@ __device__ __forceinline__ int32_t *dom_table() {
 //   minimum and the number of domains at it exact per decrement (a value below the minimum becomes the minimum, held
 //   once; a value equal to it is one more holder).  The next pod's gathers read the table before its first barrier, so
 //   a walk that moved the table ends with one barrier (workgroup-uniform: rejected, and a logged member was counted).
+// AFF (ksched_schedule_affinity): required inter-pod affinity and anti-affinity over at most 64
+//   selector groups, one bit of a 64-bit word each, at host scope (every node its own domain) and zone scope (af_dom).
+//   Paired with no other kind.  The slots' node_member and node_anti_host words and their domains live in dynamic LDS
+//   (aff_table; the registers are full), touched by the owning thread only; every workgroup keeps the whole zone table
+//   {zone_member, zone_anti}[D] in static LDS (AffZone, loaded at entry, written back by workgroup 0 at exit); any_host
+//   and any_zone are workgroup-uniform values that every thread carries.  The pod's four words come with its request as
+//   uniform loads, behind a staged word that is 0 for a pod without group or term: such a pod reads no LDS and commits
+//   nothing.  A slot is eligible when it fits and three AND tests of the pod's words against the slot's and its zone's
+//   words pass (include/ksched.h).  Every workgroup derives the same winner; its owner lane ORs the pod's words into its
+//   own slot's words (node_anti_zone, which no test reads, straight into the global array), every thread ORs member into
+//   its any words, and thread 0 ORs into its workgroup's zone words behind a uniform load of the winner's domain -- no
+//   exchange, no wait, the tag and parity sequence unchanged.  The next pod's gathers read the zone table before its
+//   first barrier, so a pod that may have moved it ends with one barrier; its condition -- placed, the winner's domain
+//   >= 0, (member | anti_zone) != 0 -- is made of uniform inputs only, never of the LDS words thread 0 is writing.
 // ------------------------------------------------------------------------------------------------
 template <int NPT, int PRIO, int DOM, bool LAB, bool F53, ExactRun RUN>
 __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
-    constexpr bool ALL = RUN == kRunAll;
+    constexpr bool ALL = RUN == kRunAll, AFF = RUN == kRunAffinity;
     constexpr bool GANG = RUN == kRunGang || ALL, SPREAD = RUN == kRunSpread || ALL, EXT = RUN == kRunExt || ALL;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -195,6 +247,27 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                 ext[r * kExtCol + k * kExactBlock] = id[k] != kNoIdx ? A.ext[(int64_t)r * A.n + id[k]] : 0;
         }
     }
+    // AFF: this thread's slot k: node_member at af_mem[k * kExactBlock], node_anti_host at af_anti[k * kExactBlock], the
+    // domain at af_dom[k * kExactBlock] (no other thread touches them); the zone table; the any words
+    [[maybe_unused]] uint64_t *const af_mem = AFF ? aff_table<AFF>() + tid : nullptr;
+    [[maybe_unused]] uint64_t *const af_anti = AFF ? af_mem + kExactBlock * NPT : nullptr;
+    [[maybe_unused]] int32_t *const af_dom = AFF ? (int32_t *)(aff_table<AFF>() + 2 * kExactBlock * NPT) + tid : nullptr;
+    [[maybe_unused]] AffZone *const zone = aff_zone<AFF>();
+    [[maybe_unused]] uint64_t any_host = AFF ? A.af_any_host : 0, any_zone = AFF ? A.af_any_zone : 0;
+    if constexpr (AFF) {
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            const bool own = id[k] != kNoIdx;
+            af_mem[k * kExactBlock] = own ? A.af_member[id[k]] : 0;
+            af_anti[k * kExactBlock] = own ? A.af_anti_host[id[k]] : 0;
+            af_dom[k * kExactBlock] = own ? A.af_dom[id[k]] : -1;
+        }
+        for (int d = tid; d < A.af_D; d += kExactBlock) {
+            zone[d].member = A.af_zone[2 * d];
+            zone[d].anti = A.af_zone[2 * d + 1];
+        }
+        __syncthreads();
+    }
 
     __shared__ double s_key[2][kExactBlock / 64];
     __shared__ int32_t s_idx[2][kExactBlock / 64];
@@ -238,6 +311,20 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                 for (int r = 0; r < kExtMax; ++r) er[r] = A.ext_req[i * kExtMax + r];
             }
         }
+        // AFF: 0 (no group, no term: nothing is read or committed), or 1 | zone scope << 1 -- loaded with the request
+        // too -- and, only where it is set, the pod's words (pod-major: uniform loads)
+        [[maybe_unused]] const int32_t aword = AFF ? A.af_word[i] : 0;
+        [[maybe_unused]] uint64_t pmem = 0, pah = 0, paz = 0, pabit = 0;
+        [[maybe_unused]] bool azone = false;  // the affinity term (pabit != 0) is of zone scope
+        if constexpr (AFF) {
+            if (aword != 0) {
+                pmem = A.af_pod[i * kAffWords]; pah = A.af_pod[i * kAffWords + 1];
+                paz = A.af_pod[i * kAffWords + 2]; pabit = A.af_pod[i * kAffWords + 3];
+                azone = (aword & 2) != 0;
+                // waived: no pod of the group is bound anywhere in scope and the pod is in the group itself
+                if ((pabit & (azone ? any_zone : any_host)) == 0 && (pabit & pmem) != 0) pabit = 0;
+            }
+        }
         const double rcf = (double)rc, rmf = (double)rm, rpf = (double)rp;
         double bk = -__builtin_inf();
         int32_t bi = kNoIdx;
@@ -261,6 +348,23 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
 #pragma unroll
                         for (int r = 0; r < kExtMax; ++r)
                             if (eword >> r & 1) f = f && er[r] <= ext[r * kExtCol + k * kExactBlock];
+                    }
+                }
+                if constexpr (AFF) {
+                    if (aword != 0) {  // (uniform: a pod without group or term reads no LDS)
+                        const uint64_t nm = af_mem[k * kExactBlock], na = af_anti[k * kExactBlock];
+                        const int32_t dk = af_dom[k * kExactBlock];
+                        // own anti-affinity | the bound pods' anti-affinity, host scope; then the same at zone scope,
+                        // which a node without the key cannot violate
+                        uint64_t bad = (nm & pah) | (na & pmem);
+                        uint64_t zm = 0;
+                        if (dk >= 0) {
+                            const AffZone z = zone[dk];
+                            bad |= (z.member & paz) | (z.anti & pmem);
+                            zm = z.member;
+                        }
+                        // own affinity (pabit == 0: none, or waived): the group on this node, or in its zone
+                        f = f && bad == 0 && ((azone ? zm : nm) & pabit) == pabit;
                     }
                 }
                 cnt += f;
@@ -358,6 +462,13 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                                 }
                         }
                     }
+                    if constexpr (AFF) {
+                        if (aword != 0) {  // the owner lane: its own slot's words; node_anti_zone is read by no test
+                            af_mem[k * kExactBlock] |= pmem;
+                            af_anti[k * kExactBlock] |= pah;
+                            if (paz != 0) A.af_anti_zone[gi] |= paz;
+                        }
+                    }
                 }
             }
         }
@@ -365,6 +476,21 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
             A.out.idx[i] = oidx;
             A.out.score[i] = osc;
             A.out.feas[i] = (int32_t)gc;
+        }
+        if constexpr (AFF) {
+            if (aword != 0 && oidx >= 0) {  // (the same in every thread of every workgroup)
+                any_host |= pmem;
+                // uniform inputs only -- the pod's words and the winner's domain, a load from an array nobody writes --
+                // decide the barrier: never the zone words themselves, which thread 0 is about to overwrite
+                if ((pmem | paz) != 0) {
+                    const int32_t wd = A.af_dom[__builtin_amdgcn_readfirstlane(oidx)];
+                    if (wd >= 0) {
+                        any_zone |= pmem;
+                        if (tid == 0) { zone[wd].member |= pmem; zone[wd].anti |= paz; }
+                        __syncthreads();  // the next pod's gathers come before its first barrier
+                    }
+                }
+            }
         }
         if constexpr (SPREAD) {
             if (sword >= 0 && oidx >= 0) {  // (the same in every thread of every workgroup)
@@ -469,6 +595,22 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                 if (id[k] != kNoIdx) A.ext[(int64_t)r * A.n + id[k]] = ext[r * kExtCol + k * kExactBlock];
         }
     }
+    if constexpr (AFF) {
+#pragma unroll
+        for (int k = 0; k < NPT; ++k)
+            if (id[k] != kNoIdx) {
+                A.af_member[id[k]] = af_mem[k * kExactBlock];
+                A.af_anti_host[id[k]] = af_anti[k * kExactBlock];
+            }
+        // (every pod that moved the zone table ended with a barrier: the copy is complete in every thread's view)
+        if (g == 0) {
+            for (int d = tid; d < A.af_D; d += kExactBlock) {
+                A.af_zone[2 * d] = zone[d].member;
+                A.af_zone[2 * d + 1] = zone[d].anti;
+            }
+            if (tid == 0) { A.af_any[0] = any_host; A.af_any[1] = any_zone; }
+        }
+    }
     if constexpr (SPREAD) {
         // (every pod that moved the table ended with a barrier: the copy is complete in every thread's view)
         if (g == 0) {
@@ -478,6 +620,7 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
     }
 }
 
+#if KSCHED_EXACT_PART == 0
 // ------------------------------------------------------------------------------------------------
 // Exact mode on ONE workgroup (kExact1Block threads; n <= kExact1Block * NPT): every node lives in a register
 // slot of this workgroup, so a pod is decided with one workgroup barrier and no cross-workgroup exchange (k_exact
@@ -621,6 +764,8 @@ __global__ __launch_bounds__(BS) void k_exact1(ExactArgs A) {
         if (id[k] != kNoIdx) set_node(A.nodes + id[k], a0[k], a1[k], a2[k]);
 }
 
+#endif  // KSCHED_EXACT_PART == 0
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
@@ -632,8 +777,13 @@ hipError_t exact_one(const ExactArgs &a, int block, bool coop, hipStream_t s) {
     auto fn = k_exact<NPT, PRIO, DOM, LAB, F53, RUN>;
     // EXT: the workgroup's slots of every column (ext_table), at most kExtMax * 256 * 8 * 8 B = 64 KiB (kRunAll without
     // a table: n_ext == 0, none)
-    const size_t lds = EXT ? (size_t)a.n_ext * kExactBlock * NPT * sizeof(int64_t) : 0;
-    if (EXT && block != kExactBlock) return hipErrorInvalidValue;
+    // AFF: the workgroup's slots of node_member and node_anti_host and their domains (aff_table), at most 256 * 8 * 20 B
+    // = 40 KiB beside the 16 KiB static zone table
+    constexpr bool AFF = RUN == kRunAffinity;
+    const size_t lds = EXT   ? (size_t)a.n_ext * kExactBlock * NPT * sizeof(int64_t)
+                       : AFF ? (size_t)kExactBlock * NPT * (2 * sizeof(uint64_t) + sizeof(int32_t))
+                             : 0;
+    if ((EXT || AFF) && block != kExactBlock) return hipErrorInvalidValue;
     if (coop && a.G > 1) {
         ExactArgs copy = a;
         void *args[] = {&copy};
@@ -654,6 +804,7 @@ hipError_t exact_npt(int npt, const ExactArgs &a, int block, bool coop, hipStrea
     }
 }
 
+#if KSCHED_EXACT_PART == 0
 template <int PRIO, int DOM, bool LAB, bool F53>
 hipError_t exact_run(ExactRun run, int npt, const ExactArgs &a, int block, bool coop, hipStream_t s) {
     switch (run) {
@@ -662,6 +813,7 @@ hipError_t exact_run(ExactRun run, int npt, const ExactArgs &a, int block, bool 
         case kRunSpread: return exact_npt<PRIO, DOM, LAB, F53, kRunSpread>(npt, a, block, coop, s);
         case kRunExt: return exact_npt<PRIO, DOM, LAB, F53, kRunExt>(npt, a, block, coop, s);
         case kRunAll: return exact_npt<PRIO, DOM, LAB, F53, kRunAll>(npt, a, block, coop, s);
+        case kRunAffinity: break;  // (part 1: launch_exact_affinity)
     }
     return hipErrorInvalidValue;
 }
@@ -700,9 +852,11 @@ hipError_t exact1_npt(int npt, int bs, const ExactArgs &a, hipStream_t s) {
     }
     return hipErrorInvalidValue;
 }
+#endif  // KSCHED_EXACT_PART == 0
 
 }  // namespace
 
+#if KSCHED_EXACT_PART == 0
 hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block,
                         bool coop, hipStream_t s) {
     switch (run) {  // the extension's fields of ExactArgs
@@ -725,6 +879,11 @@ hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool
                 return hipErrorInvalidValue;
             if (a.n_ext != 0 && (!a.ext || !a.ext_req || a.n_ext < 1 || a.n_ext > kExtMax)) return hipErrorInvalidValue;
             break;
+        case kRunAffinity:
+            if (!a.af_dom || !a.af_member || !a.af_anti_host || !a.af_anti_zone || !a.af_zone || !a.af_any || !a.af_word ||
+                !a.af_pod || a.af_D < 0 || a.af_D > kSpreadMaxDomains)
+                return hipErrorInvalidValue;
+            return launch_exact_affinity(npt, prio, dom, lab, f53, a, block, coop, s);
         default: return hipErrorInvalidValue;
     }
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact_run<P_, D_, L_, F_>(run, npt, a, block, coop, s)));
@@ -733,5 +892,11 @@ hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool
 hipError_t launch_exact1(int npt, int bs, int prio, int dom, bool lab, bool f53, const ExactArgs &a, hipStream_t s) {
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact1_npt<P_, D_, L_, F_>(npt, bs, a, s)));
 }
+#else
+hipError_t launch_exact_affinity(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
+                                 hipStream_t s) {
+    KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, kRunAffinity>(npt, a, block, coop, s)));
+}
+#endif
 
 }  // namespace ksched

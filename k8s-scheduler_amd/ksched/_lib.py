@@ -37,6 +37,7 @@ GANG_MAX = 1024  # KSCHED_GANG_MAX: members of one gang
 # ksched_load_spread's caps: domains, groups, and groups * domains (the exact kernel's per-workgroup LDS table)
 SPREAD_MAX_DOMAINS, SPREAD_MAX_GROUPS, SPREAD_MAX_CELLS = 1024, 64, 4096
 EXT_MAX = 4  # KSCHED_EXT_MAX: extended-resource columns of ksched_load_ext's table
+AFF_MAX_GROUPS = 64  # KSCHED_AFF_MAX_GROUPS: selector groups of ksched_load_affinity's table, one bit of a uint64 each
 BOUND_MAX_PER_NODE = 1024  # KSCHED_BOUND_MAX_PER_NODE: bound pods of one node in ksched_load_bound's table
 PREEMPT_NO_VICTIM_PRIO = -(1 << 31)  # KSCHED_PREEMPT_NO_VICTIM_PRIO: the key's max priority without a victim
 XCHG_HANDLE_BYTES = 128
@@ -126,6 +127,10 @@ SIGNATURES = [
     ("ksched_schedule_ext", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, I64P, I32P, F64P, I32P]),
     ("ksched_schedule_constrained", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, C.c_int64, I64P, I32P, I32P, U8P,
                                               I64P, I32P, F64P, I32P, I32P]),
+    ("ksched_load_affinity", C.c_int, [CTX, C.c_int32, I32P, U64P, U64P, U64P]),
+    ("ksched_read_affinity", C.c_int, [CTX, U64P, U64P, U64P]),
+    ("ksched_schedule_affinity", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, U64P, U64P, U64P, I32P, U8P, I32P,
+                                           F64P, I32P]),
     ("ksched_upload_pods", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P]),
     ("ksched_run", C.c_int, [CTX]),
     ("ksched_sync", C.c_int, [CTX]),

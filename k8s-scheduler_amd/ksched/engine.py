@@ -311,7 +311,7 @@ class Engine:
         return self.results()
 
     def _schedule_with(self, name, req_cpu, req_mem, req_pods, selector, extra, tail=()):
-        """What schedule_gangs / schedule_spread / schedule_ext / schedule_constrained share: the contiguous request arrays and their length
+        """What schedule_gangs / schedule_spread / schedule_ext / schedule_constrained / schedule_affinity share: the contiguous request arrays and their length
         check, the three outputs, the call of ksched_<name> -- extra(p), the extension's arguments (checked against
         the pod count), go between the selectors and the outputs, tail after them -- and self.p.  Returns (idx,
         score, feasible)."""
@@ -437,6 +437,49 @@ class Engine:
                     L.ptr(re_, C.c_int64))
         return self._schedule_with("schedule_constrained", req_cpu, req_mem, req_pods, selector, extra,
                                    (L.ptr(gp, C.c_int32),)) + (gp,)
+
+    def load_affinity(self, node_domain=None, node_member=None, node_anti_host=None, node_anti_zone=None, n_domains=None):
+        """The affinity table of schedule_affinity() (ksched_load_affinity): node j lies in zone node_domain[j] (-1: it
+        does not carry the zone key; the ids must be compact; None: there is no zone key), and of the pods bound on it
+        node_member[j] has bit s where one belongs to selector group s, node_anti_host[j] / node_anti_zone[j] where one
+        carries a required anti-affinity term against group s at host / zone scope (uint64[n]; None: zeros).  The words
+        then live in the engine and gain bits with every schedule_affinity(); load_nodes() invalidates the table,
+        apply_delta() and restore_state() leave it alone.  n_domains: the number of zones where the largest id does
+        not say it."""
+        n = max(self.n, 0)
+        nd = None if node_domain is None else np.ascontiguousarray(node_domain, dtype=np.int32)
+        assert nd is None or nd.shape == (n,)
+        if n_domains is None:
+            n_domains = 0 if nd is None or not nd.size else int(nd.max()) + 1
+        masks = [None if m is None else np.ascontiguousarray(m, dtype=np.uint64)
+                 for m in (node_member, node_anti_host, node_anti_zone)]
+        assert all(m is None or m.shape == (n,) for m in masks)
+        self._chk(L.lib().ksched_load_affinity(self._ctx, int(n_domains), L.ptr(nd, C.c_int32),
+                                               *(L.ptr(m, C.c_uint64) for m in masks)), "load_affinity")
+
+    def read_affinity(self):
+        """The affinity table's node words (node_member, node_anti_host, node_anti_zone), uint64[n] each, as the last
+        schedule_affinity() (or load_affinity()) left them."""
+        out = [np.zeros(max(self.n, 0), np.uint64) for _ in range(3)]
+        self._chk(L.lib().ksched_read_affinity(self._ctx, *(L.ptr(o, C.c_uint64) for o in out)), "read_affinity")
+        return tuple(out)
+
+    def schedule_affinity(self, req_cpu, req_mem, req_pods, selector, member=None, anti_host=None, anti_zone=None,
+                          aff_group=None, aff_zone=None):
+        """schedule() under required inter-pod affinity and anti-affinity (ksched_schedule_affinity): pod i belongs to
+        the groups of member[i], refuses nodes (anti_host[i]) / zones (anti_zone[i]) that hold a pod of the named
+        groups, is refused where a bound pod's term names one of its groups, and -- aff_group[i] >= 0 -- needs a pod
+        of that group on its node (aff_zone[i] == 0) or in its zone, unless it is the first of its own group.  uint64[p]
+        masks, int32[p] group, uint8[p] scope; None: zeros (no group).  One launch of the exact kernel, whatever the
+        engine's mode.  Returns (idx, score, feasible)."""
+        masks = [None if m is None else np.ascontiguousarray(m, dtype=np.uint64) for m in (member, anti_host, anti_zone)]
+        ag = None if aff_group is None else np.ascontiguousarray(aff_group, dtype=np.int32)
+        az = None if aff_zone is None else np.ascontiguousarray(np.asarray(aff_zone) != 0, dtype=np.uint8)
+
+        def extra(p):
+            assert all(m is None or m.shape == (p,) for m in masks + [ag, az])
+            return tuple(L.ptr(m, C.c_uint64) for m in masks) + (L.ptr(ag, C.c_int32), L.ptr(az, C.c_uint8))
+        return self._schedule_with("schedule_affinity", req_cpu, req_mem, req_pods, selector, extra)
 
 
 def engine_for(cl, mode: Optional[int] = None, **kw) -> Engine:

@@ -56,6 +56,17 @@ class SpreadConstraint:
         return all(labels.get(k) == v for k, v in self.match_labels)
 
 
+@dataclasses.dataclass(frozen=True)
+class AffinityTerm:
+    """One requiredDuringSchedulingIgnoredDuringExecution entry of spec.affinity.podAffinity / podAntiAffinity (build
+    extension)."""
+    topology_key: str
+    match_labels: tuple  # labelSelector.matchLabels as sorted (key, value) pairs
+
+    def matches(self, labels: Dict[str, str]) -> bool:
+        return all(labels.get(k) == v for k, v in self.match_labels)
+
+
 @dataclasses.dataclass
 class Pod:
     name: str
@@ -67,6 +78,8 @@ class Pod:
     priority: int = 0  # spec.priority (preemption; build extension, the reference knows no priorities)
     labels: Dict[str, str] = dataclasses.field(default_factory=dict)  # metadata.labels (topology spread groups)
     spread: Optional[SpreadConstraint] = None  # the first DoNotSchedule entry of spec.topologySpreadConstraints
+    affinity: tuple = ()       # spec.affinity.podAffinity's required terms (AffinityTerm; affinity_tables admits one)
+    anti_affinity: tuple = ()  # spec.affinity.podAntiAffinity's required terms, any number
 
 
 @dataclasses.dataclass
@@ -87,6 +100,8 @@ PRICE_ANNOTATION = "hightower.com/cost"
 # same group are bound all-or-nothing, or when at least group-min-member of them fit.
 GROUP_NAME_ANNOTATION = "scheduling.k8s.io/group-name"
 GROUP_MIN_ANNOTATION = "scheduling.k8s.io/group-min-member"
+# Inter-pod affinity's host scope: every node is its own domain of this key, whether or not it carries the label
+HOSTNAME_KEY = "kubernetes.io/hostname"
 
 
 def _as_obj(x):
@@ -134,9 +149,22 @@ def pod_from_kube(obj: dict) -> Pod:
     """One PodList item / watch event object (anchor/types.go:57-80): containers' resources.requests
     (limits are ignored, anchor/predicate.go:73-77) and spec.nodeName; spec.priority (absent: 0) for preemption;
     metadata.labels and the first DoNotSchedule entry of spec.topologySpreadConstraints (maxSkew, topologyKey,
-    labelSelector.matchLabels) for topology spread -- ScheduleAnyway entries and any further ones are ignored."""
+    labelSelector.matchLabels) for topology spread -- ScheduleAnyway entries and any further ones are ignored; and the
+    requiredDuringSchedulingIgnoredDuringExecution terms of spec.affinity.podAffinity / podAntiAffinity (topologyKey,
+    labelSelector.matchLabels) for inter-pod affinity -- preferred terms are ignored, a term with matchExpressions or
+    a namespaceSelector is a ValueError (it would otherwise match pods it must not)."""
     md = obj.get("metadata") or {}
     sp = obj.get("spec") or {}
+    terms = {}
+    for kind in ("podAffinity", "podAntiAffinity"):
+        out = []
+        for t in (((sp.get("affinity") or {}).get(kind) or {}).get("requiredDuringSchedulingIgnoredDuringExecution") or []):
+            ls = t.get("labelSelector") or {}
+            if ls.get("matchExpressions") or t.get("namespaceSelector"):
+                raise ValueError(f"pod ({md.get('name', '')}): {kind} terms support labelSelector.matchLabels only")
+            out.append(AffinityTerm(topology_key=t.get("topologyKey", ""),
+                                    match_labels=tuple(sorted((ls.get("matchLabels") or {}).items()))))
+        terms[kind] = tuple(out)
     spread = None
     for tc in (sp.get("topologySpreadConstraints") or []):
         if tc.get("whenUnsatisfiable", "DoNotSchedule") == "DoNotSchedule":
@@ -149,7 +177,8 @@ def pod_from_kube(obj: dict) -> Pod:
     return Pod(name=md.get("name", ""), containers=conts, node_name=sp.get("nodeName") or "",
                annotations=dict(md.get("annotations") or {}), uid=md.get("uid", ""),
                node_selector=dict(sp.get("nodeSelector") or {}), priority=int(sp.get("priority") or 0),
-               labels=dict(md.get("labels") or {}), spread=spread)
+               labels=dict(md.get("labels") or {}), spread=spread, affinity=terms["podAffinity"],
+               anti_affinity=terms["podAntiAffinity"])
 
 
 def _strv(items):
@@ -292,6 +321,74 @@ def spread_tables(nodes: List[Node], bound: List[Pod], pending: List[Pod]):
         else:
             group[i] = next((s for s, c in enumerate(cons) if c.matches(pod.labels)), -1)
     return node_domain, np.asarray([c.max_skew for c in cons], np.int32), counts, group, enforce
+
+
+def affinity_tables(nodes: List[Node], bound: List[Pod], pending: List[Pod]):
+    """The inputs of ksched_load_affinity / ksched_schedule_affinity from Kubernetes objects.  A term's topologyKey is
+    HOSTNAME_KEY (host scope) or the one zone key -- the only other key the bound and pending pods' terms name
+    (ValueError on a second); zone ids are compacted over the values the nodes carry for it, in node order (a node
+    without the label, or no zone key at all: -1).  The group vocabulary is the distinct selectors of the pending pods'
+    terms and then of the bound pods' anti-affinity terms, in that order, at most AFF_MAX_GROUPS (ValueError beyond); a
+    pod belongs to every group whose selector matches its labels.  The node words are the ORs over the bound pods of a
+    node: their groups, and the groups their anti-affinity terms name per scope.  A pending pod may carry one affinity
+    term (ValueError on a second) and any number of anti-affinity terms.  Returns (node_domain int32[n], node_member,
+    node_anti_host, node_anti_zone uint64[n], member, anti_host, anti_zone uint64[p], aff_group int32[p], aff_zone
+    uint8[p])."""
+    keys = []
+    for pod in pending + bound:
+        for t in (pod.affinity if not pod.node_name else ()) + pod.anti_affinity:
+            if t.topology_key != HOSTNAME_KEY and t.topology_key not in keys:
+                keys.append(t.topology_key)
+    if len(keys) > 1 or "" in keys:
+        raise ValueError(f"inter-pod affinity: a topologyKey is {HOSTNAME_KEY} or one zone key, the pods name {keys}")
+    n, p = len(nodes), len(pending)
+    node_domain = np.full(n, -1, np.int32)
+    if keys:
+        ids: Dict[str, int] = {}
+        for j, nd in enumerate(nodes):
+            v = nd.label_map.get(keys[0])
+            if v is not None:
+                node_domain[j] = ids.setdefault(v, len(ids))
+    groups: Dict[tuple, int] = {}
+    for pod in pending:
+        if len(pod.affinity) > 1:
+            raise ValueError(f"inter-pod affinity: pod ({pod.name}) carries {len(pod.affinity)} required affinity terms, one is supported")
+        for t in pod.affinity + pod.anti_affinity:
+            groups.setdefault(t.match_labels, len(groups))
+    for pod in bound:
+        for t in pod.anti_affinity:
+            groups.setdefault(t.match_labels, len(groups))
+    if len(groups) > L.AFF_MAX_GROUPS:
+        raise ValueError(f"inter-pod affinity: {len(groups)} distinct selectors, at most {L.AFF_MAX_GROUPS} per call")
+
+    def words(pod):
+        member = anti_host = anti_zone = 0
+        for ml, s in groups.items():
+            if all(pod.labels.get(k) == v for k, v in ml):
+                member |= 1 << s
+        for t in pod.anti_affinity:
+            if t.topology_key == HOSTNAME_KEY:
+                anti_host |= 1 << groups[t.match_labels]
+            else:
+                anti_zone |= 1 << groups[t.match_labels]
+        return member, anti_host, anti_zone
+
+    node_words = np.zeros((3, n), np.uint64)
+    by_name = {nd.name: j for j, nd in enumerate(nodes)}
+    for pod in bound:
+        j = by_name.get(pod.node_name)
+        if j is not None:
+            node_words[:, j] |= np.array(words(pod), np.uint64)
+    pod_words = np.zeros((3, p), np.uint64)
+    aff_group = np.full(p, -1, np.int32)
+    aff_zone = np.zeros(p, np.uint8)
+    for i, pod in enumerate(pending):
+        pod_words[:, i] = np.array(words(pod), np.uint64)
+        if pod.affinity:
+            aff_group[i] = groups[pod.affinity[0].match_labels]
+            aff_zone[i] = pod.affinity[0].topology_key != HOSTNAME_KEY
+    return (node_domain, node_words[0].copy(), node_words[1].copy(), node_words[2].copy(), pod_words[0].copy(),
+            pod_words[1].copy(), pod_words[2].copy(), aff_group, aff_zone)
 
 
 CORE_RESOURCES = ("cpu", "memory", "pods")
@@ -582,6 +679,20 @@ class FakeCluster:
         rc, rm, rp = pack_pods(pending)
         sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
         idx, _, _ = self.engine.schedule_spread(rc, rm, rp, sel, group, enforce)
+        return self._resolve(pending, idx)
+
+    def schedule_affinity(self, pending: Optional[List[Pod]] = None):
+        """schedule_pods under the pods' required inter-pod affinity and anti-affinity terms (affinity_tables;
+        ksched_schedule_affinity): the affinity table is reloaded from self.pods' bound pods on every call, then one
+        engine call resolves every pending pod in order and the binds follow.  Returns (pod, node | Exception); a pod
+        that fits nowhere its terms allow gets the usual FailedScheduling event (without per-node lines: the explain
+        calls know no affinity reason)."""
+        pending = self.unscheduled_pods() if pending is None else pending
+        t = affinity_tables(self.nodes, [p for p in self.pods if p.node_name], pending)
+        self.engine.load_affinity(*t[:4])
+        rc, rm, rp = pack_pods(pending)
+        sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
+        idx, _, _ = self.engine.schedule_affinity(rc, rm, rp, sel, *t[4:])
         return self._resolve(pending, idx)
 
     def schedule_ext(self, pending: Optional[List[Pod]] = None):
