@@ -578,8 +578,8 @@ int ksched_schedule_constrained(ksched_ctx *ctx, int64_t p,
  * domain outside [-1, D), a domain id in [0, D) that no node carries, node_domain == NULL with D > 0 and n > 0,
  * aff_group[i] outside [-1, 64), p outside [0, 2^30), opts.nranks > 1.
  *
- * Out of scope: affinity inside ksched_schedule_constrained and the gang rollback (the words only gain bits, so an undo
- * needs a snapshot of the touched words); preferred (scored) terms; more than one affinity term per pod; more than one
+ * Out of scope: affinity inside ksched_schedule_constrained (with gangs, spread and ext and the gang rollback:
+ * ksched_schedule_full below); preferred (scored) terms; more than one affinity term per pod; more than one
  * zone key; namespaceSelector, matchLabelKeys; pod removal without a reload; affinity reasons in the explain calls;
  * ksched_rank and ksched_preempt under affinity; the batched pipelines and multi-rank; the one-workgroup exact kernel.
  *
@@ -612,6 +612,83 @@ int ksched_schedule_affinity(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu,
                              const uint64_t *anti_zone /* p, or NULL */, const int32_t *aff_group /* p, or NULL */,
                              const uint8_t *aff_zone /* p, or NULL = host */,
                              int32_t *out_idx, double *out_score, int32_t *out_feasible);
+
+/* ---- gangs, spread, extended resources and affinity together (added within ABI 6: probe with dlsym(lib, "ksched_schedule_full"); the version number did not move) ----
+ * ksched_schedule_constrained and ksched_schedule_affinity in ONE launch of the exact kernel whatever opts.mode says
+ * (stats.pipeline == KSCHED_PIPE_EXACT, stats.pair_evals == p * n).  A distributed training job is a gang whose workers
+ * each ask for amd.com/gpu, refuse to share a host (podAntiAffinity on hostname) and want to sit in one zone (self-affine
+ * podAffinity): the two calls cannot be chained, because a gang that ksched_schedule_affinity would have refused has
+ * already committed.  The arguments are flat (the cgo rule at the top of this file).
+ *
+ * Each constraint is on or off for the whole call:
+ *   gang_off, spread_group, req_ext   exactly as in ksched_schedule_constrained.
+ *   affinity      on when at least one of member, anti_host, anti_zone, aff_group, aff_zone is non-NULL; the others then
+ *                 mean zeros (-1 for aff_group), as in ksched_schedule_affinity.  On: a table from ksched_load_affinity
+ *                 must be loaded (KSCHED_E_STATE otherwise).  Off (all five NULL): no table is needed, a loaded one is
+ *                 neither read nor moved.
+ *
+ * Per pod i, in order:
+ *   eligible(i, j) = fits(i, j) && spread_ok(i, j) && ext_ok(i, j) && affinity_ok(i, j)
+ * fits, spread_ok and ext_ok are ksched_schedule_constrained's; affinity_ok is the three clauses of
+ * ksched_schedule_affinity, the waiver included (true for a pod without group or term).  Everything else is
+ * ksched_schedule in exact mode with eligible in the place of fits, exactly as those calls word it: out_feasible counts
+ * eligible nodes, zero eligible nodes is KSCHED_NO_FIT, the key and the tie-break are unchanged, and under
+ * KSCHED_DOMAIN_ALL an ineligible node can still win the argmax.
+ *
+ * A pod placed on w commits the node row, the ext columns and the spread count as in ksched_schedule_constrained, and the
+ * affinity words as in ksched_schedule_affinity: node_member[w], node_anti_host[w], node_anti_zone[w], any_host and,
+ * where the affinity table's node_domain[w] >= 0, zone_member, zone_anti and any_zone.  Within a gang all four kinds of
+ * commit are tentative, and later members of the same gang see all four.  At the end of gang g, placed >= gang_min[g]
+ * decides as in ksched_schedule_gangs:
+ *   accepted: all four stand.
+ *   rejected: all four are undone.  Beside what ksched_schedule_constrained promises, the three node arrays that
+ *     ksched_read_affinity returns are bit-identical to their values before the gang's first member, and so are the
+ *     derived zone and any words the context keeps: a waiver that a rejected gang spent is available again.  Out codes and
+ *     out_gang_placed are ksched_schedule_gangs'.
+ *
+ * Separate zone keys: the spread table's node_domain and the affinity table's node_domain are two independent arrays; the
+ * keys, and the number of domains, may differ.
+ *
+ * State: the spread counts, the ext table and the affinity words carry over from call to call, as with the single calls;
+ * ksched_read_spread / ksched_read_ext / ksched_read_affinity return them.  Afterwards ksched_explain_batch /
+ * ksched_explain_pod return KSCHED_E_STATE.
+ *
+ * KSCHED_E_INVALID (nothing changed; loaded tables survive): every invalid case of the four calls -- gang_off == NULL
+ * with n_gangs != 0, p outside [0, 2^30), aff_group[i] outside [-1, 64), opts.nranks > 1 among them.
+ *
+ * Limits: the single calls' (KSCHED_GANG_MAX, KSCHED_SPREAD_MAX_*, KSCHED_EXT_MAX, KSCHED_AFF_MAX_GROUPS), and the exact
+ * kernel's geometry unchanged: up to 2048 nodes per workgroup with every table on.  A rejected gang's undo log of the
+ * affinity words lives in device memory the context owns (24 KiB, and 16 KiB per workgroup).
+ *
+ * Equivalences: with affinity off the call is ksched_schedule_constrained, with only affinity on it is
+ * ksched_schedule_affinity, output for output and state for state.
+ *
+ * Worked example (best-price, feasible domain, ample cpu and memory): nodes n0 (zone A, price 0.1, gpu 1), n1 (A, 0.2,
+ * gpu 1), n2 (B, 0.3, gpu 1), n3 (B, 0.4, gpu 0); both tables use the same zones.  Spread: one group, max_skew 1, counts
+ * 0; p0-p4 are in it and only count (enforce 0), p5 is in it and enforces.  Affinity: group train = bit 0, an empty table.
+ * Gangs {p0, p1, p2}, {p3, p4}, {p5}, every member required.  p0-p4: member train, anti_host train, affinity train at zone
+ * scope, gpu 1.  p5: no words, gpu 0.
+ *   pod  eligible  outcome  why
+ *   p0   3         n0       waived: no train anywhere
+ *   p1   1         n1       train is now in zone A only, and n0 refuses it
+ *   p2   0         NO_FIT   zone A's hosts are both taken
+ * Gang 0 is rejected: p0 and p1 become KSCHED_GANG_REJECTED; the rows, the gpus, the counts (A 2 -> 0) and every affinity
+ * word go back.
+ *   p3   3         n0       waived AGAIN -- with any_zone left set it would find no node, with the node words left set
+ *                           n0 and n1 would refuse it
+ *   p4   1         n1       as p1
+ *   p5   2         n2       zone A would make the skew 3
+ * out_idx = {-3, -3, -1, 0, 1, 2}, out_feasible = {3, 1, 0, 3, 1, 2}, out_gang_placed = {0, 2, 1}, final counts A 2, B 1,
+ * final gpu column {0, 0, 1, 0}, node_member = node_anti_host = {1, 1, 0, 0}, node_anti_zone all 0. */
+int ksched_schedule_full(ksched_ctx *ctx, int64_t p,
+        const int64_t *req_cpu, const int64_t *req_mem, const int64_t *req_pods, const uint64_t *selector,
+        int64_t n_gangs, const int64_t *gang_off /* n_gangs + 1, or NULL */, const int32_t *gang_min /* or NULL */,
+        const int32_t *spread_group /* p, or NULL */, const uint8_t *spread_enforce /* p, or NULL */,
+        const int64_t *req_ext /* n_ext * p, or NULL */,
+        const uint64_t *member /* p, or NULL */, const uint64_t *anti_host /* p, or NULL */,
+        const uint64_t *anti_zone /* p, or NULL */, const int32_t *aff_group /* p, or NULL */,
+        const uint8_t *aff_zone /* p, or NULL = host */,
+        int32_t *out_idx, double *out_score, int32_t *out_feasible, int32_t *out_gang_placed);
 
 /* Same, in two halves, with the pods staged in HBM: upload once, run many times (bench). */
 int ksched_upload_pods(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,

@@ -1,7 +1,8 @@
 // ksched_constraints.hip -- libksched: the extensions of exact mode above the kernel.  The schedule calls
-// (ksched_schedule_gangs / _spread / _ext, ksched_schedule_constrained for the three in one run, and
-// ksched_schedule_affinity) check and pack on the host, stage what they packed and run k_exact with their extension
-// (ExactRun, ksched_exact.h); the table calls load and read the context's spread, extended-resource and affinity tables.
+// (ksched_schedule_gangs / _spread / _ext, ksched_schedule_constrained for the three in one run,
+// ksched_schedule_affinity, and ksched_schedule_full for all four in one run) check and pack on the host, stage what
+// they packed and run k_exact with their extension (ExactRun, ksched_exact.h); the table calls load and read
+// the context's spread, extended-resource and affinity tables.
 #include <cstring>
 
 #include <new>
@@ -10,6 +11,7 @@
 #include "ksched_affinity.h"
 #include "ksched_ctx.h"
 #include "ksched_ext.h"
+#include "ksched_full.h"
 #include "ksched_gang.h"
 #include "ksched_spread.h"
 
@@ -330,6 +332,49 @@ int ksched_schedule_affinity(ksched_ctx *c, int64_t p, const int64_t *rc, const 
     // the run's final any words, for the next call's arguments (the sync above is behind the kernel that wrote them)
     HIPCHK(c, hipMemcpy(c->aff_any, c->d->aany, sizeof(c->aff_any), hipMemcpyDeviceToHost));
     return KSCHED_OK;
+}
+
+// ksched_schedule_constrained and ksched_schedule_affinity in one run of k_exact<kRunFull>.  A constraint whose
+// argument is NULL (affinity: all five) is off for the whole call: its per-pod words say so and the kernel is not given
+// its table.  Every check of the four calls runs, through their own checkers and packers (ksched_full.h), before anything
+// is staged.
+int ksched_schedule_full(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                         const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
+                         const int32_t *spread_group, const uint8_t *spread_enforce, const int64_t *req_ext,
+                         const uint64_t *member, const uint64_t *anti_host, const uint64_t *anti_zone,
+                         const int32_t *aff_group, const uint8_t *aff_zone, int32_t *oi, double *os, int32_t *of,
+                         int32_t *out_gang_placed) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_full before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_full is single-GPU (the exact kernel)");
+    // every argument is checked, and every per-pod word is packed, before anything is written or allocated (ksched_full.h)
+    const FullArgs args{p, n_gangs, gang_off, gang_min, spread_group, spread_enforce, req_ext, member, anti_host, anti_zone,
+                        aff_group, aff_zone};
+    FullPacked k;
+    try {
+        const char *why = nullptr;
+        if (const int code = full_check_pack(args, c->spread_S, c->ext_R, c->aff_valid, &k, &why))
+            return fail(c, code, std::string("schedule_full: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "schedule_full: host staging buffer");
+    }
+    const size_t ng = k.n_gangs;
+    const bool aff = k.aff;
+    c->all_spread = k.spread;
+    c->all_ext = k.ext;
+    c->all_aff = k.aff;
+    const int r = schedule_staged(c, kRunFull, "schedule_full", p, rc, rm, rp, sel, oi, os, of,
+                                  Staged<int32_t>{c->d->gend, k.gend.data(), (size_t)p * 4},
+                                  Staged<int32_t>{c->d->gplaced, nullptr, ng * 4},
+                                  Staged<int32_t>{c->d->sword, k.swords.data(), (size_t)p * 4},
+                                  Staged<int64_t>{c->d->ereq, k.reqs.data(), k.reqs.size() * 8},
+                                  Staged<int32_t>{c->d->eword, k.ewords.data(), (size_t)p * 4},
+                                  Staged<int32_t>{c->d->aword, k.awords.data(), (size_t)p * 4},
+                                  Staged<uint64_t>{c->d->apod, k.apods.data(), k.apods.size() * 8});
+    if (r != KSCHED_OK) return r;
+    // the run's final any words, for the next call's arguments (no pods: no launch, the any words stand)
+    if (aff && p > 0) HIPCHK(c, hipMemcpy(c->aff_any, c->d->aany, sizeof(c->aff_any), hipMemcpyDeviceToHost));
+    return gang_results(c, ng, gang_off ? out_gang_placed : nullptr);
 }
 
 }  // extern "C"

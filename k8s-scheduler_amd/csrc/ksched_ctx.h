@@ -115,6 +115,8 @@ struct ksched_bufs {
     DevBuf<uint64_t> azone, aany;         // ... {zone_member, zone_anti} per domain; the run's final {any_host, any_zone}
     DevBuf<int32_t> aword;                // ksched_schedule_affinity: ExactArgs::af_word per pod
     DevBuf<uint64_t> apod;                // ... ExactArgs::af_pod, kAffWords per pod
+    DevBuf<uint64_t> aundo;               // ksched_schedule_full: a rejected gang's undo log of the affinity words,
+                                          // ExactArgs::af_undo_slot [kGangMax][3], then af_undo_zone [G][kGangMax][2]
     DevBuf<void> xws, xbuf;               // explain: workspace; counts + NO_FIT pod list, or one pod's state + counts
     DevBuf<void> rws;                     // ksched_rank: one chunk's pods, span lists and outputs (rank_geometry's bound)
     DevBuf<int64_t> bcpu, bmem, boff;     // ksched_load_bound: the bound-pod table (BoundTable, ksched_preempt.h)
@@ -212,6 +214,7 @@ struct ksched_ctx {
     int32_t aff_D = 0;           // ... its zone domains (0: no zone key)
     uint64_t aff_any[2] = {};    // ... any_host, any_zone: into every affinity run by value, back from d->aany behind it
     bool all_spread = false, all_ext = false;  // ksched_schedule_constrained: the tables its kRunAll launch is given
+    bool all_aff = false;        // ksched_schedule_full: its kRunFull launch is given the affinity table (with the two above)
     // pods
     int64_t p = 0;
     // batched workspace

@@ -467,7 +467,7 @@ int enqueue_persistent(ksched_ctx *c) {
 }
 
 // run (ExactRun, ksched_exact.h): a plain exact run, or the run of ksched_schedule_gangs / _spread / _ext /
-// _constrained / _affinity over what that call staged -- always k_exact, the multi-slot kernel, under the same geometry and launch
+// _constrained / _affinity / _full over what that call staged -- always k_exact, the multi-slot kernel, under the same geometry and launch
 // rule as a plain run
 int enqueue_exact(ksched_ctx *c, ExactRun run) {
     if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "exact mode is single-GPU; use batched mode across ranks");
@@ -514,6 +514,10 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
         return fail(c, KSCHED_E_INVALID, "exact mode: too many nodes per workgroup (raise exact_wgs)");
     if (G > c->cus) return fail(c, KSCHED_E_INVALID, "exact mode: more workgroups than CUs");
     HIPCHK(c, c->d->slots.reserve((size_t)2 * G * 4 * sizeof(uint64_t)));
+    // kRunFull: a rejected gang's undo log of the affinity words -- one slot record per member, one zone record per
+    // workgroup and member (written before it is read: not cleared); reserved here, before the timed span begins
+    const size_t undo_slot_words = (size_t)kGangMax * 3;
+    if (run == kRunFull) HIPCHK(c, c->d->aundo.reserve((undo_slot_words + (size_t)G * kGangMax * 2) * sizeof(uint64_t)));
     HIPCHK(c, hipMemsetAsync(c->d->slots, 0, (size_t)2 * G * 4 * sizeof(uint64_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d->err, 0, sizeof(int32_t), c->stream));
     a.G = G; a.per_wg = (int32_t)per_wg; a.slots = c->d->slots;
@@ -546,6 +550,21 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
             a.af_any_host = c->aff_any[0]; a.af_any_zone = c->aff_any[1]; a.af_D = c->aff_D;
             a.af_word = c->d->aword; a.af_pod = c->d->apod;
             break;
+        case kRunFull:  // every staged word; a table only where ksched_schedule_full was given its argument; the undo log
+            a.gang_end = c->d->gend; a.gang_placed = c->d->gplaced; a.sp_word = c->d->sword; a.ext_word = c->d->eword;
+            a.af_word = c->d->aword; a.af_pod = c->d->apod;
+            if (c->all_spread) {
+                a.sp_dom = c->d->sdom; a.sp_counts = c->d->scnt; a.sp_skew = c->d->sskew;
+                a.sp_D = c->spread_D; a.sp_S = c->spread_S;
+            }
+            if (c->all_ext) { a.ext = c->d->etab; a.ext_req = c->d->ereq; a.n_ext = c->ext_R; }
+            if (c->all_aff) {
+                a.af_dom = c->d->adom; a.af_member = c->d->amem; a.af_anti_host = c->d->aanti_h;
+                a.af_anti_zone = c->d->aanti_z; a.af_zone = c->d->azone; a.af_any = c->d->aany;
+                a.af_any_host = c->aff_any[0]; a.af_any_zone = c->aff_any[1]; a.af_D = c->aff_D;
+            }
+            a.af_undo_slot = c->d->aundo; a.af_undo_zone = c->d->aundo.p + undo_slot_words;
+            break;
     }
     HIPCHK(c, launch_exact(run, npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
                            G > 1 && !c->diag.plain_launch, c->stream));
@@ -557,7 +576,7 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
 }  // namespace
 
 // ksched_run, or the run of ksched_schedule_gangs / ksched_schedule_spread / ksched_schedule_ext /
-// ksched_schedule_constrained: the exact kernel over the staged gangs / spread words / extended requests whatever opts.mode
+// ksched_schedule_constrained / ksched_schedule_affinity / ksched_schedule_full: the exact kernel over the staged gangs / spread words / extended requests whatever opts.mode
 int ksched::run_impl(ksched_ctx *c, ExactRun run) {
     if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "run before load_nodes");
     if (c->o.nranks > 1 && !c->comm && !c->group && !c->xchg_ready)

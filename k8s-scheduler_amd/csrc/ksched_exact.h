@@ -17,7 +17,9 @@ namespace ksched {
 // one).  kRunAffinity (ksched_schedule_affinity): the staged words in d->aword / d->apod and the context's affinity
 // table; it is paired with no other kind.  Every run but kRunPlain is the multi-slot kernel k_exact whatever opts.mode, under the same geometry and launch
 // rule as a plain exact run.
-enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3, kRunAll = 4, kRunAffinity = 5 };
+// kRunFull (ksched_schedule_full): kRunAll and kRunAffinity in one launch -- the staged words of both and the tables the
+// call switched on; a rejected gang also puts back the affinity words it ORed into, from the undo log in d->aundo.
+enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3, kRunAll = 4, kRunAffinity = 5, kRunFull = 6 };
 
 struct ExactArgs {
     NodeRec *nodes;
@@ -58,6 +60,13 @@ struct ExactArgs {
     const int32_t *af_word;   // per pod: 0 (no group, no term), or 1 | zone scope of its affinity term << 1; the kernel
                               // reads it with the request
     const uint64_t *af_pod;   // [p][kAffWords] member, anti_host, anti_zone, the affinity term's group bit (0: none)
+    // k_exact<kRunFull> (ksched_schedule_full): every field above (sp_S == 0, n_ext == 0 as in kRunAll; af_dom null --
+    // no affinity table, every af_word is 0) and the rejected gang's undo log of the affinity words, device memory that
+    // every thread reads back only where it wrote itself
+    uint64_t *af_undo_slot;   // [kGangMax][3] per member: its winner's node_member, node_anti_host and (where the member
+                              // has an anti_zone word) node_anti_zone before the commit -- the winner's owner lane
+    uint64_t *af_undo_zone;   // [G][kGangMax][2] per workgroup and member: {zone_member, zone_anti} of the winner's domain
+                              // before the commit -- thread 0 of the workgroup
 };
 constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
 constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
@@ -77,7 +86,9 @@ constexpr int kExact1Block = 1024;  // k_exact1: the whole node set in one workg
 // One launch of k_exact<run>.  kRunGang: a.gang_end set (a.gang_placed may be null); kRunSpread: a.sp_* set; kRunExt:
 // a.ext* set, dynamic LDS of a.n_ext * block * npt * 8 bytes; kRunAll: a.gang_end, a.sp_word and a.ext_word set, the
 // spread table's fields set or sp_S == 0, the extended-resource table's set or n_ext == 0; kRunAffinity: a.af_* set,
-// dynamic LDS of block * npt * 20 bytes (two 8-byte words and the domain of every slot).  (An extension never runs
+// dynamic LDS of block * npt * 20 bytes (two 8-byte words and the domain of every slot); kRunFull: kRunAll's fields, and
+// kRunAffinity's set or a.af_dom null, with a.af_undo_* set, dynamic LDS of both (the affinity words behind the columns:
+// above 64 KiB, so the launcher raises the kernel's limit first).  (An extension never runs
 // k_exact1: the one-workgroup kernel knows no gang log and no spread, extended-resource or affinity table.)
 hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
                         bool cooperative, hipStream_t s);

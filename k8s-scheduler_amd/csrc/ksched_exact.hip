@@ -2,11 +2,15 @@
 // extended resources -- each alone, or all three composed -- and inter-pod affinity, alone), the one-workgroup k_exact1,
 // and their launchers.
 // Compiled with -ffp-contract=off: every double op rounds individually, exactly like the Go reference.
-// Two objects, as ksched_pipe.hip's three (-DKSCHED_EXACT_PART): part 0 is every kind but affinity, k_exact1 and the
-// launchers; part 1 is the affinity kind's 40 instantiations behind launch_exact_affinity.
+// Three objects, as ksched_pipe.hip's three (-DKSCHED_EXACT_PART): part 0 is every kind but affinity and full, k_exact1
+// and the launchers; part 1 is the affinity kind's 40 instantiations behind launch_exact_affinity; part 2 the full
+// kind's (gangs, spread, extended resources and affinity composed) behind launch_exact_full.
 #include <hip/hip_runtime.h>
 
+#include <mutex>
+#include <set>
 #include <type_traits>
+#include <utility>
 
 #include "ksched_exact.h"
 #include "ksched_kernels.h"  // KSCHED_DISPATCH, kErrExactExchange
@@ -19,6 +23,8 @@ namespace ksched {
 
 hipError_t launch_exact_affinity(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
                                  hipStream_t s);  // part 1
+hipError_t launch_exact_full(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
+                             hipStream_t s);  // part 2
 
 namespace {
 
@@ -179,10 +185,23 @@ __device__ __forceinline__ uint64_t *aff_table() {
 //   exchange, no wait, the tag and parity sequence unchanged.  The next pod's gathers read the zone table before its
 //   first barrier, so a pod that may have moved it ends with one barrier; its condition -- placed, the winner's domain
 //   >= 0, (member | anti_zone) != 0 -- is made of uniform inputs only, never of the LDS words thread 0 is writing.
+// FULL (ksched_schedule_full): ALL and AFF together.  Affinity too is switched off by a uniform
+//   runtime value (af_dom null: no table is loaded or written back, no affinity slot words in LDS, every af_word is 0);
+//   the affinity slot words lie behind the n_ext columns of the dynamic region.  The affinity words only gain bits, so a
+//   rejected gang restores old values from a log in device memory (the LDS is full): at a logging member's commit the
+//   winner's owner lane writes its slot's node_member, node_anti_host and -- where it is about to OR into it --
+//   node_anti_zone to af_undo_slot[member], and thread 0 of every workgroup writes its copy of the winner's zone words to
+//   af_undo_zone[workgroup][member], both BEFORE the OR; every thread keeps the any words of the gang's first member in
+//   registers.  A gang of one never rolls a commit back and logs nothing.  The walk runs newest member first, so a slot
+//   or zone hit several times ends at its oldest logged value; every thread reads back only what it wrote itself (same
+//   thread, same address: program order, no fence).  The walk's closing barrier gains one more workgroup-uniform reason:
+//   a logged member moved a zone word (its af_word, its words and its winner's domain: uniform loads from arrays nobody
+//   writes).  No exchange, no wait, the tag and parity sequence unchanged.
 // ------------------------------------------------------------------------------------------------
 template <int NPT, int PRIO, int DOM, bool LAB, bool F53, ExactRun RUN>
 __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
-    constexpr bool ALL = RUN == kRunAll, AFF = RUN == kRunAffinity;
+    constexpr bool FULL = RUN == kRunFull;
+    constexpr bool ALL = RUN == kRunAll || FULL, AFF = RUN == kRunAffinity || FULL;
     constexpr bool GANG = RUN == kRunGang || ALL, SPREAD = RUN == kRunSpread || ALL, EXT = RUN == kRunExt || ALL;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -249,24 +268,30 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
     }
     // AFF: this thread's slot k: node_member at af_mem[k * kExactBlock], node_anti_host at af_anti[k * kExactBlock], the
     // domain at af_dom[k * kExactBlock] (no other thread touches them); the zone table; the any words
-    [[maybe_unused]] uint64_t *const af_mem = AFF ? aff_table<AFF>() + tid : nullptr;
+    // FULL: behind the n_ext columns of the dynamic region; af_on false (no table): nothing is loaded, and no pod reads it
+    [[maybe_unused]] const bool af_on = FULL ? A.af_dom != nullptr : AFF;
+    [[maybe_unused]] uint64_t *const af_base = AFF ? aff_table<AFF>() + (FULL ? A.n_ext * (kExactBlock * NPT) : 0) : nullptr;
+    [[maybe_unused]] uint64_t *const af_mem = AFF ? af_base + tid : nullptr;
     [[maybe_unused]] uint64_t *const af_anti = AFF ? af_mem + kExactBlock * NPT : nullptr;
-    [[maybe_unused]] int32_t *const af_dom = AFF ? (int32_t *)(aff_table<AFF>() + 2 * kExactBlock * NPT) + tid : nullptr;
+    [[maybe_unused]] int32_t *const af_dom = AFF ? (int32_t *)(af_base + 2 * kExactBlock * NPT) + tid : nullptr;
     [[maybe_unused]] AffZone *const zone = aff_zone<AFF>();
     [[maybe_unused]] uint64_t any_host = AFF ? A.af_any_host : 0, any_zone = AFF ? A.af_any_zone : 0;
+    [[maybe_unused]] uint64_t sv_host = 0, sv_zone = 0;  // FULL: the any words before the current gang's first member
     if constexpr (AFF) {
+        if (af_on) {  // (uniform)
 #pragma unroll
-        for (int k = 0; k < NPT; ++k) {
-            const bool own = id[k] != kNoIdx;
-            af_mem[k * kExactBlock] = own ? A.af_member[id[k]] : 0;
-            af_anti[k * kExactBlock] = own ? A.af_anti_host[id[k]] : 0;
-            af_dom[k * kExactBlock] = own ? A.af_dom[id[k]] : -1;
+            for (int k = 0; k < NPT; ++k) {
+                const bool own = id[k] != kNoIdx;
+                af_mem[k * kExactBlock] = own ? A.af_member[id[k]] : 0;
+                af_anti[k * kExactBlock] = own ? A.af_anti_host[id[k]] : 0;
+                af_dom[k * kExactBlock] = own ? A.af_dom[id[k]] : -1;
+            }
+            for (int d = tid; d < A.af_D; d += kExactBlock) {
+                zone[d].member = A.af_zone[2 * d];
+                zone[d].anti = A.af_zone[2 * d + 1];
+            }
+            __syncthreads();
         }
-        for (int d = tid; d < A.af_D; d += kExactBlock) {
-            zone[d].member = A.af_zone[2 * d];
-            zone[d].anti = A.af_zone[2 * d + 1];
-        }
-        __syncthreads();
     }
 
     __shared__ double s_key[2][kExactBlock / 64];
@@ -316,6 +341,12 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
         [[maybe_unused]] const int32_t aword = AFF ? A.af_word[i] : 0;
         [[maybe_unused]] uint64_t pmem = 0, pah = 0, paz = 0, pabit = 0;
         [[maybe_unused]] bool azone = false;  // the affinity term (pabit != 0) is of zone scope
+        // FULL: this member's commits go to the undo log -- not in a gang of one, which never rolls a commit back
+        [[maybe_unused]] bool logit = false;
+        if constexpr (FULL) {
+            logit = gs.gm != 0 || gend == 0;
+            if (gs.gm == 0) { sv_host = any_host; sv_zone = any_zone; }
+        }
         if constexpr (AFF) {
             if (aword != 0) {
                 pmem = A.af_pod[i * kAffWords]; pah = A.af_pod[i * kAffWords + 1];
@@ -464,6 +495,14 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                     }
                     if constexpr (AFF) {
                         if (aword != 0) {  // the owner lane: its own slot's words; node_anti_zone is read by no test
+                            if constexpr (FULL) {
+                                if (logit) {  // the words before the OR, for this lane's own walk of a rejected gang
+                                    uint64_t *u = A.af_undo_slot + gs.gm * 3;
+                                    u[0] = af_mem[k * kExactBlock];
+                                    u[1] = af_anti[k * kExactBlock];
+                                    if (paz != 0) u[2] = A.af_anti_zone[gi];
+                                }
+                            }
                             af_mem[k * kExactBlock] |= pmem;
                             af_anti[k * kExactBlock] |= pah;
                             if (paz != 0) A.af_anti_zone[gi] |= paz;
@@ -486,7 +525,16 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                     const int32_t wd = A.af_dom[__builtin_amdgcn_readfirstlane(oidx)];
                     if (wd >= 0) {
                         any_zone |= pmem;
-                        if (tid == 0) { zone[wd].member |= pmem; zone[wd].anti |= paz; }
+                        if (tid == 0) {
+                            if constexpr (FULL) {
+                                if (logit) {  // this workgroup's copy before the OR, for thread 0's own walk
+                                    uint64_t *u = A.af_undo_zone + ((size_t)g * kGangMax + gs.gm) * 2;
+                                    u[0] = zone[wd].member;
+                                    u[1] = zone[wd].anti;
+                                }
+                            }
+                            zone[wd].member |= pmem; zone[wd].anti |= paz;
+                        }
                         __syncthreads();  // the next pod's gathers come before its first barrier
                     }
                 }
@@ -525,17 +573,38 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                     uint32_t dirty = 0;
                     [[maybe_unused]] bool moved = false;  // ALL: the walk decremented a count of the spread table
 #pragma nounroll
-                    for (int32_t m = 0; m < gsize; ++m) {
+                    for (int32_t mm = 0; mm < gsize; ++mm) {
+                        // FULL: newest first -- a word logged several times ends at its oldest value (the other undos
+                        // are sums: any order)
+                        const int32_t m = FULL ? gsize - 1 - mm : mm;
                         const int32_t li = s_log[m];
                         if (li < 0) continue;  // a member that failed keeps its own code
                         if (g == 0 && tid == 0) { A.out.idx[first + m] = kGangRejected; A.out.score[first + m] = 0.0; }
                         const int64_t urc = A.pods.rc[first + m], urm = A.pods.rm[first + m];
                         [[maybe_unused]] const int32_t uew = ALL ? A.ext_word[first + m] : 0;
+                        // FULL: the member's affinity word and, where set, its member and anti_zone words (uniform); a
+                        // rejected gang of placed members is never a gang of one, so every such member was logged
+                        [[maybe_unused]] const int32_t uaw = FULL ? A.af_word[first + m] : 0;
+                        [[maybe_unused]] uint64_t upm = 0, upz = 0;
+                        if constexpr (FULL) {
+                            if (uaw != 0) {
+                                upm = A.af_pod[(first + m) * kAffWords];
+                                upz = A.af_pod[(first + m) * kAffWords + 2];
+                            }
+                        }
 #pragma unroll
                         for (int k = 0; k < NPT; ++k) {
                             if (id[k] == li) {  // the commit's inverse: a wrapping add undoes the wrapping subtract
                                 a0[k] = wadd(a0[k], urc); a1[k] = wadd(a1[k], urm); a2[k] = wadd(a2[k], 1);
                                 dirty |= 1u << k;
+                                if constexpr (FULL) {
+                                    if (uaw != 0) {  // the owner lane: what it logged itself at this member's commit
+                                        const uint64_t *u = A.af_undo_slot + m * 3;
+                                        af_mem[k * kExactBlock] = u[0];
+                                        af_anti[k * kExactBlock] = u[1];
+                                        if (upz != 0) A.af_anti_zone[li] = u[2];
+                                    }
+                                }
                                 if constexpr (ALL) {
                                     if (uew != 0) {  // the owner lane: the member's non-zero requests back to its own words
 #pragma unroll
@@ -567,7 +636,21 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
                                 }
                             }
                         }
+                        if constexpr (FULL) {
+                            if (uaw != 0 && (upm | upz) != 0) {  // (the same in every thread, as the commit's condition was)
+                                const int32_t wd = A.af_dom[__builtin_amdgcn_readfirstlane(li)];
+                                if (wd >= 0) {
+                                    moved = true;
+                                    if (tid == 0) {  // what thread 0 logged itself at this member's commit
+                                        const uint64_t *u = A.af_undo_zone + ((size_t)g * kGangMax + m) * 2;
+                                        zone[wd].member = u[0];
+                                        zone[wd].anti = u[1];
+                                    }
+                                }
+                            }
+                        }
                     }
+                    if constexpr (FULL) { any_host = sv_host; any_zone = sv_zone; }
                     if constexpr (ALL) {
                         if (moved) __syncthreads();  // the next pod's gathers come before its first barrier
                     }
@@ -596,19 +679,22 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
         }
     }
     if constexpr (AFF) {
+        if (af_on) {
 #pragma unroll
-        for (int k = 0; k < NPT; ++k)
-            if (id[k] != kNoIdx) {
-                A.af_member[id[k]] = af_mem[k * kExactBlock];
-                A.af_anti_host[id[k]] = af_anti[k * kExactBlock];
+            for (int k = 0; k < NPT; ++k)
+                if (id[k] != kNoIdx) {
+                    A.af_member[id[k]] = af_mem[k * kExactBlock];
+                    A.af_anti_host[id[k]] = af_anti[k * kExactBlock];
+                }
+            // (every pod -- and every walk -- that moved the zone table ended with a barrier: the copy is complete in
+            // every thread's view)
+            if (g == 0) {
+                for (int d = tid; d < A.af_D; d += kExactBlock) {
+                    A.af_zone[2 * d] = zone[d].member;
+                    A.af_zone[2 * d + 1] = zone[d].anti;
+                }
+                if (tid == 0) { A.af_any[0] = any_host; A.af_any[1] = any_zone; }
             }
-        // (every pod that moved the zone table ended with a barrier: the copy is complete in every thread's view)
-        if (g == 0) {
-            for (int d = tid; d < A.af_D; d += kExactBlock) {
-                A.af_zone[2 * d] = zone[d].member;
-                A.af_zone[2 * d + 1] = zone[d].anti;
-            }
-            if (tid == 0) { A.af_any[0] = any_host; A.af_any[1] = any_zone; }
         }
     }
     if constexpr (SPREAD) {
@@ -771,19 +857,44 @@ __global__ __launch_bounds__(BS) void k_exact1(ExactArgs A) {
 // ------------------------------------------------------------------------------------------------
 namespace {
 
+// kRunFull (part 2): hipFuncAttributeMaxDynamicSharedMemorySize belongs to a kernel on ONE device, and a context chooses
+// its device: the (device ordinal, kernel) pairs that have it, set at the pair's first launch as launch_stream_kernel
+// does.  Contexts run on threads of their own.
+[[maybe_unused]] hipError_t full_lds_limit(const void *fn, size_t most) {
+    static std::mutex mu;
+    static std::set<std::pair<int, const void *>> have;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lk(mu);
+    if (have.count({dev, fn})) return hipSuccess;
+    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most);
+    if (e == hipSuccess) have.insert({dev, fn});
+    return e;
+}
+
 template <int NPT, int PRIO, int DOM, bool LAB, bool F53, ExactRun RUN>
 hipError_t exact_one(const ExactArgs &a, int block, bool coop, hipStream_t s) {
+    constexpr bool FULL = RUN == kRunFull;
     constexpr bool EXT = RUN == kRunExt || RUN == kRunAll;
     auto fn = k_exact<NPT, PRIO, DOM, LAB, F53, RUN>;
     // EXT: the workgroup's slots of every column (ext_table), at most kExtMax * 256 * 8 * 8 B = 64 KiB (kRunAll without
     // a table: n_ext == 0, none)
     // AFF: the workgroup's slots of node_member and node_anti_host and their domains (aff_table), at most 256 * 8 * 20 B
     // = 40 KiB beside the 16 KiB static zone table
+    // FULL: both, the affinity words behind the columns and only where the call has a table: up to 104 KiB, beyond the
+    // 64 KiB a kernel is admitted to by default -- so the kernel's first launch on a device raises its limit to the
+    // kind's maximum there (full_lds_limit)
     constexpr bool AFF = RUN == kRunAffinity;
-    const size_t lds = EXT   ? (size_t)a.n_ext * kExactBlock * NPT * sizeof(int64_t)
-                       : AFF ? (size_t)kExactBlock * NPT * (2 * sizeof(uint64_t) + sizeof(int32_t))
-                             : 0;
-    if ((EXT || AFF) && block != kExactBlock) return hipErrorInvalidValue;
+    constexpr size_t aff = (size_t)kExactBlock * NPT * (2 * sizeof(uint64_t) + sizeof(int32_t));
+    const size_t cols = (size_t)a.n_ext * kExactBlock * NPT * sizeof(int64_t);
+    const size_t lds = FULL ? cols + (a.af_dom ? aff : 0) : EXT ? cols : AFF ? aff : 0;
+    if ((EXT || AFF || FULL) && block != kExactBlock) return hipErrorInvalidValue;
+    if constexpr (FULL) {
+        if (a.n_ext < 0 || a.n_ext > kExtMax) return hipErrorInvalidValue;
+        const hipError_t e = full_lds_limit((const void *)fn, (size_t)kExtMax * kExactBlock * NPT * sizeof(int64_t) + aff);
+        if (e != hipSuccess) return e;
+    }
     if (coop && a.G > 1) {
         ExactArgs copy = a;
         void *args[] = {&copy};
@@ -814,6 +925,7 @@ hipError_t exact_run(ExactRun run, int npt, const ExactArgs &a, int block, bool 
         case kRunExt: return exact_npt<PRIO, DOM, LAB, F53, kRunExt>(npt, a, block, coop, s);
         case kRunAll: return exact_npt<PRIO, DOM, LAB, F53, kRunAll>(npt, a, block, coop, s);
         case kRunAffinity: break;  // (part 1: launch_exact_affinity)
+        case kRunFull: break;      // (part 2: launch_exact_full)
     }
     return hipErrorInvalidValue;
 }
@@ -884,6 +996,18 @@ hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool
                 !a.af_pod || a.af_D < 0 || a.af_D > kSpreadMaxDomains)
                 return hipErrorInvalidValue;
             return launch_exact_affinity(npt, prio, dom, lab, f53, a, block, coop, s);
+        case kRunFull:  // kRunAll's and kRunAffinity's checks, "no table" (af_dom null) accepted for affinity too
+            if (!a.gang_end || !a.sp_word || !a.ext_word || !a.af_word || !a.af_undo_slot || !a.af_undo_zone)
+                return hipErrorInvalidValue;
+            if (a.sp_S != 0 && (!a.sp_dom || !a.sp_counts || !a.sp_skew || a.sp_D < 1 || a.sp_S < 1 ||
+                                (int64_t)a.sp_D * a.sp_S > kSpreadMaxCells || a.sp_S > kSpreadMaxGroups))
+                return hipErrorInvalidValue;
+            if (a.n_ext != 0 && (!a.ext || !a.ext_req || a.n_ext < 1 || a.n_ext > kExtMax)) return hipErrorInvalidValue;
+            if (a.af_dom && (!a.af_member || !a.af_anti_host || !a.af_anti_zone || !a.af_zone || !a.af_any || !a.af_pod ||
+                             a.af_D < 0 || a.af_D > kSpreadMaxDomains))
+                return hipErrorInvalidValue;
+            if (!a.af_dom && a.af_D != 0) return hipErrorInvalidValue;
+            return launch_exact_full(npt, prio, dom, lab, f53, a, block, coop, s);
         default: return hipErrorInvalidValue;
     }
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact_run<P_, D_, L_, F_>(run, npt, a, block, coop, s)));
@@ -892,10 +1016,15 @@ hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool
 hipError_t launch_exact1(int npt, int bs, int prio, int dom, bool lab, bool f53, const ExactArgs &a, hipStream_t s) {
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact1_npt<P_, D_, L_, F_>(npt, bs, a, s)));
 }
-#else
+#elif KSCHED_EXACT_PART == 1
 hipError_t launch_exact_affinity(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
                                  hipStream_t s) {
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, kRunAffinity>(npt, a, block, coop, s)));
+}
+#else
+hipError_t launch_exact_full(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
+                             hipStream_t s) {
+    KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, kRunFull>(npt, a, block, coop, s)));
 }
 #endif
 

@@ -131,6 +131,8 @@ SIGNATURES = [
     ("ksched_read_affinity", C.c_int, [CTX, U64P, U64P, U64P]),
     ("ksched_schedule_affinity", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, U64P, U64P, U64P, I32P, U8P, I32P,
                                            F64P, I32P]),
+    ("ksched_schedule_full", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, C.c_int64, I64P, I32P, I32P, U8P, I64P,
+                                       U64P, U64P, U64P, I32P, U8P, I32P, F64P, I32P, I32P]),
     ("ksched_upload_pods", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P]),
     ("ksched_run", C.c_int, [CTX]),
     ("ksched_sync", C.c_int, [CTX]),

@@ -311,7 +311,7 @@ class Engine:
         return self.results()
 
     def _schedule_with(self, name, req_cpu, req_mem, req_pods, selector, extra, tail=()):
-        """What schedule_gangs / schedule_spread / schedule_ext / schedule_constrained / schedule_affinity share: the contiguous request arrays and their length
+        """What schedule_gangs / schedule_spread / schedule_ext / schedule_constrained / schedule_affinity / schedule_full share: the contiguous request arrays and their length
         check, the three outputs, the call of ksched_<name> -- extra(p), the extension's arguments (checked against
         the pod count), go between the selectors and the outputs, tail after them -- and self.p.  Returns (idx,
         score, feasible)."""
@@ -480,6 +480,37 @@ class Engine:
             assert all(m is None or m.shape == (p,) for m in masks + [ag, az])
             return tuple(L.ptr(m, C.c_uint64) for m in masks) + (L.ptr(ag, C.c_int32), L.ptr(az, C.c_uint8))
         return self._schedule_with("schedule_affinity", req_cpu, req_mem, req_pods, selector, extra)
+
+    def schedule_full(self, req_cpu, req_mem, req_pods, selector, gang_off=None, gang_min=None, group=None, enforce=None,
+                      req_ext=None, member=None, anti_host=None, anti_zone=None, aff_group=None, aff_zone=None):
+        """schedule_constrained() and schedule_affinity() in one launch of the exact kernel (ksched_schedule_full): a
+        pod's node must fit, satisfy its spread constraint, hold its extended requests and pass its affinity and
+        anti-affinity terms; a placed pod commits its node row, the load_ext() columns, the load_spread() count and the
+        load_affinity() words, and a rejected gang undoes all four -- the affinity words, which only ever gain bits, go
+        back to their values before the gang's first member.  gang_off, group and req_ext switch their constraint on as
+        in schedule_constrained(); affinity is on where any of its five arguments is given (None then: zeros, no
+        group).  Returns (idx, score, feasible, gang_placed); gang_placed is empty when gang_off is None."""
+        off = None if gang_off is None else _i64(gang_off)
+        ng = 0 if off is None else off.shape[0] - 1
+        gmin = None if gang_min is None or off is None else np.ascontiguousarray(gang_min, dtype=np.int32)
+        assert ng >= 0 and (gmin is None or gmin.shape[0] == ng)
+        gr = None if group is None else np.ascontiguousarray(group, dtype=np.int32)
+        en = None if enforce is None or gr is None else np.ascontiguousarray(np.asarray(enforce) != 0, dtype=np.uint8)
+        re_ = None if req_ext is None else np.ascontiguousarray(req_ext, dtype=np.int64)
+        masks = [None if m is None else np.ascontiguousarray(m, dtype=np.uint64) for m in (member, anti_host, anti_zone)]
+        ag = None if aff_group is None else np.ascontiguousarray(aff_group, dtype=np.int32)
+        az = None if aff_zone is None else np.ascontiguousarray(np.asarray(aff_zone) != 0, dtype=np.uint8)
+        gp = np.empty(ng, np.int32)
+
+        def extra(p):
+            assert (gr is None or gr.shape[0] == p) and (en is None or en.shape[0] == p)
+            assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], p))
+            assert all(m is None or m.shape == (p,) for m in masks + [ag, az])
+            return ((ng, L.ptr(off, C.c_int64), L.ptr(gmin, C.c_int32), L.ptr(gr, C.c_int32), L.ptr(en, C.c_uint8),
+                     L.ptr(re_, C.c_int64)) + tuple(L.ptr(m, C.c_uint64) for m in masks) +
+                    (L.ptr(ag, C.c_int32), L.ptr(az, C.c_uint8)))
+        return self._schedule_with("schedule_full", req_cpu, req_mem, req_pods, selector, extra,
+                                   (L.ptr(gp, C.c_int32),)) + (gp,)
 
 
 def engine_for(cl, mode: Optional[int] = None, **kw) -> Engine:

@@ -727,6 +727,27 @@ class FakeCluster:
         idx, _, _, placed = self.engine.schedule_constrained(rc, rm, rp, sel, off, gmin, group, enforce, req_ext)
         return self._resolve_gangs(pods, off, gmin, idx, placed)
 
+    def schedule_full(self, pending: Optional[List[Pod]] = None):
+        """schedule_constrained and schedule_affinity in one engine call (ksched_schedule_full): the pending pods are
+        grouped into their gangs first (group_gangs reorders them), the spread, extended-resource and affinity tables
+        are built for the reordered list (spread_tables, ext_tables, affinity_tables) and reloaded from self.pods' bound
+        pods, and one launch resolves every gang in order -- a rejected gang gives back the extended resources it took,
+        the spread counts it raised and the affinity words it set.  Resolved gang by gang exactly as schedule_gangs
+        does: binds, GangRejected and events."""
+        pending = self.unscheduled_pods() if pending is None else pending
+        pods, off, gmin = group_gangs(pending)
+        bound = [p for p in self.pods if p.node_name]
+        node_domain, skew, counts, group, enforce = spread_tables(self.nodes, bound, pods)
+        _, node_ext, req_ext = ext_tables(self.nodes, bound, pods)
+        t = affinity_tables(self.nodes, bound, pods)
+        self.engine.load_spread(node_domain, skew, counts)
+        self.engine.load_ext(node_ext)
+        self.engine.load_affinity(*t[:4])
+        rc, rm, rp = pack_pods(pods)
+        sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
+        idx, _, _, placed = self.engine.schedule_full(rc, rm, rp, sel, off, gmin, group, enforce, req_ext, *t[4:])
+        return self._resolve_gangs(pods, off, gmin, idx, placed)
+
     def schedule_pod(self, pod: Pod, selector: Optional[int] = None):
         """schedulePod (anchor/schedule.go:68-89) for a single pod."""
         if selector is None:
