@@ -368,8 +368,8 @@ int ksched_schedule_gangs(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, co
  * ksched_load_nodes invalidates the table (ksched_schedule_spread and ksched_read_spread return KSCHED_E_STATE until
  * it is loaded again); ksched_apply_delta and ksched_save_state / ksched_restore_state leave the counts alone --
  * keeping them in step is the caller's business, as with ksched_load_bound (FakeCluster.schedule_spread reloads the
- * table on every call).  ksched_schedule, ksched_schedule_gangs, ksched_rank, ksched_explain* and ksched_preempt
- * neither read nor move the table.  After ksched_schedule_spread, ksched_explain_batch / ksched_explain_pod return
+ * table on every call).  ksched_schedule, ksched_schedule_gangs, ksched_rank, ksched_explain, ksched_explain_batch /
+ * _pod and ksched_preempt neither read nor move the table; ksched_rank_full and ksched_explain_full read it.  After ksched_schedule_spread, ksched_explain_batch / ksched_explain_pod return
  * KSCHED_E_STATE: they know no spread reason (KSCHED_NUM_REASONS did not change).
  *
  * KSCHED_E_INVALID (nothing changed; a table loaded earlier survives): D or S < 1 or above the caps, S * D >
@@ -379,7 +379,7 @@ int ksched_schedule_gangs(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, co
  *
  * Out of scope: ScheduleAnyway scoring; several constraints or topology keys per pod; minDomains;
  * nodeAffinityPolicy / nodeTaintsPolicy (the minimum ranges over all domains, which is k8s's Ignore); a spread reason
- * in the explain calls; multi-rank; the batched pipeline.
+ * at a pod's turn (against the current state: ksched_explain_full below); multi-rank; the batched pipeline.
  *
  * Worked example (best-price, feasible domain): nodes n0 (zone A, price 0.1), n1 (A, 0.2), n2 (B, 0.5), all with ample
  * room; one group with max_skew 1 and counts 0; four enforcing pods.  Pod 0 sees A 0, B 0: every node is eligible, the
@@ -425,15 +425,15 @@ int ksched_schedule_spread(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, c
  * ksched_load_nodes invalidates it (ksched_schedule_ext and ksched_read_ext return KSCHED_E_STATE until it is loaded
  * again); ksched_apply_delta and ksched_save_state / ksched_restore_state leave it alone -- keeping it in step is the
  * caller's business (FakeCluster.schedule_ext reloads the table on every call).  ksched_schedule,
- * ksched_schedule_gangs, ksched_schedule_spread, ksched_rank, ksched_explain* and ksched_preempt neither read nor
- * move it.  After ksched_schedule_ext, ksched_explain_batch / ksched_explain_pod return KSCHED_E_STATE: they know no
+ * ksched_schedule_gangs, ksched_schedule_spread, ksched_rank, ksched_explain, ksched_explain_batch / _pod and
+ * ksched_preempt neither read nor move it; ksched_rank_full and ksched_explain_full read it.  After ksched_schedule_ext, ksched_explain_batch / ksched_explain_pod return KSCHED_E_STATE: they know no
  * extended-resource reason (KSCHED_NUM_REASONS did not change).
  *
  * KSCHED_E_INVALID (nothing changed; a table loaded earlier survives): n_ext outside [1, KSCHED_EXT_MAX], a null
  * node_ext, a negative request, p outside [0, 2^30), opts.nranks > 1.
  *
- * Out of scope: extended columns in rank, preempt and explain (with gangs and spread: ksched_schedule_constrained
- * below); the batched pipeline and multi-rank; the one-workgroup exact kernel (an ext run always takes the multi-slot one); an apply_delta for the table; init
+ * Out of scope: extended columns in ksched_rank, ksched_preempt and ksched_explain* (dry runs that see them:
+ * ksched_rank_full and ksched_explain_full below; with gangs and spread: ksched_schedule_constrained below); the batched pipeline and multi-rank; the one-workgroup exact kernel (an ext run always takes the multi-slot one); an apply_delta for the table; init
  * containers and pod overhead; quantity suffixes (amounts are whole numbers, pre-scaled by the caller); scoring on
  * extended resources.
  *
@@ -570,7 +570,8 @@ int ksched_schedule_constrained(ksched_ctx *ctx, int64_t p,
  * arrays (any pointer may be NULL).  ksched_load_nodes invalidates the table (ksched_schedule_affinity and
  * ksched_read_affinity return KSCHED_E_STATE until it is loaded again); ksched_apply_delta and ksched_save_state /
  * ksched_restore_state leave it alone, as with spread -- the caller reloads after deletions
- * (FakeCluster.schedule_affinity reloads the table on every call).  No other call reads or moves the table.  After
+ * (FakeCluster.schedule_affinity reloads the table on every call).  ksched_schedule_full reads and moves the table,
+ * ksched_rank_full and ksched_explain_full read it; no other call does either.  After
  * ksched_schedule_affinity, ksched_explain_batch / ksched_explain_pod return KSCHED_E_STATE: they know no affinity reason
  * (KSCHED_NUM_REASONS did not change).
  *
@@ -580,8 +581,9 @@ int ksched_schedule_constrained(ksched_ctx *ctx, int64_t p,
  *
  * Out of scope: affinity inside ksched_schedule_constrained (with gangs, spread and ext and the gang rollback:
  * ksched_schedule_full below); preferred (scored) terms; more than one affinity term per pod; more than one
- * zone key; namespaceSelector, matchLabelKeys; pod removal without a reload; affinity reasons in the explain calls;
- * ksched_rank and ksched_preempt under affinity; the batched pipelines and multi-rank; the one-workgroup exact kernel.
+ * zone key; namespaceSelector, matchLabelKeys; pod removal without a reload; affinity reasons at a pod's turn, and
+ * ksched_rank under affinity (against the current state: ksched_explain_full and ksched_rank_full below); ksched_preempt
+ * under affinity; the batched pipelines and multi-rank; the one-workgroup exact kernel.
  *
  * Worked example (best-price, feasible domain, ample room): nodes n0 (zone A, price 0.1), n1 (B, 0.2), n2 (A, 0.3), n3
  * (no key, 0.4); groups web = bit 0, cache = bit 1, db = bit 2; the table starts empty.  Pods: p0, p1: member web,
@@ -689,6 +691,91 @@ int ksched_schedule_full(ksched_ctx *ctx, int64_t p,
         const uint64_t *anti_zone /* p, or NULL */, const int32_t *aff_group /* p, or NULL */,
         const uint8_t *aff_zone /* p, or NULL = host */,
         int32_t *out_idx, double *out_score, int32_t *out_feasible, int32_t *out_gang_placed);
+
+/* ---- dry runs under constraints (added within ABI 6: probe with dlsym(lib, "ksched_rank_full"); the version number did not move) ----
+ * ksched_rank and ksched_explain with ksched_schedule_full's eligible in the place of fits: the scheduler-extender filter
+ * and prioritize verbs, and the FailedScheduling event with its per-node reasons (anchor/predicate.go:127-171), for a pod
+ * that carries a spread constraint, extended-resource requests or affinity terms.  A caller whose training job came back
+ * KSCHED_NO_FIT from ksched_schedule_full asks here whether it was "Insufficient amd.com/gpu", the spread skew, its own
+ * anti-affinity or somebody else's.
+ *
+ * Both are dry runs in ksched_rank's sense.  They read the node rows and the context's spread, extended-resource and
+ * affinity tables AS THEY STAND, every pod on its own; NOTHING is committed.  Afterwards the node rows, what
+ * ksched_read_spread / ksched_read_ext / ksched_read_affinity return, the staged pods, the last call's results and the
+ * validity and content of ksched_explain_batch are byte-identical to before.  So they describe the CURRENT state, not the
+ * state a pod of an earlier call saw at its turn -- as kube-scheduler re-posts FailedScheduling at each retry against the
+ * then-current state.
+ *
+ * Reason codes: KSCHED_REASON_FIT .. KSCHED_REASON_LABELS keep their values; the constraints add the codes below.  A
+ * node's reason is the FIRST failing check in exactly this order: cpu, memory, pods, labels (under opts.use_labels), the
+ * extended columns 0 .. n_ext - 1 (a zero request is skipped), the spread key, the spread skew, the pod's affinity term,
+ * its own anti-affinity terms, the bound pods' anti-affinity terms.  Reason 0 is eligible(i, j) of ksched_schedule_full
+ * -- the same predicate, with the same tables, not a restatement: spread_ok is ksched_schedule_spread's clause with minc
+ * taken over the current counts, ext_ok ksched_schedule_ext's, and the three affinity clauses are
+ * ksched_schedule_affinity's.  The waiver of clause 3 is decided per pod from the context's current any_host / any_zone,
+ * as that call words it; a waived pod never gets KSCHED_REASON_AFFINITY.
+ *
+ * ksched_rank_full is ksched_rank with eligible in the place of fits; everything else is that call's contract word for
+ * word: m pod shapes, each on its own; entry r of pod i its r-th best eligible node in the scheduler's order; count == 0
+ * with feasible == 0 is KSCHED_NO_FIT and with feasible > 0 KSCHED_NO_POSITIVE_SCORE; under KSCHED_DOMAIN_ALL an
+ * ineligible node can be ranked, and out_reason then carries its full code; 1 <= k <= KSCHED_RANK_MAX; large m is served
+ * in chunks with a bounded device workspace (below 20 MiB); any output pointer may be NULL; the call waits for the
+ * context's stream first.  Entry 0 of pod i is what ksched_schedule_full would choose if that pod were the next call's
+ * only pod.  What differs:
+ *   out_feasible       m     nodes with reason 0
+ *   out_reason_counts  m*14  out_reason_counts[i * KSCHED_NUM_REASONS_FULL + r] = nodes whose reason is r: a row sums to
+ *                            n_local, and its column 0 is out_feasible[i]
+ * Each constraint is on or off for the whole call, by ksched_schedule_full's NULL rule: spread_group, req_ext, or any of
+ * the five affinity pointers switches its constraint on (the other affinity arrays then mean zeros, -1 for aff_group).
+ * On: its table must be loaded (KSCHED_E_STATE otherwise).  Off: no table is needed, a loaded one is not read.
+ *
+ * ksched_explain_full is ksched_explain for one pod with these codes: out_counts[r] counts the nodes per code
+ * (out_counts[KSCHED_REASON_FIT] is the pod's feasible count), out_reason (n_local bytes, may be NULL) receives each
+ * node's code.  A constraint is on where the pod uses it: spread when spread_group >= 0 (spread_enforce == 0: the pod
+ * only counts, and no spread code arises), ext when req_ext != NULL, affinity when a word is non-zero or aff_group >= 0.
+ * Its counts equal the pod's row of ksched_rank_full's out_reason_counts, and its codes at ranked nodes that call's
+ * out_reason.
+ *
+ * KSCHED_E_INVALID (nothing changed): the single calls' argument rules -- spread_group outside [-1, S), a negative
+ * extended-resource request, aff_group outside [-1, 64) --, k out of range, m outside [0, 2^30), a NULL request array, a
+ * NULL selector under opts.use_labels, a NULL out_counts, opts.nranks > 1 (the tables are single-GPU; there is no shard
+ * merge).  KSCHED_E_STATE before ksched_load_nodes.  n_local == 0 answers as ksched_rank does: empty lists, zero counts.
+ *
+ * Out of scope: dry runs of a gang (members see each other's tentative commits); ksched_preempt under constraints; the
+ * reasons a pod of a finished constrained run saw at its turn (a rolled-back gang leaves no placements to rebuild from:
+ * ksched_explain_batch / ksched_explain_pod still return KSCHED_E_STATE after a constrained call); multi-rank;
+ * ScheduleAnyway and preferred terms.
+ *
+ * Worked example, from the end state of ksched_schedule_full's own worked example (best-price, feasible domain): n0, n1
+ * in zone A, n2, n3 in B; counts A 2, B 1 with max_skew 1 (minc 1: a domain may hold at most 1); gpu column {0, 0, 1, 0};
+ * node_member = node_anti_host = {1, 1, 0, 0}, so zone_member = {A 1, B 0}; train = bit 0.
+ *   pod                                                              reasons n0..n3   list
+ *   X  member, anti_host and zone affinity train, gpu 1, group 0     5, 5, 11, 5      empty, feasible 0
+ *   Y  as X, but gpu 0 and no spread group                           12, 12, 11, 11   empty
+ *   Z  member train only                                             13, 13, 0, 0     n2 (0.3), n3 (0.4)
+ *   W  no affinity words, gpu 0, group 0 (enforcing)                 10, 10, 0, 0     n2, n3
+ * X: three nodes have no gpu, and the check comes before the affinity term that n2 fails (no train in zone B).  Y: the
+ * train pods on n0 and n1 are what its own anti-affinity names.  Z carries no term, but the bound pods' terms refuse it. */
+#define KSCHED_REASON_EXT0                    5   /* + r, r < KSCHED_EXT_MAX: "Insufficient <resource r>"; the lowest failing column */
+#define KSCHED_REASON_SPREAD_NO_KEY           9   /* an enforcing pod, node_domain[j] < 0 */
+#define KSCHED_REASON_SPREAD_SKEW            10   /* counts[s][d] + 1 - minc > max_skew[s] */
+#define KSCHED_REASON_AFFINITY               11   /* ksched_schedule_affinity's clause 3, the pod's own affinity term (not waived) */
+#define KSCHED_REASON_ANTI_AFFINITY          12   /* clause 1, the pod's own anti-affinity terms */
+#define KSCHED_REASON_EXISTING_ANTI_AFFINITY 13   /* clause 2, bound pods' terms: the symmetric half */
+#define KSCHED_NUM_REASONS_FULL              14
+int ksched_rank_full(ksched_ctx *ctx, int64_t m,
+        const int64_t *req_cpu, const int64_t *req_mem, const int64_t *req_pods, const uint64_t *selector,
+        const int32_t *spread_group /* m, or NULL */, const uint8_t *spread_enforce /* m, or NULL = all 1 */,
+        const int64_t *req_ext /* n_ext * m, req_ext[r * m + i], or NULL */,
+        const uint64_t *member /* m, or NULL */, const uint64_t *anti_host /* m, or NULL */,
+        const uint64_t *anti_zone /* m, or NULL */, const int32_t *aff_group /* m, or NULL */,
+        const uint8_t *aff_zone /* m, or NULL = host */,
+        int32_t k, int32_t *out_idx, double *out_score, uint8_t *out_reason, int32_t *out_count,
+        int32_t *out_feasible, int64_t *out_reason_counts /* m * KSCHED_NUM_REASONS_FULL, or NULL */);
+int ksched_explain_full(ksched_ctx *ctx, int64_t req_cpu, int64_t req_mem, int64_t req_pods, uint64_t selector,
+        int32_t spread_group /* -1: none */, int32_t spread_enforce, const int64_t *req_ext /* n_ext, or NULL */,
+        uint64_t member, uint64_t anti_host, uint64_t anti_zone, int32_t aff_group /* -1: none */, int32_t aff_zone,
+        int64_t out_counts[KSCHED_NUM_REASONS_FULL], uint8_t *out_reason /* n_local, or NULL */);
 
 /* Same, in two halves, with the pods staged in HBM: upload once, run many times (bench). */
 int ksched_upload_pods(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,

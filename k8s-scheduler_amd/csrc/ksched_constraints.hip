@@ -2,7 +2,9 @@
 // (ksched_schedule_gangs / _spread / _ext, ksched_schedule_constrained for the three in one run,
 // ksched_schedule_affinity, and ksched_schedule_full for all four in one run) check and pack on the host, stage what
 // they packed and run k_exact with their extension (ExactRun, ksched_exact.h); the table calls load and read
-// the context's spread, extended-resource and affinity tables.
+// the context's spread, extended-resource and affinity tables; the dry runs (ksched_rank_full, ksched_explain_full) read
+// the rows and those tables through the kernels of ksched_dryrun.hip and write nothing a context holds.
+#include <algorithm>
 #include <cstring>
 
 #include <new>
@@ -10,6 +12,7 @@
 
 #include "ksched_affinity.h"
 #include "ksched_ctx.h"
+#include "ksched_dryrun.h"
 #include "ksched_ext.h"
 #include "ksched_full.h"
 #include "ksched_gang.h"
@@ -64,6 +67,34 @@ int gang_results(ksched_ctx *c, size_t ng, int32_t *out) {
     if (out && ng > 0) std::memcpy(out, gp.data(), ng * 4);
     return KSCHED_OK;
 }
+
+// The tables a dry run is given: those its call switched on, as the context holds them (read only), and the workspace
+// word per group that k_dry_min fills.
+DryTables dry_tables(const ksched_ctx *c, const DryPacked &k, int32_t *sp_min) {
+    const ksched_bufs &d = *c->d;
+    DryTables t{};
+    if (k.spread) { t.sp_dom = d.sdom; t.sp_cnt = d.scnt; t.sp_skew = d.sskew; t.sp_D = c->spread_D; t.sp_S = c->spread_S; t.sp_min = sp_min; }
+    if (k.ext) { t.ext = d.etab; t.n_ext = c->ext_R; }
+    if (k.aff) { t.af_dom = d.adom; t.af_mem = d.amem; t.af_anti_h = d.aanti_h; t.af_zone = d.azone; t.af_D = c->aff_D; }
+    return t;
+}
+
+// What both dry runs check before anything else, and the packing of their pods (ksched_dryrun.h).
+int dry_begin(ksched_ctx *c, const char *name, const DryCall &call, DryPacked *k) {
+    const std::string nm(name);
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, nm + " before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, nm + " is single-GPU (the tables are: there is no shard merge)");
+    const DryState st{c->o.use_labels != 0, c->spread_S, c->ext_R, c->aff_valid, c->aff_any[0], c->aff_any[1]};
+    try {
+        const char *why = nullptr;
+        if (const int code = dry_check_pack(call, st, k, &why)) return fail(c, code, nm + ": " + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, nm + ": host staging buffer");
+    }
+    return KSCHED_OK;
+}
+
+uint64_t uabs64(int64_t v) { return v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v; }
 
 }  // namespace
 
@@ -377,5 +408,120 @@ int ksched_schedule_full(ksched_ctx *c, int64_t p, const int64_t *rc, const int6
     return gang_results(c, ng, gang_off ? out_gang_placed : nullptr);
 }
 
-}  // extern "C"
+// Ranked dry run under constraints (ksched_dryrun.hip).  Touches nothing a schedule call left behind and no table: the
+// groups' minima, its pods, span lists and outputs live in d->dws, and FAST53 is decided here for these m pods alone.
+int ksched_rank_full(ksched_ctx *c, int64_t m, const int64_t *rc, const int64_t *rm, const int64_t *rp, const uint64_t *sel,
+                     const int32_t *spread_group, const uint8_t *spread_enforce, const int64_t *req_ext,
+                     const uint64_t *member, const uint64_t *anti_host, const uint64_t *anti_zone, const int32_t *aff_group,
+                     const uint8_t *aff_zone, int32_t k, int32_t *out_idx, double *out_score, uint8_t *out_reason,
+                     int32_t *out_count, int32_t *out_feasible, int64_t *out_reason_counts) {
+    if (!c) return KSCHED_E_INVALID;
+    static_assert(KSCHED_NUM_REASONS_FULL == kNumReasonsFull && KSCHED_RANK_MAX == 64, "dry run constants");
+    if (k < 1 || k > KSCHED_RANK_MAX) return fail(c, KSCHED_E_INVALID, "rank_full: k must be in 1..KSCHED_RANK_MAX");
+    DryPacked pk;
+    const DryCall call{m, rc, rm, rp, sel, spread_group, spread_enforce, req_ext, member, anti_host, anti_zone, aff_group, aff_zone};
+    if (const int r = dry_begin(c, "rank_full", call, &pk)) return r;
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (m == 0) return KSCHED_OK;
+    const int64_t n = c->n_local;
+    if (n == 0) {  // no node: nothing is ranked and nothing is counted
+        const size_t e = (size_t)m * (size_t)k;
+        if (out_idx) std::fill(out_idx, out_idx + e, -1);
+        if (out_score) std::fill(out_score, out_score + e, 0.0);
+        if (out_reason) std::memset(out_reason, 0, e);
+        if (out_count) std::fill(out_count, out_count + m, 0);
+        if (out_feasible) std::fill(out_feasible, out_feasible + m, 0);
+        if (out_reason_counts) std::fill(out_reason_counts, out_reason_counts + m * KSCHED_NUM_REASONS_FULL, (int64_t)0);
+        return KSCHED_OK;
+    }
+    uint64_t mxr = 0;
+    for (int64_t i = 0; i < m; ++i) mxr = std::max(mxr, std::max(uabs64(rc[i]), std::max(uabs64(rm[i]), uabs64(rp[i]))));
+    const bool f53 = sat_add(c->max_abs_alloc, mxr) < (1ull << 52);
+    // the workspace: minima | one chunk's pods | span lists | span histograms | outputs, each 256-byte aligned
+    const int64_t mc_max = std::min<int64_t>(m, kRankChunk);
+    size_t nl = 0;  // span lists of the largest chunk: at most kRankGridWGs * kDryTile (dry_geometry)
+    for (int64_t q : {mc_max, m % kRankChunk}) {  // the full chunk and the tail (fewer pods, more spans)
+        if (q <= 0) continue;
+        int32_t s; int64_t rows;
+        dry_geometry(n, q, &s, &rows);
+        nl = std::max(nl, (size_t)q * (size_t)s);
+    }
+    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t o_min = 0, o_pods = al(o_min + KSCHED_SPREAD_MAX_GROUPS * 4), o_part = al(o_pods + (size_t)mc_max * sizeof(DryPod)),
+                 o_ph = al(o_part + nl * 64 * sizeof(Cand)), o_idx = al(o_ph + nl * kDryHist * 4),
+                 o_sc = al(o_idx + (size_t)mc_max * k * 4), o_rs = al(o_sc + (size_t)mc_max * k * 8),
+                 o_cnt = al(o_rs + (size_t)mc_max * k), o_feas = al(o_cnt + (size_t)mc_max * 4),
+                 o_hist = al(o_feas + (size_t)mc_max * 4), total = al(o_hist + (size_t)mc_max * kNumReasonsFull * 8);
+    HIPCHK(c, c->d->dws.reserve(total));
+    char *w = static_cast<char *>(c->d->dws.p);
+    const DryTables t = dry_tables(c, pk, reinterpret_cast<int32_t *>(w + o_min));
+    HIPCHK(c, launch_dry_min(t, c->stream));
+    std::vector<char> stage(total - o_idx);  // host side of a chunk's copy out
+    for (int64_t at = 0; at < m; at += kRankChunk) {
+        const int64_t mc = std::min<int64_t>(kRankChunk, m - at);
+        DryArgs a{};
+        a.nodes = c->d->nodes; a.n_local = n; a.node_offset = c->o.node_offset;
+        a.t = t;
+        a.pods = reinterpret_cast<DryPod *>(w + o_pods);
+        a.m = (int32_t)mc; a.k = k;
+        dry_geometry(n, mc, &a.spans, &a.span_rows);
+        if ((size_t)mc * a.spans > nl) return fail(c, KSCHED_E_NOMEM, "rank_full: workspace bound");  // (dry_geometry's bound)
+        a.part = reinterpret_cast<Cand *>(w + o_part); a.part_hist = reinterpret_cast<int32_t *>(w + o_ph);
+        a.out_idx = reinterpret_cast<int32_t *>(w + o_idx); a.out_score = reinterpret_cast<double *>(w + o_sc);
+        a.out_reason = reinterpret_cast<uint8_t *>(w + o_rs); a.out_count = reinterpret_cast<int32_t *>(w + o_cnt);
+        a.out_feasible = reinterpret_cast<int32_t *>(w + o_feas); a.out_hist = reinterpret_cast<int64_t *>(w + o_hist);
+        // one copy in and one copy out per chunk, in the stream of the kernels
+        HIPCHK(c, hipMemcpyAsync(w + o_pods, pk.pods.data() + at, (size_t)mc * sizeof(DryPod), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_dry_rank(c->o.priority, c->o.domain, c->o.use_labels != 0, f53, a, c->stream));
+        HIPCHK(c, hipMemcpyAsync(stage.data(), w + o_idx, total - o_idx, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // the next chunk reuses the workspace and the staging buffer
+        const size_t e = (size_t)mc * k, eo = (size_t)at * k;
+        const char *ho = stage.data();  // the outputs, at their workspace offsets less o_idx
+        if (out_idx) std::memcpy(out_idx + eo, ho, e * 4);
+        if (out_score) std::memcpy(out_score + eo, ho + (o_sc - o_idx), e * 8);
+        if (out_reason) std::memcpy(out_reason + eo, ho + (o_rs - o_idx), e);
+        if (out_count) std::memcpy(out_count + at, ho + (o_cnt - o_idx), (size_t)mc * 4);
+        if (out_feasible) std::memcpy(out_feasible + at, ho + (o_feas - o_idx), (size_t)mc * 4);
+        if (out_reason_counts)
+            std::memcpy(out_reason_counts + at * kNumReasonsFull, ho + (o_hist - o_idx), (size_t)mc * kNumReasonsFull * 8);
+    }
+    return KSCHED_OK;
+}
 
+// One pod's per-node reasons and their histogram under constraints: k_dry_explain behind k_dry_min, in d->dws.
+int ksched_explain_full(ksched_ctx *c, int64_t rc, int64_t rm, int64_t rp, uint64_t sel, int32_t spread_group,
+                        int32_t spread_enforce, const int64_t *req_ext, uint64_t member, uint64_t anti_host,
+                        uint64_t anti_zone, int32_t aff_group, int32_t aff_zone, int64_t out_counts[KSCHED_NUM_REASONS_FULL],
+                        uint8_t *out_reason) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "explain_full before load_nodes");
+    if (!out_counts) return fail(c, KSCHED_E_INVALID, "explain_full: out_counts is NULL");
+    if (const char *why = dry_check_one(spread_group, aff_group)) return fail(c, KSCHED_E_INVALID, std::string("explain_full: ") + why);
+    const DryOne one{rc, rm, rp, sel, member, anti_host, anti_zone, spread_group, aff_group,
+                     (uint8_t)(spread_enforce != 0), (uint8_t)(aff_zone != 0)};
+    DryPacked pk;
+    if (const int r = dry_begin(c, "explain_full", one.call(req_ext), &pk)) return r;
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t n = c->n_local;
+    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t o_min = 0, o_cnt = al(o_min + KSCHED_SPREAD_MAX_GROUPS * 4), o_rs = al(o_cnt + kNumReasonsFull * 8),
+                 total = al(o_rs + (size_t)n);
+    HIPCHK(c, c->d->dws.reserve(total));
+    char *w = static_cast<char *>(c->d->dws.p);
+    const DryTables t = dry_tables(c, pk, reinterpret_cast<int32_t *>(w + o_min));
+    unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(w + o_cnt);
+    unsigned long long h[kNumReasonsFull] = {};
+    HIPCHK(c, hipMemsetAsync(d_cnt, 0, sizeof(h), c->stream));
+    HIPCHK(c, launch_dry_min(t, c->stream));
+    HIPCHK(c, launch_dry_explain(c->d->nodes, n, t, pk.pods[0], c->o.use_labels != 0,
+                                 out_reason ? reinterpret_cast<uint8_t *>(w + o_rs) : nullptr, d_cnt, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(h, d_cnt, sizeof(h), hipMemcpyDeviceToHost));
+    if (out_reason && n > 0) HIPCHK(c, hipMemcpy(out_reason, w + o_rs, (size_t)n, hipMemcpyDeviceToHost));
+    for (int r = 0; r < kNumReasonsFull; ++r) out_counts[r] = (int64_t)h[r];
+    return KSCHED_OK;
+}
+
+}  // extern "C"

@@ -119,6 +119,8 @@ struct ksched_bufs {
                                           // ExactArgs::af_undo_slot [kGangMax][3], then af_undo_zone [G][kGangMax][2]
     DevBuf<void> xws, xbuf;               // explain: workspace; counts + NO_FIT pod list, or one pod's state + counts
     DevBuf<void> rws;                     // ksched_rank: one chunk's pods, span lists and outputs (rank_geometry's bound)
+    DevBuf<void> dws;                     // ksched_rank_full / ksched_explain_full: the groups' minima, one chunk's pods,
+                                          // span lists, histograms and outputs (dry_geometry's bound)
     DevBuf<int64_t> bcpu, bmem, boff;     // ksched_load_bound: the bound-pod table (BoundTable, ksched_preempt.h)
     DevBuf<int32_t> bprio, btidx, bdepth, bseg;
     DevBuf<void> vws;                     // ksched_preempt: one chunk's pods, span parts and outputs

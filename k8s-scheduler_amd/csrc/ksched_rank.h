@@ -36,8 +36,9 @@ struct RankArgs {
 // The spans of a chunk of m pods over n rows: as many as keep the scan grid near kRankGridWGs workgroups, none
 // shorter than kRankSpanMin rows.  m = 1 .. 8: ceil(n / 1024) spans (at most 2048); a full chunk: at most 16.
 // spans * m <= kRankGridWGs * kRankTile lists of 1 KiB: the part lists never exceed 16 MiB.
-inline void rank_geometry(int64_t n, int64_t m, int32_t *spans, int64_t *span_rows) {
-    const int64_t tiles = (m + kRankTile - 1) / kRankTile;
+// (tile: the pods a scan wave carries -- ksched_dryrun.hip's scan has the same geometry at a smaller tile)
+inline void rank_geometry(int64_t n, int64_t m, int32_t *spans, int64_t *span_rows, int tile = kRankTile) {
+    const int64_t tiles = (m + tile - 1) / tile;
     int64_t s = kRankGridWGs / (tiles < 1 ? 1 : tiles);
     const int64_t smax = (n + kRankSpanMin - 1) / kRankSpanMin;
     if (s > smax) s = smax;

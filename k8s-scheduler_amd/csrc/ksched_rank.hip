@@ -3,7 +3,8 @@
 //
 // The mapping is the opposite of the stream pipeline's k_score_topk (lane = pod, rows scalar-loaded): here
 // lane = node, so ONE pod already fills a wave, and a pod's list is one (key code, idx) pair per lane -- 64
-// entries in 3 VGPRs, sorted and merged by the register-only wave sorts of ksched_merge.h.
+// entries in 3 VGPRs, sorted and merged by the register-only wave sorts of ksched_merge.h and the list steps of
+// ksched_rank_steps.h (rank_merge_step, rank_insert_step; ksched_dryrun.hip uses the same).
 //
 //   k_rank_scan   grid (node spans, pod tiles).  Each wave of a workgroup walks its share of the span 64 rows at
 //                 a time, one NodeRec per lane, and scores the rows against the tile's kRankTile pods (wave-uniform
@@ -22,8 +23,8 @@
 // scheduling kernel, so the bits agree with the scheduler by construction.
 #include <hip/hip_runtime.h>
 
-#include "ksched_merge.h"
 #include "ksched_rank.h"
+#include "ksched_rank_steps.h"
 
 namespace ksched {
 
@@ -31,50 +32,6 @@ namespace {
 
 typedef __attribute__((address_space(4))) const int64_t CI64;
 typedef __attribute__((address_space(4))) const uint64_t CU64;
-
-// kept, cand: sorted 64-lists (rank r in lane r) over disjoint nodes.  On return kept is the sorted best 64 of
-// the 128.  Lane l first keeps the better of kept[l] and cand[63 - l] (the flip of the bitonic merge: of the pairs
-// (kept[l], cand[63 - l]) the winners are the best 64 of the 128), and the winners, read along the lanes, fall and
-// then rise -- a bitonic sequence, which the six half-cleaners (xor 32 .. 1, the lane with the bit clear keeps
-// the better) sort.  tests/test_rank_host.py runs this network, and rank_insert_step below, lane for lane over
-// every zero-one input.
-__device__ __forceinline__ void rank_merge_step(uint64_t &kc, int32_t &ki, uint64_t cc, int32_t ci, const int lane) {
-    uint32_t lo = (uint32_t)kc, hi = (uint32_t)(kc >> 32), ix = (uint32_t)ki;
-    {
-        const uint32_t rlo = xpartner<63>((uint32_t)cc), rhi = xpartner<63>((uint32_t)(cc >> 32));
-        const uint32_t rix = xpartner<63>((uint32_t)ci);
-        const bool take = code_better(((uint64_t)rhi << 32) | rlo, (int32_t)rix, kc, ki);
-        lo = take ? rlo : lo;
-        hi = take ? rhi : hi;
-        ix = take ? rix : ix;
-    }
-    sort_stage<32, 32>(lo, hi, ix, lane); sort_stage<16, 16>(lo, hi, ix, lane);
-    sort_stage<8, 8>(lo, hi, ix, lane); sort_stage<4, 4>(lo, hi, ix, lane);
-    sort_stage<2, 2>(lo, hi, ix, lane); sort_stage<1, 1>(lo, hi, ix, lane);
-    kc = ((uint64_t)hi << 32) | lo;
-    ki = (int32_t)ix;
-}
-
-// One candidate (xc, xi), wave-uniform, into the sorted list: the lanes whose entry it beats are a suffix; each of
-// them takes its upper neighbour's entry (DPP wave_shr:1), the first of them the candidate; lane 63's entry falls
-// off.  A candidate that beats nobody changes nothing.  Lane 0's missing neighbour reads as the unbeatable code ~0.
-__device__ __forceinline__ uint32_t wave_shr1(uint32_t v, uint32_t lane0) {
-    return (uint32_t)__builtin_amdgcn_update_dpp((int)lane0, (int)v, 0x138, 0xF, 0xF, false);
-}
-__device__ __forceinline__ void rank_insert_step(uint64_t &kc, int32_t &ki, uint64_t xc, int32_t xi) {
-    const uint32_t plo = wave_shr1((uint32_t)kc, 0xffffffffu), phi = wave_shr1((uint32_t)(kc >> 32), 0xffffffffu);
-    const uint32_t pix = wave_shr1((uint32_t)ki, 0u);
-    const uint64_t pc = ((uint64_t)phi << 32) | plo;
-    const bool b = code_better(xc, xi, kc, ki);               // the candidate beats this lane's entry
-    const bool pb = code_better(xc, xi, pc, (int32_t)pix);    // ... and its upper neighbour's
-    kc = b ? (pb ? pc : xc) : kc;
-    ki = b ? (pb ? (int32_t)pix : xi) : ki;
-}
-
-__device__ __forceinline__ double code_key(uint64_t c) {  // inverse of key_code
-    const uint64_t u = (c >> 63) ? (c & 0x7fffffffffffffffull) : ~c;
-    return __longlong_as_double((long long)u);
-}
 
 // The LDS of both kernels: every wave's lists (scan: kRankTile pods; merge: one), and the counts.
 template <int T>

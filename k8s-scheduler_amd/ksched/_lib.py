@@ -32,6 +32,11 @@ PRIORITY_RESOURCE, PRIORITY_BEST_PRICE = 0, 1
 DOMAIN_ALL, DOMAIN_FEASIBLE = 0, 1
 REASON_FIT, REASON_CPU, REASON_MEMORY, REASON_POD, REASON_LABELS = 0, 1, 2, 3, 4
 NUM_REASONS = 5
+# the codes ksched_rank_full / ksched_explain_full add: REASON_EXT0 + r for extended column r < EXT_MAX, then spread
+# (no key, skew) and affinity (the pod's term, its own anti-affinity terms, the bound pods' terms)
+REASON_EXT0, REASON_SPREAD_NO_KEY, REASON_SPREAD_SKEW = 5, 9, 10
+REASON_AFFINITY, REASON_ANTI_AFFINITY, REASON_EXISTING_ANTI_AFFINITY = 11, 12, 13
+NUM_REASONS_FULL = 14
 RANK_MAX = 64  # KSCHED_RANK_MAX: entries ksched_rank keeps per pod
 GANG_MAX = 1024  # KSCHED_GANG_MAX: members of one gang
 # ksched_load_spread's caps: domains, groups, and groups * domains (the exact kernel's per-workgroup LDS table)
@@ -44,6 +49,24 @@ XCHG_HANDLE_BYTES = 128
 # the reference's per-node failure text (anchor/predicate.go:135,140,145)
 REASON_TEXT = {REASON_CPU: "Insufficient CPU", REASON_MEMORY: "Insufficient Memory", REASON_POD: "Insufficient Pod",
                REASON_LABELS: "node labels do not match the pod's selector"}
+# ... and kube-scheduler's for the constraints; the four extended columns read "Insufficient {resource}" with the name
+# the caller knows (reason_text_full)
+REASON_TEXT_FULL = dict(REASON_TEXT)
+REASON_TEXT_FULL.update({REASON_EXT0 + r: "Insufficient {resource}" for r in range(4)})
+REASON_TEXT_FULL.update({
+    REASON_SPREAD_NO_KEY: "node(s) didn't match pod topology spread constraints (missing required label)",
+    REASON_SPREAD_SKEW: "node(s) didn't match pod topology spread constraints",
+    REASON_AFFINITY: "node(s) didn't match pod affinity rules",
+    REASON_ANTI_AFFINITY: "node(s) didn't match pod anti-affinity rules",
+    REASON_EXISTING_ANTI_AFFINITY: "node(s) didn't satisfy existing pods anti-affinity rules"})
+
+
+def reason_text_full(code: int, resources=()) -> str:
+    """REASON_TEXT_FULL[code], an extended column's line naming resources[code - REASON_EXT0] (its index where the
+    caller has no name for it)."""
+    r = code - REASON_EXT0
+    name = resources[r] if 0 <= r < len(resources) else f"extended resource {r}"
+    return REASON_TEXT_FULL[code].format(resource=name)
 
 _ERRNAMES = {E_INVALID: "E_INVALID", E_DEVICE: "E_DEVICE", E_PARSE: "E_PARSE", E_STATE: "E_STATE",
              E_NOMEM: "E_NOMEM", E_UNKNOWN_NODE: "E_UNKNOWN_NODE"}
@@ -133,6 +156,10 @@ SIGNATURES = [
                                            F64P, I32P]),
     ("ksched_schedule_full", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, C.c_int64, I64P, I32P, I32P, U8P, I64P,
                                        U64P, U64P, U64P, I32P, U8P, I32P, F64P, I32P, I32P]),
+    ("ksched_rank_full", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, I32P, U8P, I64P, U64P, U64P, U64P, I32P, U8P,
+                                   C.c_int32, I32P, F64P, U8P, I32P, I32P, I64P]),
+    ("ksched_explain_full", C.c_int, [CTX, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, I64P,
+                                      C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, I64P, U8P]),
     ("ksched_upload_pods", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P]),
     ("ksched_run", C.c_int, [CTX]),
     ("ksched_sync", C.c_int, [CTX]),

@@ -512,6 +512,53 @@ class Engine:
         return self._schedule_with("schedule_full", req_cpu, req_mem, req_pods, selector, extra,
                                    (L.ptr(gp, C.c_int32),)) + (gp,)
 
+    def rank_full(self, req_cpu, req_mem, req_pods, selector=None, k: int = 16, group=None, enforce=None, req_ext=None,
+                  member=None, anti_host=None, anti_zone=None, aff_group=None, aff_zone=None):
+        """rank() under constraints (ksched_rank_full): for each pod shape its k best nodes among those
+        schedule_full() would call eligible, against the node rows and the load_spread() / load_ext() /
+        load_affinity() tables as they stand; nothing is committed and no table moves.  group, req_ext and the five
+        affinity arguments switch their constraint on as in schedule_full().  Returns (idx, score, reason, count,
+        feasible, reason_counts): rank()'s five arrays -- reason with the REASON_* codes up to NUM_REASONS_FULL,
+        feasible counting eligible nodes -- and reason_counts int64[m, NUM_REASONS_FULL], the nodes per code."""
+        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
+        m = rc.shape[0]
+        assert rm.shape[0] == m and rp.shape[0] == m
+        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
+        gr = None if group is None else np.ascontiguousarray(group, dtype=np.int32)
+        en = None if enforce is None or gr is None else np.ascontiguousarray(np.asarray(enforce) != 0, dtype=np.uint8)
+        re_ = None if req_ext is None else np.ascontiguousarray(req_ext, dtype=np.int64)
+        masks = [None if x is None else np.ascontiguousarray(x, dtype=np.uint64) for x in (member, anti_host, anti_zone)]
+        ag = None if aff_group is None else np.ascontiguousarray(aff_group, dtype=np.int32)
+        az = None if aff_zone is None else np.ascontiguousarray(np.asarray(aff_zone) != 0, dtype=np.uint8)
+        assert all(x is None or x.shape == (m,) for x in [gr, en, ag, az] + masks)
+        assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], m))
+        kk = max(int(k), 0)
+        idx = np.empty((m, kk), np.int32); score = np.empty((m, kk), np.float64); reason = np.empty((m, kk), np.uint8)
+        count = np.empty(m, np.int32); feas = np.empty(m, np.int32); hist = np.empty((m, L.NUM_REASONS_FULL), np.int64)
+        self._chk(L.lib().ksched_rank_full(
+            self._ctx, m, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64), L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64),
+            L.ptr(gr, C.c_int32), L.ptr(en, C.c_uint8), L.ptr(re_, C.c_int64), *(L.ptr(x, C.c_uint64) for x in masks),
+            L.ptr(ag, C.c_int32), L.ptr(az, C.c_uint8), int(k), L.ptr(idx, C.c_int32), L.ptr(score, C.c_double),
+            L.ptr(reason, C.c_uint8), L.ptr(count, C.c_int32), L.ptr(feas, C.c_int32), L.ptr(hist, C.c_int64)),
+            "rank_full")
+        return idx, score, reason, count, feas, hist
+
+    def explain_full(self, req_cpu: int, req_mem: int, req_pods: int, selector: int = 0, group: int = -1,
+                     enforce: bool = True, req_ext=None, member: int = 0, anti_host: int = 0, anti_zone: int = 0,
+                     aff_group: int = -1, aff_zone: bool = False, per_node: bool = True):
+        """explain() under constraints (ksched_explain_full): ONE pod against the current rows and tables, a constraint
+        on where the pod uses it (group >= 0, req_ext given, an affinity word or group).  Returns (counts
+        int64[NUM_REASONS_FULL], reasons uint8[n] | None)."""
+        cnt = np.zeros(L.NUM_REASONS_FULL, np.int64)
+        rs = np.empty(max(self.n, 0), np.uint8) if per_node else None
+        re_ = None if req_ext is None else np.ascontiguousarray(req_ext, dtype=np.int64)
+        assert re_ is None or re_.shape == (getattr(self, "_ext_shape", (re_.shape[0],))[0],)
+        self._chk(L.lib().ksched_explain_full(
+            self._ctx, int(req_cpu), int(req_mem), int(req_pods), int(selector), int(group), int(bool(enforce)),
+            L.ptr(re_, C.c_int64), int(member), int(anti_host), int(anti_zone), int(aff_group), int(bool(aff_zone)),
+            L.ptr(cnt, C.c_int64), L.ptr(rs, C.c_uint8)), "explain_full")
+        return cnt, rs
+
 
 def engine_for(cl, mode: Optional[int] = None, **kw) -> Engine:
     """Engine configured for a ksched.cluster.Cluster and loaded with its nodes."""

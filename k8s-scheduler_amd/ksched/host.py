@@ -567,6 +567,50 @@ class FakeCluster:
         return [(self.nodes[int(idx[0, r])], float(score[0, r]), L.REASON_TEXT.get(int(reason[0, r])))
                 for r in range(int(count[0]))]
 
+    def _dry_run_args(self, pod: Pod, selector: Optional[int]):
+        """What rank_pod_full and explain_pod_full share: the spread, extended-resource and affinity tables reloaded
+        from self.pods' bound pods with [pod] as the pending list (spread_tables, ext_tables, affinity_tables), as
+        preempt_pod reloads its table.  Returns the pod's request, its selector array, the per-pod constraint arrays
+        in Engine.rank_full's order and the extended resources' names."""
+        bound = [p for p in self.pods if p.node_name]
+        node_domain, skew, counts, group, enforce = spread_tables(self.nodes, bound, [pod])
+        names, node_ext, req_ext = ext_tables(self.nodes, bound, [pod])
+        t = affinity_tables(self.nodes, bound, [pod])
+        self.engine.load_spread(node_domain, skew, counts)
+        self.engine.load_ext(node_ext)
+        self.engine.load_affinity(*t[:4])
+        if selector is None:
+            selector = self.selector_of(pod)
+        sel = np.asarray([selector], dtype=np.uint64) if self.use_labels else None
+        return pack_pods([pod]), sel, (group, enforce, req_ext) + tuple(t[4:]), names
+
+    def rank_pod_full(self, pod: Pod, k: int = 16, selector: Optional[int] = None):
+        """rank_pod under the pod's spread constraint, extended resources and affinity terms (ksched_rank_full): its k
+        best nodes among those schedule_full would call eligible, as [(Node, score | price, reason text | None)].  The
+        three tables are reloaded from self.pods' bound pods first; nothing is placed.  The text (REASON_TEXT_FULL, an
+        extended column by its resource's name) is set only where a ranked node is not eligible -- the all-node
+        domain's quirk."""
+        (rc, rm, rp), sel, cons, names = self._dry_run_args(pod, selector)
+        idx, score, reason, count, _, _ = self.engine.rank_full(rc, rm, rp, sel, k, *cons)
+        return [(self.nodes[int(idx[0, r])], float(score[0, r]),
+                 L.reason_text_full(int(reason[0, r]), names) if reason[0, r] != L.REASON_FIT else None)
+                for r in range(int(count[0]))]
+
+    def explain_pod_full(self, pod: Pod, selector: Optional[int] = None):
+        """Why the pod fits where it does, constraints included (ksched_explain_full), against the current state: the
+        three tables are reloaded from self.pods' bound pods first; nothing is placed and no event is posted.  Returns
+        (counts int64[NUM_REASONS_FULL], message): the nodes per reason code, and the FailedScheduling text with one
+        "fit failure on node (...): ..." line per node that is not eligible, in node-list order -- kube-scheduler's
+        wordings (REASON_TEXT_FULL), the extended-resource lines naming the resource."""
+        (rc, rm, rp), sel, cons, names = self._dry_run_args(pod, selector)
+        group, enforce, req_ext, member, anti_host, anti_zone, aff_group, aff_zone = cons
+        counts, reasons = self.engine.explain_full(
+            int(rc[0]), int(rm[0]), int(rp[0]), 0 if sel is None else int(sel[0]), int(group[0]), bool(enforce[0]),
+            req_ext[:, 0], int(member[0]), int(anti_host[0]), int(anti_zone[0]), int(aff_group[0]), bool(aff_zone[0]))
+        lines = [f"fit failure on node ({self.nodes[j].name}): {L.reason_text_full(int(r), names)}"
+                 for j, r in enumerate(reasons) if r != L.REASON_FIT]
+        return counts, f"pod ({pod.name}) failed to fit in any node\n" + "\n".join(lines)
+
     def preempt_pod(self, pod: Pod, evict: bool = False, selector: Optional[int] = None):
         """kube-scheduler's default preemption for one pod that fits nowhere (ksched_preempt): the node on which the
         cheapest set of lower-priority bound pods would have to go, and those pods, most important first, as
@@ -670,8 +714,8 @@ class FakeCluster:
         """schedule_pods under the pending pods' topology spread constraints (spread_tables;
         ksched_schedule_spread): the spread table is reloaded from self.pods' bound pods on every call, then one
         engine call resolves every pending pod in order and the binds follow.  Returns (pod, node | Exception); a
-        pod that fits nowhere its constraint allows gets the usual FailedScheduling event (without per-node lines:
-        the explain calls know no spread reason)."""
+        pod that fits nowhere its constraint allows gets the usual FailedScheduling event (without per-node lines: the at-its-turn explain
+        calls know no spread reason; explain_pod_full gives them against the current state)."""
         pending = self.unscheduled_pods() if pending is None else pending
         node_domain, skew, counts, group, enforce = spread_tables(self.nodes, [p for p in self.pods if p.node_name],
                                                                   pending)
@@ -685,8 +729,8 @@ class FakeCluster:
         """schedule_pods under the pods' required inter-pod affinity and anti-affinity terms (affinity_tables;
         ksched_schedule_affinity): the affinity table is reloaded from self.pods' bound pods on every call, then one
         engine call resolves every pending pod in order and the binds follow.  Returns (pod, node | Exception); a pod
-        that fits nowhere its terms allow gets the usual FailedScheduling event (without per-node lines: the explain
-        calls know no affinity reason)."""
+        that fits nowhere its terms allow gets the usual FailedScheduling event (without per-node lines: the at-its-turn
+        explain calls know no affinity reason; explain_pod_full gives them against the current state)."""
         pending = self.unscheduled_pods() if pending is None else pending
         t = affinity_tables(self.nodes, [p for p in self.pods if p.node_name], pending)
         self.engine.load_affinity(*t[:4])
@@ -699,7 +743,8 @@ class FakeCluster:
         """schedule_pods with the pending pods' extended resources (ext_tables; ksched_schedule_ext) in the fit
         predicate: the table is reloaded from self.pods' bound pods on every call, then one engine call resolves every
         pending pod in order and the binds follow.  Returns (pod, node | Exception); a pod that fits nowhere gets the
-        usual FailedScheduling event (without per-node lines: the explain calls know no extended-resource reason)."""
+        usual FailedScheduling event (without per-node lines: the at-its-turn explain calls know no extended-resource
+        reason; explain_pod_full gives them against the current state)."""
         pending = self.unscheduled_pods() if pending is None else pending
         _, node_ext, req_ext = ext_tables(self.nodes, [p for p in self.pods if p.node_name], pending)
         self.engine.load_ext(node_ext)
