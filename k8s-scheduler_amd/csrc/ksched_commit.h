@@ -28,6 +28,9 @@
 #ifndef KSCHED_XCHG_DEBUG
 #define KSCHED_XCHG_DEBUG 0  // the exchange diagnostics of tests/diag/xchg_ring_experiment.py (a separate build)
 #endif
+#ifndef KSCHED_COMMIT_SPLIT
+#define KSCHED_COMMIT_SPLIT 0  // 1: cycle marks inside the check step under KSCHED_COMMIT_STAMPS (a diagnostics build)
+#endif
 
 #include "ksched_pipe.h"  // the persistent (COH) paths: PersistArgs, the tagged records, the rescue request
 
@@ -171,6 +174,79 @@ __device__ __forceinline__ int64_t rl64(int64_t v, int src) {
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)((uint64_t)v >> 32), src);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)v, src);
     return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// the set bits of a ballot below this lane (v_mbcnt: no per-lane mask constant to build or keep)
+__device__ __forceinline__ int lanes_below(uint64_t mask) {
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// ---- LDS gathers with their loads in flight ----
+// commit_spc_batch is short of registers, and the compiler then issues the guess step's dependent LDS reads one at a
+// time, each behind its own wait (16 round trips for 16 list entries).  These statements issue every load of a level
+// before the one wait for it; the loads and their wait sit in one statement (early-clobber outputs), so no value is
+// used before it has landed.  LDS reads of a wave stay in order behind its earlier LDS writes.
+__device__ __forceinline__ uint32_t lds_addr(const void *p) {  // the LDS byte address of a pointer into shared memory
+    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void *)p;
+}
+
+// o0 = *(int32_t *)a0, o1 = *(int32_t *)a1: one round trip
+__device__ __forceinline__ void lds_read2(uint32_t a0, uint32_t a1, int32_t &o0, int32_t &o1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %3\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(o0), "=&v"(o1) : "v"(a0), "v"(a1) : "memory");
+#else
+    o0 = o1 = 0; (void)a0; (void)a1;
+#endif
+}
+
+// hp[u] = HP[u * 64] (hp_at: the LDS address of the lane's first entry; a [K][64] array of table positions) and
+// w[u] = the word of a second array (at LDS address base2) that hp[u] >> SHIFT indexes: N = 4 or 8, two round trips
+template <int N, int SHIFT>
+__device__ __forceinline__ void lds_gather(uint32_t hp_at, uint32_t base2, int32_t (&hp)[N], int32_t (&w)[N]) {
+    static_assert(N == 4 || N == 8, "lds_gather: 4 or 8 entries");
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (N == 4) {
+        asm volatile("ds_read_b32 %0, %8\n\tds_read_b32 %1, %8 offset:256\n\t"
+                     "ds_read_b32 %2, %8 offset:512\n\tds_read_b32 %3, %8 offset:768\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\t"
+                     "v_lshrrev_b32 %4, %10, %0\n\tv_lshrrev_b32 %5, %10, %1\n\t"
+                     "v_lshrrev_b32 %6, %10, %2\n\tv_lshrrev_b32 %7, %10, %3\n\t"
+                     "v_lshl_add_u32 %4, %4, 2, %9\n\tv_lshl_add_u32 %5, %5, 2, %9\n\t"
+                     "v_lshl_add_u32 %6, %6, 2, %9\n\tv_lshl_add_u32 %7, %7, 2, %9\n\t"
+                     "ds_read_b32 %4, %4\n\tds_read_b32 %5, %5\n\tds_read_b32 %6, %6\n\tds_read_b32 %7, %7\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(hp[0]), "=&v"(hp[1]), "=&v"(hp[2]), "=&v"(hp[3]), "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]),
+                       "=&v"(w[3])
+                     : "v"(hp_at), "v"(base2), "i"(SHIFT)
+                     : "memory");
+    } else {
+        asm volatile("ds_read_b32 %0, %16\n\tds_read_b32 %1, %16 offset:256\n\t"
+                     "ds_read_b32 %2, %16 offset:512\n\tds_read_b32 %3, %16 offset:768\n\t"
+                     "ds_read_b32 %4, %16 offset:1024\n\tds_read_b32 %5, %16 offset:1280\n\t"
+                     "ds_read_b32 %6, %16 offset:1536\n\tds_read_b32 %7, %16 offset:1792\n\t"
+                     "s_waitcnt lgkmcnt(0)\n\t"
+                     "v_lshrrev_b32 %8, %18, %0\n\tv_lshrrev_b32 %9, %18, %1\n\t"
+                     "v_lshrrev_b32 %10, %18, %2\n\tv_lshrrev_b32 %11, %18, %3\n\t"
+                     "v_lshrrev_b32 %12, %18, %4\n\tv_lshrrev_b32 %13, %18, %5\n\t"
+                     "v_lshrrev_b32 %14, %18, %6\n\tv_lshrrev_b32 %15, %18, %7\n\t"
+                     "v_lshl_add_u32 %8, %8, 2, %17\n\tv_lshl_add_u32 %9, %9, 2, %17\n\t"
+                     "v_lshl_add_u32 %10, %10, 2, %17\n\tv_lshl_add_u32 %11, %11, 2, %17\n\t"
+                     "v_lshl_add_u32 %12, %12, 2, %17\n\tv_lshl_add_u32 %13, %13, 2, %17\n\t"
+                     "v_lshl_add_u32 %14, %14, 2, %17\n\tv_lshl_add_u32 %15, %15, 2, %17\n\t"
+                     "ds_read_b32 %8, %8\n\tds_read_b32 %9, %9\n\tds_read_b32 %10, %10\n\tds_read_b32 %11, %11\n\t"
+                     "ds_read_b32 %12, %12\n\tds_read_b32 %13, %13\n\tds_read_b32 %14, %14\n\tds_read_b32 %15, %15\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : "=&v"(hp[0]), "=&v"(hp[1]), "=&v"(hp[2]), "=&v"(hp[3]), "=&v"(hp[4]), "=&v"(hp[5]), "=&v"(hp[6]),
+                       "=&v"(hp[7]), "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3]), "=&v"(w[4]), "=&v"(w[5]),
+                       "=&v"(w[6]), "=&v"(w[7])
+                     : "v"(hp_at), "v"(base2), "i"(SHIFT)
+                     : "memory");
+    }
+#else
+    for (int u = 0; u < N; ++u) hp[u] = w[u] = 0;
+    (void)hp_at; (void)base2;
+#endif
 }
 
 // plan_after_commit for the persistent commit (batch b plans batch b + kPipeLag): the plans come from
@@ -456,6 +532,10 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
     uint64_t t_start = dbg ? __builtin_amdgcn_s_memtime() : 0;
     uint64_t t_pre = 0;
     uint64_t t_s1 = 0, t_s2 = 0, t_s3 = 0, t_mark = 0;
+    // the check step's split (wave 0; trace columns 33-36): builds with -DKSCHED_COMMIT_SPLIT=1 only -- additions to this
+    // function cost a plain run through register allocation alone
+    const bool sdbg = KSCHED_COMMIT_SPLIT && dbg;
+    uint64_t t_fold = 0, t_probe = 0, t_pod = 0, t_load = 0;
     SpcSmem m;
     {
         // every array but S below 64 KB: an LDS instruction's immediate offset (16 bits) then reaches it from one
@@ -758,7 +838,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                 dup = (m.tkc[h >> 5] >> (h & 31)) & 1u;  // only export(b - 2)'s slots are taken yet
             }
             const uint64_t nm = __ballot(lane < n1 && !dup);
-            const int slot = dup ? m.own[h] : n2 + __popcll(nm & ((1ull << lane) - 1ull));
+            const int slot = dup ? m.own[h] : n2 + lanes_below(nm);
             if (lane < n1) {
                 SpcSlot &x = m.T[slot];
                 x.idx = xi.idx; x.mine = 0;
@@ -820,6 +900,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
         rmax = rcredit >= 2 * A.rescue_cap ? A.rescue_max : A.rescue_low;
     }
     int64_t placed = 0, nrounds = 0, nfail = 0, niters = 0, nseq = 0;
+    int nfull = 0;  // wave 0: guess iterations that scanned all K entries
     if (wave == 0) {
         int64_t ds2 = 0;
         double xk = -__builtin_inf();
@@ -939,9 +1020,9 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             // Guesses by fixpoint iteration, lane = pod: g_i = the first list entry of pod i that is neither
             // confirmed-taken nor proposed by a pod < i (own[pos] < i) in the previous iteration.  Pod i's
             // proposal is final once those of all pods < i are, so the fixpoint is reached after at most
-            // (cend - c) + 1 iterations and equals the sequential greedy guess order; with first touches
-            // the rule (99 %), it is reached after two.  The entries' table positions and the mask of those
-            // not confirmed-taken are loaded once per round; an iteration probes own[] only.
+            // (cend - c) + 1 iterations and equals the sequential greedy guess order (c4: 3.6 iterations per
+            // round -- the pods of a batch list much the same nodes -- and 54 % of them go past the lane's two
+            // lowest entries).  The mask of the entries not confirmed-taken is computed once per round.
             // own[] aliases pbk / pbx, which the wave-0 state (or the last check) just read as doubles: an LDS order
             // on both sides of its initialisation, so no load or store moves across it (the accesses differ in type)
             lds_order();
@@ -949,28 +1030,57 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             lds_order();
             const uint64_t fitm = __ballot(fcc != 0);  // pods with a feasible node before this round
             const bool act = lane >= c && lane < cend && ((fitm >> lane) & 1);
-            int32_t hp[K];
+            // (every gather below: lds_gather / lds_read2, all loads of a level in flight)
+            constexpr int G = K < 8 ? K : 8;
+            const uint32_t hp_at = lds_addr(m.HP + lane), own_at = lds_addr(m.own);
             uint32_t am = 0;
 #pragma unroll
-            for (int qq = 0; qq < K; ++qq) hp[qq] = m.HP[qq * 64 + lane];
+            for (int g = 0; g < K; g += G) {  // kSpcInvalid's table bit is always set: ends the list
+                int32_t hp[G], tw[G];
+                lds_gather<G, 5>(hp_at + g * 256, lds_addr(m.tkc), hp, tw);
 #pragma unroll
-            for (int qq = 0; qq < K; ++qq) {  // kSpcInvalid's table bit is always set: ends the list
-                const int pos = hp[qq];
-                am |= ((m.tkc[pos >> 5] >> (pos & 31)) & 1u) ? 0u : (1u << qq);
+                for (int u = 0; u < G; ++u) am |= (((uint32_t)tw[u] >> (hp[u] & 31)) & 1u) ? 0u : (1u << (g + u));
             }
             if (!act) am = 0;
+            // The lane's two lowest active entries: their table positions are kept in registers for the round, the
+            // other K - 2 stay in LDS (m.HP).  A lane without one (am == 0: not active, or outside [c, cend)) reads its
+            // entry 0 and own[] at that position in every iteration and never uses the values: hash_lists fills m.HP
+            // for all 64 * K (pod, entry) pairs, with kSpcInvalid where a list has no entry, and every value it
+            // writes, kSpcInvalid included, indexes inside own[] -- the statements below hide these accesses from the
+            // compiler, so that bound is kept by hand.
+            const uint32_t am1 = am & (am - 1u), amr = am1 & (am1 - 1u);
+            const int32_t q0 = am ? (int32_t)__builtin_ctz(am) : 0, q1 = am1 ? (int32_t)__builtin_ctz(am1) : 0;
+            int32_t h0, h1;
+            lds_read2(hp_at + q0 * 256, hp_at + q1 * 256, h0, h1);
             int32_t pq = -1, ph = kSpcInvalid;  // current proposal (list position, table position)
             for (int it = 0;; ++it) {
                 ++niters;
-                // the first entry not confirmed-taken and not proposed by an earlier pod: every probe of own[] in
-                // flight at once (highest entry first, so the lowest match is the one kept), no branch per entry
-                int32_t nq = -1, nh = kSpcInvalid;
-                if (am) {
+                // the first entry not confirmed-taken and not proposed by an earlier pod.  Two tiers: the two lowest
+                // active entries are probed with both loads of own[] in flight; only when some active lane finds both
+                // taken and has further active entries does the whole wave scan all K entries (a uniform branch; up to
+                // 8 table positions, then their own[] words, in flight at a time -- highest entry first, so the
+                // lowest match is the one kept).  Either tier yields the lowest active entry whose own[] >= lane.
+                int32_t nq, nh;
+                {
+                    int32_t o0, o1;
+                    lds_read2(own_at + h0 * 4, own_at + h1 * 4, o0, o1);
+                    const bool ok0 = am != 0u && o0 >= lane, ok1 = am1 != 0u && o1 >= lane;
+                    nq = ok0 ? q0 : (ok1 ? q1 : -1);
+                    nh = ok0 ? h0 : (ok1 ? h1 : kSpcInvalid);
+                    if (__ballot(amr != 0u && !ok0 && !ok1) != 0) {
+                        ++nfull;
+                        nq = -1; nh = kSpcInvalid;
 #pragma unroll
-                    for (int qq = K - 1; qq >= 0; --qq) {
-                        const bool ok = (((am >> qq) & 1u) != 0u) & (m.own[hp[qq]] >= lane);
-                        nq = ok ? qq : nq;
-                        nh = ok ? hp[qq] : nh;
+                        for (int g = K - G; g >= 0; g -= G) {
+                            int32_t hp[G], ow[G];
+                            lds_gather<G, 0>(hp_at + g * 256, own_at, hp, ow);
+#pragma unroll
+                            for (int u = G - 1; u >= 0; --u) {
+                                const bool ok = (((am >> (g + u)) & 1u) != 0u) & (ow[u] >= lane);
+                                nq = ok ? g + u : nq;
+                                nh = ok ? hp[u] : nh;
+                            }
+                        }
                     }
                 }
                 const bool changed = __ballot(act && nq != pq) != 0;
@@ -986,7 +1096,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                 my_g = act ? (pq >= 0 ? 0 : -1) : -2;
                 my_q = pq;
                 my_h = act && pq >= 0 ? ph : kSpcInvalid;
-                my_s = act && pq >= 0 ? nT + __popcll(gm & ((1ull << lane) - 1ull)) : -1;
+                my_s = act && pq >= 0 ? nT + lanes_below(gm) : -1;
             }
             const bool in = lane >= c && lane < cend;
             if (in && my_g == 0) my_g = m.LI[my_q * 64 + lane];  // the guessed node
@@ -1182,6 +1292,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             nT += ncg;
             if (f < nb) {
                 // bring the confirmed state of the pods still to come up to date with [c, f)
+                const uint64_t tf0 = sdbg ? __builtin_amdgcn_s_memtime() : 0;
                 float b2 = trk ? m.rb2[lane] : 0.0f;
                 for (int k = c; k < f; ++k) {
                     const int32_t g = __builtin_amdgcn_readlane(my_g, k);
@@ -1197,6 +1308,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                     rbk = up ? v : rbk; rbi = up ? g : rbi; rbs = up ? s : rbs;
                 }
                 if (trk) m.rb2[lane] = b2;
+                if (sdbg) t_fold += __builtin_amdgcn_s_memtime() - tf0;
             }
             if (f < cend) {
                 ++nfail;
@@ -1214,6 +1326,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                 // an overflow hands back to the guess rounds.
                 for (;;) {
                 int qf = -1;
+                const uint64_t tp0 = sdbg ? __builtin_amdgcn_s_memtime() : 0;
                 if (kf == 4) {
                     // first list entry of pod f not in T (guesses before f are confirmed, later ones void)
                     const int cvf = __builtin_amdgcn_readlane(cv, f);
@@ -1243,6 +1356,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                     }
                 }
                 kf = __builtin_amdgcn_readfirstlane(kf);
+                if (sdbg) t_probe += __builtin_amdgcn_s_memtime() - tp0;
                 bool rescued = false;
                 RescueOut ro{};
                 if constexpr (COH) {
@@ -1302,6 +1416,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                     }
                     if (kf != 0) {
                         ++placed;
+                        const uint64_t tc0 = sdbg ? __builtin_amdgcn_s_memtime() : 0;
                         int64_t b0, b1, b2;
                         uint64_t lab;
                         float pr;
@@ -1313,6 +1428,10 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                             load_rec_state<COH>(A.lists + (size_t)f * K + qf, ra, &lab, &pr);
                             b0 = ra[0]; b1 = ra[1]; b2 = ra[2];
                             s = nT++;
+                            if (sdbg) {  // diagnostics: the record's state, landed (the wait the next use would take)
+                                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                                t_load += __builtin_amdgcn_s_memtime() - tc0;
+                            }
                         } else {
                             const SpcSlot &x = m.T[s];
                             b0 = x.cur[0]; b1 = x.cur[1]; b2 = x.cur[2]; lab = x.labels; pr = x.price;
@@ -1369,6 +1488,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                         rbk = (up || keep) ? kv : rbk; rbi = up ? wi : rbi; rbs = up ? s : rbs;
                         const bool anyr = __ballot(rescan) != 0;
                         const bool anyw = RB2 && __ballot(worse) != 0;
+                        if (sdbg) t_pod += __builtin_amdgcn_s_memtime() - tc0;  // (the state load included)
                         if (RB2 && A.dbg && lane == 0 && anyw) {  // diagnostics: steps with a worsened holder / all kept
                             atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[23]), 1ull);
                             if (!anyr) atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[24]), 1ull);
@@ -1462,7 +1582,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             o.sb[0] = x.sb[0]; o.sb[1] = x.sb[1]; o.sb[2] = x.sb[2];
             o.cur[0] = x.cur[0]; o.cur[1] = x.cur[1]; o.cur[2] = x.cur[2];
             o.labels = x.labels; o.price = x.price; o.pad2 = 0;
-            const int slot = base + __popcll(mask & ((1ull << lane) - 1));
+            const int slot = base + lanes_below(mask);
             store_xrec<COH>(A.xout->e, slot, o, (uint32_t)(A.batch + 1));
         }
         base += __popcll(mask);
@@ -1511,8 +1631,12 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                               (uint64_t)nseq << 48;
         if (A.dbg) {
             A.dbg[12] += nrounds; A.dbg[13] += nfail; A.dbg[14] += 1; A.dbg[5] += niters;
+            A.dbg[8] += nfull; A.dbg[31] += nseq;
             A.dbg[0] += t_pro; A.dbg[1] += t_s1; A.dbg[2] += t_s2; A.dbg[3] += t_s3;
             if (A.trace_row) { A.trace_row[18] = t_pro; A.trace_row[19] = t_s1; A.trace_row[20] = t_s2; A.trace_row[21] = t_s3; }
+            if (KSCHED_COMMIT_SPLIT && A.trace_row) {  // the check step's split: fold, probe, commit of the pod, of it the state load
+                A.trace_row[33] = t_fold; A.trace_row[34] = t_probe; A.trace_row[35] = t_pod; A.trace_row[36] = t_load;
+            }
             A.dbg[4] += __builtin_amdgcn_s_memtime() - t_start;
             A.dbg[6] += t_pre;
         }

@@ -114,6 +114,9 @@ void print_persist_trace(ksched_ctx *c) {
                     (double)hd[17] / std::max<int64_t>(1, hd[16]), (long long)hd[18], (double)hd[19] / std::max<int64_t>(1, hd[18]),
                     (long long)hd[20], (double)hd[21] / std::max<int64_t>(1, hd[20]), (long long)hd[22]);
         if (hd[14])
+            fprintf(stderr, "persist commit guess: iterations %lld, of them past the two lowest entries (all K scanned) %lld | "
+                    "pods resolved one by one %lld\n", (long long)hd[5], (long long)hd[8], (long long)hd[31]);
+        if (hd[14])
             fprintf(stderr, "persist commit: batches=%lld rounds/batch %.3f guess iterations/round %.2f failures %lld | "
                     "cycles/batch: before the wait %.0f (other waves %.0f) entry to past the wait %.0f (poll %.0f, poll + barrier %.0f, early read sufficed %.3f, early inh read sufficed %lld of %lld) | prologue %.0f guess %.0f evaluate %.0f check %.0f total %.0f\n",
                     (long long)hd[14], (double)hd[12] / hd[14], (double)hd[5] / std::max<int64_t>(1, hd[12]),

@@ -280,9 +280,10 @@ hipError_t launch_xchg_min(const PersistArgs &a, int32_t mine, int32_t *out, hip
 // trace row: 0-15 stamps (col 13: exact rows), 16 the commit's counters, 17 its rescue waits; with
 // KSCHED_COMMIT_STAMPS 18-21 its prologue / guess / evaluate / check cycles, 22-23 prologue marks (lists hashed, all
 // waves past), 24 before the wait, 25 entry -> past the wait, 26 the inherited keys loaded early (0: after the wait),
-// 27 P1 done, 30 the lists hashed; 26-30 the check step's split (update, probe, commit,
-// rescan, state load), 31-32 the guess step's (set-up, fixpoint), 33-36 the wave-0 state's (26-36: builds with
-// KSCHED_COMMIT_SPLIT only)
+// 27 P1 done, 29 the check step's rescans, 30 the lists hashed; 33-36 the check step's split in cycles (the fold of
+// the confirmed columns, the probe of a pod resolved exactly, the commit of that pod, of it the wait for a listed
+// record's state; builds with -DKSCHED_COMMIT_SPLIT=1 only).  An earlier check split had columns 26-28 and 30; P1's
+// stamps took 26, 27 and 30 since, so the split moved to 33-36.  Free (no writer): 28, 31-32, 38-48.
 constexpr int kTraceCols = 54;  // + 37: score WG 0 behind the bound's barrier (every wave's pass 1 / seed pass done);
                                 // 49-53: the commit's rounds
 // KSCHED_JITTER (race hunting): at one in four (workgroup, batch, site) triples, sleep the wave for up to ~50 us,

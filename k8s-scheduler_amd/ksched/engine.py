@@ -293,7 +293,7 @@ class Engine:
         w = (C.c_int64 * 32)()
         self._chk(L.lib().ksched_get_commit_stamps(self._ctx, 32, w), "get_commit_stamps")
         return dict(rounds=w[12], failed_guesses=w[13], batches=w[14], early_merged=w[15], early_inh=w[29],
-                    early_inh_tried=w[30])
+                    early_inh_tried=w[30], guess_iterations=w[5], full_scans=w[8], one_by_one=w[31])
 
     def set_timing(self, on: bool, every: int = 0):
         """Sampled per-kernel HIP-event timing for the following calls (every: one batch in N)."""

@@ -130,15 +130,27 @@ def main():
         if s.any():
             print(f"  {r} rescues: {s.sum()} batches, commit mean {cm[s].mean():.1f} p50 {np.median(cm[s]):.1f} max {cm[s].max():.1f} us,"
                   f" rounds mean {rounds[s].mean():.2f}, resolved {done[s].mean():.1f}")
+    # The check step's split (columns 33-36: fold of the confirmed columns, probe, commit of the resolved pod, of it
+    # the wait for a listed record's state) is written only by a library built with -DKSCHED_COMMIT_SPLIT=1
+    # (tools/build_split.sh); the rescans (29) by every build.  Columns 31-32 (the guess step's set-up / fixpoint) have
+    # no writer in this tree (they printed as zeros) and are no longer printed.
+    split = bool((t[b][:, 33:37] != 0).any())
     print("commit time by rounds (kcycles per batch: prologue / guess / evaluate / check):")
     for lo, hi in ((0, 1), (1, 2), (2, 3), (3, 5), (5, 10), (10, 1 << 16)):
         s = (rounds >= lo) & (rounds < hi)
         if s.any():
-            # (columns 26, 27 and 30 hold P1's stamps now: the check step's update / probe / commit / state-load split is gone)
-            kc = [t[b[s], c].mean() / 1e3 for c in (18, 19, 20, 21, 29, 31, 32)]
+            kc = [t[b[s], c].mean() / 1e3 for c in (18, 19, 20, 21, 29, 33, 34, 35, 36)]
+            tail = (f"fold {kc[5]:.1f} probe {kc[6]:.1f} pod {kc[7]:.1f} [state load {kc[8]:.1f}] " if split else "")
             print(f"  rounds [{lo},{hi}): {s.sum()} batches, commit mean {cm[s].mean():.1f} max {cm[s].max():.1f} us, total"
                   f" {cm[s].sum() / 1e3:.2f} ms | {kc[0]:.1f} / {kc[1]:.1f} / {kc[2]:.1f} / {kc[3]:.1f}"
-                  f" (guess: set-up {kc[5]:.1f} fixpoint {kc[6]:.1f}; check: rescan {kc[4]:.1f})")
+                  f" (check: {tail}rescan {kc[4]:.1f})")
+    ck = [float(t[b, c].sum()) / 1e6 for c in (21, 33, 34, 35, 36, 29)]
+    if split:
+        print(f"check step, Mcycles over the call: {ck[0]:.1f} = fold {ck[1]:.1f} + probe {ck[2]:.1f} + pod {ck[3]:.1f}"
+              f" [state load {ck[4]:.1f}] + rescan {ck[5]:.1f} + rest {ck[0] - ck[1] - ck[2] - ck[3] - ck[5]:.1f}")
+    else:
+        print(f"check step, Mcycles over the call: {ck[0]:.1f}, of it rescans {ck[5]:.1f} (no split: the library was not"
+              f" built with KSCHED_COMMIT_SPLIT)")
     # which phase of the chain is the long one when the period is long
     chain = us((t[b, 4] - t[b - lag, 4]).astype(np.float64))
     print(f"chain (commit(b-L) end -> commit(b) end): mean {chain.mean():.1f} p50 {np.median(chain):.1f} us = "
