@@ -332,7 +332,8 @@ int ksched_schedule(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const in
  * A call whose gangs all have size 1 is ksched_schedule in exact mode.  KSCHED_E_INVALID (nothing changed): a gang
  * above KSCHED_GANG_MAX, bad offsets or minima, opts.nranks > 1.  Afterwards ksched_explain_batch /
  * ksched_explain_pod return KSCHED_E_STATE (they rebuild a pod's state from final placements, which a rolled-back
- * gang does not have); after a device error the node state is as unspecified as after a failed ksched_schedule. */
+ * gang does not have: ksched_schedule_full_why below collects a pod's reasons inside the run, at its turn); after a
+ * device error the node state is as unspecified as after a failed ksched_schedule. */
 #define KSCHED_GANG_MAX 1024
 int ksched_schedule_gangs(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,
                           const int64_t *req_pods, const uint64_t *selector, int64_t n_gangs, const int64_t *gang_off,
@@ -370,7 +371,8 @@ int ksched_schedule_gangs(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, co
  * keeping them in step is the caller's business, as with ksched_load_bound (FakeCluster.schedule_spread reloads the
  * table on every call).  ksched_schedule, ksched_schedule_gangs, ksched_rank, ksched_explain, ksched_explain_batch /
  * _pod and ksched_preempt neither read nor move the table; ksched_rank_full and ksched_explain_full read it.  After ksched_schedule_spread, ksched_explain_batch / ksched_explain_pod return
- * KSCHED_E_STATE: they know no spread reason (KSCHED_NUM_REASONS did not change).
+ * KSCHED_E_STATE: they know no spread reason (KSCHED_NUM_REASONS did not change); ksched_schedule_full_why below gives
+ * the reasons at a pod's turn.
  *
  * KSCHED_E_INVALID (nothing changed; a table loaded earlier survives): D or S < 1 or above the caps, S * D >
  * KSCHED_SPREAD_MAX_CELLS, a node domain outside [-1, D), a domain id in [0, D) that no node carries (the minimum
@@ -379,7 +381,8 @@ int ksched_schedule_gangs(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, co
  *
  * Out of scope: ScheduleAnyway scoring; several constraints or topology keys per pod; minDomains;
  * nodeAffinityPolicy / nodeTaintsPolicy (the minimum ranges over all domains, which is k8s's Ignore); a spread reason
- * at a pod's turn (against the current state: ksched_explain_full below); multi-rank; the batched pipeline.
+ * from this call itself (at a pod's turn: ksched_schedule_full_why below; against the current state:
+ * ksched_explain_full); multi-rank; the batched pipeline.
  *
  * Worked example (best-price, feasible domain): nodes n0 (zone A, price 0.1), n1 (A, 0.2), n2 (B, 0.5), all with ample
  * room; one group with max_skew 1 and counts 0; four enforcing pods.  Pod 0 sees A 0, B 0: every node is eligible, the
@@ -427,7 +430,8 @@ int ksched_schedule_spread(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, c
  * caller's business (FakeCluster.schedule_ext reloads the table on every call).  ksched_schedule,
  * ksched_schedule_gangs, ksched_schedule_spread, ksched_rank, ksched_explain, ksched_explain_batch / _pod and
  * ksched_preempt neither read nor move it; ksched_rank_full and ksched_explain_full read it.  After ksched_schedule_ext, ksched_explain_batch / ksched_explain_pod return KSCHED_E_STATE: they know no
- * extended-resource reason (KSCHED_NUM_REASONS did not change).
+ * extended-resource reason (KSCHED_NUM_REASONS did not change); ksched_schedule_full_why below gives the reasons at a
+ * pod's turn.
  *
  * KSCHED_E_INVALID (nothing changed; a table loaded earlier survives): n_ext outside [1, KSCHED_EXT_MAX], a null
  * node_ext, a negative request, p outside [0, 2^30), opts.nranks > 1.
@@ -486,7 +490,7 @@ int ksched_schedule_ext(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, cons
  *
  * State: the spread counts and the ext table carry over from call to call, as with the single calls;
  * ksched_read_spread / ksched_read_ext return them.  Afterwards ksched_explain_batch / ksched_explain_pod return
- * KSCHED_E_STATE.
+ * KSCHED_E_STATE (the reasons at a pod's turn: ksched_schedule_full_why below).
  *
  * KSCHED_E_INVALID (nothing changed; loaded tables survive): every invalid case of the three calls, gang_off == NULL
  * with n_gangs != 0, p outside [0, 2^30), opts.nranks > 1.
@@ -573,7 +577,7 @@ int ksched_schedule_constrained(ksched_ctx *ctx, int64_t p,
  * (FakeCluster.schedule_affinity reloads the table on every call).  ksched_schedule_full reads and moves the table,
  * ksched_rank_full and ksched_explain_full read it; no other call does either.  After
  * ksched_schedule_affinity, ksched_explain_batch / ksched_explain_pod return KSCHED_E_STATE: they know no affinity reason
- * (KSCHED_NUM_REASONS did not change).
+ * (KSCHED_NUM_REASONS did not change); ksched_schedule_full_why below gives the reasons at a pod's turn.
  *
  * KSCHED_E_INVALID (nothing changed; a table loaded earlier survives): D outside [0, KSCHED_SPREAD_MAX_DOMAINS], a node
  * domain outside [-1, D), a domain id in [0, D) that no node carries, node_domain == NULL with D > 0 and n > 0,
@@ -581,8 +585,9 @@ int ksched_schedule_constrained(ksched_ctx *ctx, int64_t p,
  *
  * Out of scope: affinity inside ksched_schedule_constrained (with gangs, spread and ext and the gang rollback:
  * ksched_schedule_full below); preferred (scored) terms; more than one affinity term per pod; more than one
- * zone key; namespaceSelector, matchLabelKeys; pod removal without a reload; affinity reasons at a pod's turn, and
- * ksched_rank under affinity (against the current state: ksched_explain_full and ksched_rank_full below); ksched_preempt
+ * zone key; namespaceSelector, matchLabelKeys; pod removal without a reload; affinity reasons from this call itself (at
+ * a pod's turn: ksched_schedule_full_why below) and ksched_rank under affinity (against the current state:
+ * ksched_explain_full and ksched_rank_full below); ksched_preempt
  * under affinity; the batched pipelines and multi-rank; the one-workgroup exact kernel.
  *
  * Worked example (best-price, feasible domain, ample room): nodes n0 (zone A, price 0.1), n1 (B, 0.2), n2 (A, 0.3), n3
@@ -653,7 +658,8 @@ int ksched_schedule_affinity(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu,
  *
  * State: the spread counts, the ext table and the affinity words carry over from call to call, as with the single calls;
  * ksched_read_spread / ksched_read_ext / ksched_read_affinity return them.  Afterwards ksched_explain_batch /
- * ksched_explain_pod return KSCHED_E_STATE.
+ * ksched_explain_pod return KSCHED_E_STATE; the same run with every NO_FIT pod's reasons at its turn is
+ * ksched_schedule_full_why below.
  *
  * KSCHED_E_INVALID (nothing changed; loaded tables survive): every invalid case of the four calls -- gang_off == NULL
  * with n_gangs != 0, p outside [0, 2^30), aff_group[i] outside [-1, 64), opts.nranks > 1 among them.
@@ -741,10 +747,11 @@ int ksched_schedule_full(ksched_ctx *ctx, int64_t p,
  * NULL selector under opts.use_labels, a NULL out_counts, opts.nranks > 1 (the tables are single-GPU; there is no shard
  * merge).  KSCHED_E_STATE before ksched_load_nodes.  n_local == 0 answers as ksched_rank does: empty lists, zero counts.
  *
- * Out of scope: dry runs of a gang (members see each other's tentative commits); ksched_preempt under constraints; the
- * reasons a pod of a finished constrained run saw at its turn (a rolled-back gang leaves no placements to rebuild from:
- * ksched_explain_batch / ksched_explain_pod still return KSCHED_E_STATE after a constrained call); multi-rank;
- * ScheduleAnyway and preferred terms.
+ * Out of scope: dry runs of a gang (members see each other's tentative commits); ksched_preempt under constraints;
+ * multi-rank; ScheduleAnyway and preferred terms.  The reasons a pod of a finished constrained run saw at its turn are
+ * not a dry run's to give -- a rolled-back gang leaves no placements to rebuild from, and ksched_explain_batch /
+ * ksched_explain_pod still return KSCHED_E_STATE after a constrained call: ksched_schedule_full_why below collects them
+ * inside the run.
  *
  * Worked example, from the end state of ksched_schedule_full's own worked example (best-price, feasible domain): n0, n1
  * in zone A, n2, n3 in B; counts A 2, B 1 with max_skew 1 (minc 1: a domain may hold at most 1); gpu column {0, 0, 1, 0};
@@ -776,6 +783,70 @@ int ksched_explain_full(ksched_ctx *ctx, int64_t req_cpu, int64_t req_mem, int64
         int32_t spread_group /* -1: none */, int32_t spread_enforce, const int64_t *req_ext /* n_ext, or NULL */,
         uint64_t member, uint64_t anti_host, uint64_t anti_zone, int32_t aff_group /* -1: none */, int32_t aff_zone,
         int64_t out_counts[KSCHED_NUM_REASONS_FULL], uint8_t *out_reason /* n_local, or NULL */);
+
+/* ---- FailedScheduling reasons at a pod's turn (added within ABI 6: probe with dlsym(lib, "ksched_schedule_full_why"); the version number did not move) ----
+ * The reference posts a FailedScheduling event at the turn of every pod that fits nowhere, with one line per node
+ * (anchor/predicate.go:127-171).  ksched_explain_batch / ksched_explain_pod keep that for ksched_schedule by rebuilding a
+ * pod's state from the call's placements; a constrained call cannot be rebuilt that way -- the state a member of a
+ * rejected gang saw held the tentative commits of its own gang, and the rollback erased them -- and ksched_explain_full
+ * answers against the state of NOW.  This call collects the reasons inside the run, at the pod's turn: the training job
+ * that came back KSCHED_GANG_REJECTED learns which member failed and why ("Insufficient amd.com/gpu on 61 nodes,
+ * anti-affinity on 3").
+ *
+ * The call IS ksched_schedule_full on the same arguments: out_idx, out_score, out_feasible and out_gang_placed are what
+ * that call returns on the same input, bit for bit, and so are the node rows, the three tables, the stats
+ * (stats.pipeline == KSCHED_PIPE_EXACT, stats.pair_evals == p * n), the NULL rules that switch a constraint off and the
+ * state rules afterwards (ksched_explain_batch / ksched_explain_pod return KSCHED_E_STATE).  With every constraint off
+ * it is therefore the at-its-turn explain of ksched_schedule in exact mode, with the codes 0-4 only.
+ *
+ * What it adds.  Every pod whose outcome at its turn is KSCHED_NO_FIT (zero eligible nodes) is one NO_FIT pod, in pod
+ * order; *out_nofit (may be NULL) is their total number, and the first min(total, why_rows) of them are recorded, row r
+ * for the r-th:
+ *   out_why_pod[r]                               the pod's index
+ *   out_why_counts[r * KSCHED_NUM_REASONS_FULL + c]   the number of local nodes whose reason is c
+ *   out_why_reason[r * n_local + j]              node j's code, for r < node_rows (node_rows <= why_rows; NULL with 0)
+ * Rows past the recorded ones: out_why_pod -1, the counts 0, the bytes 0.  why_rows == 0 is allowed: only *out_nofit is
+ * produced.
+ *
+ * The codes are ksched_rank_full's fourteen in its order -- the first failing check -- evaluated against the rows and
+ * tables AS THE POD SAW THEM AT ITS TURN: all commits of the earlier pods of the call; the tentative commits of the
+ * earlier members of its own gang, whether that gang is later accepted or rejected; the spread minimum of that moment;
+ * and the waiver of the affinity term decided from the any_host / any_zone of that moment (a waived pod never gets
+ * KSCHED_REASON_AFFINITY).  Consequences: a recorded row has column 0 equal to 0 and sums to n_local; a NO_FIT member
+ * of a rejected gang keeps its row -- the reason the gang failed; members that found a node have no row, and neither
+ * have KSCHED_NO_POSITIVE_SCORE pods (they had eligible nodes).
+ *
+ * KSCHED_E_INVALID (nothing changed; loaded tables survive): every case of ksched_schedule_full, in its order; then
+ * why_rows or node_rows negative, node_rows > why_rows, why_rows >= 2^30; a NULL out_why_pod or out_why_counts with
+ * why_rows > 0; a NULL out_why_reason with node_rows > 0; node_rows * n_local above KSCHED_WHY_MAX_NODE_BYTES.  The rows
+ * live in a device buffer the context owns, why_rows * (4 + 8 * KSCHED_NUM_REASONS_FULL) bytes and the node bytes;
+ * KSCHED_E_NOMEM when it cannot be had, with everything unchanged.
+ *
+ * Worked example: ksched_schedule_full's own.  p2 is the only NO_FIT pod (*out_nofit == 1, out_why_pod[0] == 2).  At its
+ * turn n0 and n1 hold p0 and p1 -- tentatively: their gang is rejected afterwards -- and the gpu column is {0, 0, 1, 0}.
+ * Its codes n0..n3 are 5, 5, 11, 5: three nodes without a gpu (the check comes before n0's and n1's anti-affinity), and
+ * zone B without a train pod; the counts row has 3 in column 5 and 1 in column 11.  Asked of ksched_explain_full after
+ * the call, the same pod is judged against a state where gang 0 has gone and gang 1 sits on n0 and n1 instead: this
+ * input gives the same four codes there, but in general they differ (in the tests' generated inputs, for between one half
+ * and all of a call's NO_FIT pods).
+ *
+ * Out of scope: the batched pipelines and multi-rank (opts.nranks > 1 is KSCHED_E_INVALID, as for ksched_schedule_full);
+ * per-node bytes for pods that were placed or had no positive score; a reason for KSCHED_GANG_REJECTED members beyond
+ * their gang's NO_FIT rows; the Go shim. */
+#define KSCHED_WHY_MAX_NODE_BYTES (1 << 28)  /* node_rows * n_local: the per-node bytes of one call */
+int ksched_schedule_full_why(ksched_ctx *ctx, int64_t p,
+        const int64_t *req_cpu, const int64_t *req_mem, const int64_t *req_pods, const uint64_t *selector,
+        int64_t n_gangs, const int64_t *gang_off /* n_gangs + 1, or NULL */, const int32_t *gang_min /* or NULL */,
+        const int32_t *spread_group /* p, or NULL */, const uint8_t *spread_enforce /* p, or NULL */,
+        const int64_t *req_ext /* n_ext * p, or NULL */,
+        const uint64_t *member /* p, or NULL */, const uint64_t *anti_host /* p, or NULL */,
+        const uint64_t *anti_zone /* p, or NULL */, const int32_t *aff_group /* p, or NULL */,
+        const uint8_t *aff_zone /* p, or NULL = host */,
+        int32_t *out_idx, double *out_score, int32_t *out_feasible, int32_t *out_gang_placed,
+        int64_t why_rows, int32_t *out_why_pod /* why_rows */,
+        int64_t *out_why_counts /* why_rows * KSCHED_NUM_REASONS_FULL */,
+        int64_t node_rows, uint8_t *out_why_reason /* node_rows * n_local, or NULL with node_rows 0 */,
+        int64_t *out_nofit /* or NULL */);
 
 /* Same, in two halves, with the pods staged in HBM: upload once, run many times (bench). */
 int ksched_upload_pods(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,

@@ -1,6 +1,7 @@
 // ksched_constraints.hip -- libksched: the extensions of exact mode above the kernel.  The schedule calls
 // (ksched_schedule_gangs / _spread / _ext, ksched_schedule_constrained for the three in one run,
-// ksched_schedule_affinity, and ksched_schedule_full for all four in one run) check and pack on the host, stage what
+// ksched_schedule_affinity, ksched_schedule_full for all four in one run and ksched_schedule_full_why for the same run
+// with the reasons of the pods that fit nowhere) check and pack on the host, stage what
 // they packed and run k_exact with their extension (ExactRun, ksched_exact.h); the table calls load and read
 // the context's spread, extended-resource and affinity tables; the dry runs (ksched_rank_full, ksched_explain_full) read
 // the rows and those tables through the kernels of ksched_dryrun.hip and write nothing a context holds.
@@ -17,6 +18,7 @@
 #include "ksched_full.h"
 #include "ksched_gang.h"
 #include "ksched_spread.h"
+#include "ksched_why.h"
 
 using namespace ksched;
 
@@ -92,6 +94,30 @@ int dry_begin(ksched_ctx *c, const char *name, const DryCall &call, DryPacked *k
         return fail(c, KSCHED_E_NOMEM, nm + ": host staging buffer");
     }
     return KSCHED_OK;
+}
+
+// What ksched_schedule_full and ksched_schedule_full_why share behind their checks: the packed words go up, the run
+// (kRunFull or kRunFullWhy) over them, the results, the final any words and the gangs' counts.
+int full_staged(ksched_ctx *c, ExactRun run, const char *name, const FullPacked &k, int64_t p, const int64_t *rc,
+                const int64_t *rm, const int64_t *rp, const uint64_t *sel, int32_t *oi, double *os, int32_t *of,
+                int32_t *out_gang_placed) {
+    const size_t ng = k.n_gangs;
+    const bool aff = k.aff;
+    c->all_spread = k.spread;
+    c->all_ext = k.ext;
+    c->all_aff = k.aff;
+    const int r = schedule_staged(c, run, name, p, rc, rm, rp, sel, oi, os, of,
+                                  Staged<int32_t>{c->d->gend, k.gend.data(), (size_t)p * 4},
+                                  Staged<int32_t>{c->d->gplaced, nullptr, ng * 4},
+                                  Staged<int32_t>{c->d->sword, k.swords.data(), (size_t)p * 4},
+                                  Staged<int64_t>{c->d->ereq, k.reqs.data(), k.reqs.size() * 8},
+                                  Staged<int32_t>{c->d->eword, k.ewords.data(), (size_t)p * 4},
+                                  Staged<int32_t>{c->d->aword, k.awords.data(), (size_t)p * 4},
+                                  Staged<uint64_t>{c->d->apod, k.apods.data(), k.apods.size() * 8});
+    if (r != KSCHED_OK) return r;
+    // the run's final any words, for the next call's arguments (no pods: no launch, the any words stand)
+    if (aff && p > 0) HIPCHK(c, hipMemcpy(c->aff_any, c->d->aany, sizeof(c->aff_any), hipMemcpyDeviceToHost));
+    return gang_results(c, ng, out_gang_placed);
 }
 
 uint64_t uabs64(int64_t v) { return v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v; }
@@ -389,23 +415,61 @@ int ksched_schedule_full(ksched_ctx *c, int64_t p, const int64_t *rc, const int6
     } catch (const std::bad_alloc &) {
         return fail(c, KSCHED_E_NOMEM, "schedule_full: host staging buffer");
     }
-    const size_t ng = k.n_gangs;
-    const bool aff = k.aff;
-    c->all_spread = k.spread;
-    c->all_ext = k.ext;
-    c->all_aff = k.aff;
-    const int r = schedule_staged(c, kRunFull, "schedule_full", p, rc, rm, rp, sel, oi, os, of,
-                                  Staged<int32_t>{c->d->gend, k.gend.data(), (size_t)p * 4},
-                                  Staged<int32_t>{c->d->gplaced, nullptr, ng * 4},
-                                  Staged<int32_t>{c->d->sword, k.swords.data(), (size_t)p * 4},
-                                  Staged<int64_t>{c->d->ereq, k.reqs.data(), k.reqs.size() * 8},
-                                  Staged<int32_t>{c->d->eword, k.ewords.data(), (size_t)p * 4},
-                                  Staged<int32_t>{c->d->aword, k.awords.data(), (size_t)p * 4},
-                                  Staged<uint64_t>{c->d->apod, k.apods.data(), k.apods.size() * 8});
+    return full_staged(c, kRunFull, "schedule_full", k, p, rc, rm, rp, sel, oi, os, of, gang_off ? out_gang_placed : nullptr);
+}
+
+// ksched_schedule_full, and what every pod that fits nowhere saw at its turn: one run of k_exact<kRunFullWhy>.  The
+// call's own arguments are checked behind ksched_schedule_full's (ksched_why.h), and the rows' buffer is reserved and
+// cleared, before anything is staged: a refused call and a failed allocation leave the context as it was.
+int ksched_schedule_full_why(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                             const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
+                             const int32_t *spread_group, const uint8_t *spread_enforce, const int64_t *req_ext,
+                             const uint64_t *member, const uint64_t *anti_host, const uint64_t *anti_zone,
+                             const int32_t *aff_group, const uint8_t *aff_zone, int32_t *oi, double *os, int32_t *of,
+                             int32_t *out_gang_placed, int64_t why_rows, int32_t *out_why_pod, int64_t *out_why_counts,
+                             int64_t node_rows, uint8_t *out_why_reason, int64_t *out_nofit) {
+    if (!c) return KSCHED_E_INVALID;
+    static_assert(KSCHED_NUM_REASONS_FULL == kNumWhyReasons, "why constants");
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_full_why before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_full_why is single-GPU (the exact kernel)");
+    const FullArgs args{p, n_gangs, gang_off, gang_min, spread_group, spread_enforce, req_ext, member, anti_host, anti_zone,
+                        aff_group, aff_zone};
+    FullPacked k;
+    try {
+        const char *why = nullptr;
+        if (const int code = full_check_pack(args, c->spread_S, c->ext_R, c->aff_valid, &k, &why))
+            return fail(c, code, std::string("schedule_full_why: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "schedule_full_why: host staging buffer");
+    }
+    const int64_t n = c->n_local;
+    if (const char *why = why_check(WhyArgs{why_rows, out_why_pod, out_why_counts, node_rows, out_why_reason, n}))
+        return fail(c, KSCHED_E_INVALID, std::string("schedule_full_why: ") + why);
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const WhyLayout l = why_layout(why_rows, node_rows, n);
+    if (c->d->why.reserve(l.total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, KSCHED_E_NOMEM, "schedule_full_why: the rows' device buffer");
+    }
+    // counts, total and bytes 0, every pod -1: a row the kernel does not reach reads as the header words it
+    char *w = static_cast<char *>(c->d->why.p);
+    HIPCHK(c, hipMemsetAsync(w, 0, l.total, c->stream));
+    if (why_rows > 0) HIPCHK(c, hipMemsetAsync(w + l.o_pod, 0xff, (size_t)why_rows * 4, c->stream));
+    c->why_rows = why_rows; c->why_node_rows = node_rows;
+    const int r = full_staged(c, kRunFullWhy, "schedule_full_why", k, p, rc, rm, rp, sel, oi, os, of,
+                              gang_off ? out_gang_placed : nullptr);
     if (r != KSCHED_OK) return r;
-    // the run's final any words, for the next call's arguments (no pods: no launch, the any words stand)
-    if (aff && p > 0) HIPCHK(c, hipMemcpy(c->aff_any, c->d->aany, sizeof(c->aff_any), hipMemcpyDeviceToHost));
-    return gang_results(c, ng, gang_off ? out_gang_placed : nullptr);
+    // (full_staged's sync is behind the kernel, or -- no pods, no launch -- behind the clears alone)
+    int64_t total = 0;
+    HIPCHK(c, hipMemcpy(&total, w + l.o_nofit, 8, hipMemcpyDeviceToHost));
+    if (why_rows > 0) {
+        HIPCHK(c, hipMemcpy(out_why_pod, w + l.o_pod, (size_t)why_rows * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(out_why_counts, w + l.o_counts, (size_t)why_rows * KSCHED_NUM_REASONS_FULL * 8, hipMemcpyDeviceToHost));
+    }
+    if (node_rows > 0 && n > 0) HIPCHK(c, hipMemcpy(out_why_reason, w + l.o_reason, (size_t)node_rows * (size_t)n, hipMemcpyDeviceToHost));
+    if (out_nofit) *out_nofit = total;
+    return KSCHED_OK;
 }
 
 // Ranked dry run under constraints (ksched_dryrun.hip).  Touches nothing a schedule call left behind and no table: the

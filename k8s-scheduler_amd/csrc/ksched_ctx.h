@@ -117,6 +117,7 @@ struct ksched_bufs {
     DevBuf<uint64_t> apod;                // ... ExactArgs::af_pod, kAffWords per pod
     DevBuf<uint64_t> aundo;               // ksched_schedule_full: a rejected gang's undo log of the affinity words,
                                           // ExactArgs::af_undo_slot [kGangMax][3], then af_undo_zone [G][kGangMax][2]
+    DevBuf<void> why;                     // ksched_schedule_full_why: the NO_FIT pods' rows (WhyLayout, ksched_why.h)
     DevBuf<void> xws, xbuf;               // explain: workspace; counts + NO_FIT pod list, or one pod's state + counts
     DevBuf<void> rws;                     // ksched_rank: one chunk's pods, span lists and outputs (rank_geometry's bound)
     DevBuf<void> dws;                     // ksched_rank_full / ksched_explain_full: the groups' minima, one chunk's pods,
@@ -217,6 +218,7 @@ struct ksched_ctx {
     uint64_t aff_any[2] = {};    // ... any_host, any_zone: into every affinity run by value, back from d->aany behind it
     bool all_spread = false, all_ext = false;  // ksched_schedule_constrained: the tables its kRunAll launch is given
     bool all_aff = false;        // ksched_schedule_full: its kRunFull launch is given the affinity table (with the two above)
+    int64_t why_rows = 0, why_node_rows = 0;  // ksched_schedule_full_why: the rows its kRunFullWhy launch may fill in d->why
     // pods
     int64_t p = 0;
     // batched workspace

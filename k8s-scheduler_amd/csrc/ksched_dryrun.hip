@@ -2,8 +2,8 @@
 // ksched_schedule_full's eligible in the place of fits, against the node rows AND the spread, extended-resource and
 // affinity tables as they stand.  Dry runs: no row and no table is written.
 //
-// ONE device function, dry_reason, gives the FailedScheduling code of a (pod, node) pair -- the first failing check in
-// include/ksched.h's order; 0 is eligible.  The scan ranks by it, the merge labels the ranked entries with it and the
+// ONE device function, dry_reason (ksched_reason.h: k_exact<kRunFullWhy> uses it too), gives the FailedScheduling code
+// of a (pod, node) pair -- the first failing check in include/ksched.h's order; 0 is eligible.  The scan ranks by it, the merge labels the ranked entries with it and the
 // explain kernel is nothing else, so ranking and explaining cannot disagree.
 //
 //   k_dry_min     one wave per spread group: the minimum of its D counts, into the call's workspace (the scan's
@@ -30,6 +30,7 @@
 
 #include "ksched_dryrun.h"
 #include "ksched_rank_steps.h"
+#include "ksched_reason.h"  // PodU, RowX, dry_reason
 
 namespace ksched {
 
@@ -37,16 +38,6 @@ namespace {
 
 typedef __attribute__((address_space(4))) const DryPod CPod;
 typedef __attribute__((address_space(4))) const int32_t CI32;
-
-// A pod as a wave carries it: DryPod with the spread group resolved against the table.
-struct PodU {
-    int64_t rc, rm, rp;
-    uint64_t sel, mem, anti_h, anti_z, abit;
-    int64_t er[KSCHED_EXT_MAX];
-    int32_t srow;   // the enforced group's row of the counts, -1: none
-    int64_t slim;   // ... the largest count an eligible domain may hold: max_skew + minimum - 1
-    int32_t flags;
-};
 
 __device__ __forceinline__ PodU load_pod(const DryPod *pods, int p, const DryTables &t) {
     const CPod *q = (CPod *)pods + p;
@@ -65,14 +56,6 @@ __device__ __forceinline__ PodU load_pod(const DryPod *pods, int p, const DryTab
     return u;
 }
 
-// What a lane holds of its node beside the NodeRec's fields.
-struct RowX {
-    int32_t sd;                   // spread domain (-1 also where spread is off)
-    int64_t ext[KSCHED_EXT_MAX];  // extended columns (0 where not loaded: only non-zero requests read them)
-    int32_t ad;                   // affinity zone domain
-    uint64_t nm, na;              // node_member, node_anti_host
-};
-
 __device__ __forceinline__ RowX load_rowx(const DryTables &t, int64_t j, int64_t n) {
     RowX x;
     x.sd = t.sp_dom ? t.sp_dom[j] : -1;
@@ -81,33 +64,6 @@ __device__ __forceinline__ RowX load_rowx(const DryTables &t, int64_t j, int64_t
     x.ad = -1; x.nm = 0; x.na = 0;
     if (t.af_dom) { x.ad = t.af_dom[j]; x.nm = t.af_mem[j]; x.na = t.af_anti_h[j]; }
     return x;
-}
-
-// The first failing check of pod u on a node, in include/ksched.h's order: cpu, memory, pods, labels, the extended
-// columns (zero requests skipped), the spread key, the spread skew, the pod's affinity term, its own anti-affinity
-// terms, the bound pods' anti-affinity.  0: eligible(i, j) of ksched_schedule_full.  cnt: the [S][D] counts, zone: the
-// per-domain {zone_member, zone_anti} pairs -- in LDS (the scan) or in global memory.
-template <bool LAB>
-__device__ __forceinline__ int dry_reason(const PodU &u, int64_t a0, int64_t a1, int64_t a2, uint64_t lab,
-                                          const RowX &x, const int32_t *cnt, const uint64_t *zone) {
-    int c = a0 < u.rc ? 1 : a1 < u.rm ? 2 : a2 < u.rp ? 3 : (LAB && (lab & u.sel) != u.sel) ? 4 : 0;
-    if (c == 0) {
-#pragma unroll
-        for (int r = KSCHED_EXT_MAX - 1; r >= 0; --r)  // (downwards: the lowest failing column is the one that stays)
-            if (u.er[r] != 0 && u.er[r] > x.ext[r]) c = KSCHED_REASON_EXT0 + r;
-    }
-    if (c == 0 && u.srow >= 0) {  // (the first clause is per lane, the second wave-uniform)
-        if (x.sd < 0) c = KSCHED_REASON_SPREAD_NO_KEY;
-        else if ((int64_t)cnt[u.srow + x.sd] > u.slim) c = KSCHED_REASON_SPREAD_SKEW;
-    }
-    if (c == 0 && (u.flags & kDryAff)) {
-        uint64_t zm = 0, za = 0;
-        if (x.ad >= 0) { zm = zone[2 * x.ad]; za = zone[2 * x.ad + 1]; }  // a node without the key violates no zone term
-        if ((((u.flags & kDryAffZone) ? zm : x.nm) & u.abit) != u.abit) c = KSCHED_REASON_AFFINITY;
-        else if (((x.nm & u.anti_h) | (zm & u.anti_z)) != 0) c = KSCHED_REASON_ANTI_AFFINITY;
-        else if (((x.na | za) & u.mem) != 0) c = KSCHED_REASON_EXISTING_ANTI_AFFINITY;
-    }
-    return c;
 }
 
 // The LDS of the scan and the merge: every wave's lists (scan: kDryTile pods; merge: one) and histograms.

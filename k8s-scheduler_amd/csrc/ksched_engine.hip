@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "ksched_ctx.h"
+#include "ksched_why.h"
 
 using namespace ksched;
 
@@ -467,7 +468,7 @@ int enqueue_persistent(ksched_ctx *c) {
 }
 
 // run (ExactRun, ksched_exact.h): a plain exact run, or the run of ksched_schedule_gangs / _spread / _ext /
-// _constrained / _affinity / _full over what that call staged -- always k_exact, the multi-slot kernel, under the same geometry and launch
+// _constrained / _affinity / _full / _full_why over what that call staged -- always k_exact, the multi-slot kernel, under the same geometry and launch
 // rule as a plain run
 int enqueue_exact(ksched_ctx *c, ExactRun run) {
     if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "exact mode is single-GPU; use batched mode across ranks");
@@ -517,7 +518,7 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
     // kRunFull: a rejected gang's undo log of the affinity words -- one slot record per member, one zone record per
     // workgroup and member (written before it is read: not cleared); reserved here, before the timed span begins
     const size_t undo_slot_words = (size_t)kGangMax * 3;
-    if (run == kRunFull) HIPCHK(c, c->d->aundo.reserve((undo_slot_words + (size_t)G * kGangMax * 2) * sizeof(uint64_t)));
+    if (run == kRunFull || run == kRunFullWhy) HIPCHK(c, c->d->aundo.reserve((undo_slot_words + (size_t)G * kGangMax * 2) * sizeof(uint64_t)));
     HIPCHK(c, hipMemsetAsync(c->d->slots, 0, (size_t)2 * G * 4 * sizeof(uint64_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d->err, 0, sizeof(int32_t), c->stream));
     a.G = G; a.per_wg = (int32_t)per_wg; a.slots = c->d->slots;
@@ -551,6 +552,7 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
             a.af_word = c->d->aword; a.af_pod = c->d->apod;
             break;
         case kRunFull:  // every staged word; a table only where ksched_schedule_full was given its argument; the undo log
+        case kRunFullWhy:  // ... and the rows of d->why, which ksched_schedule_full_why reserved and cleared (ksched_why.h)
             a.gang_end = c->d->gend; a.gang_placed = c->d->gplaced; a.sp_word = c->d->sword; a.ext_word = c->d->eword;
             a.af_word = c->d->aword; a.af_pod = c->d->apod;
             if (c->all_spread) {
@@ -564,6 +566,16 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
                 a.af_any_host = c->aff_any[0]; a.af_any_zone = c->aff_any[1]; a.af_D = c->aff_D;
             }
             a.af_undo_slot = c->d->aundo; a.af_undo_zone = c->d->aundo.p + undo_slot_words;
+            if (run == kRunFullWhy) {
+                const WhyLayout l = why_layout(c->why_rows, c->why_node_rows, n);
+                char *w = static_cast<char *>(c->d->why.p);
+                if (!w || c->d->why.bytes < l.total) return fail(c, KSCHED_E_STATE, "exact mode: the why rows are not reserved");
+                a.why_counts = reinterpret_cast<unsigned long long *>(w + l.o_counts);
+                a.why_nofit = reinterpret_cast<int64_t *>(w + l.o_nofit);
+                a.why_pod = reinterpret_cast<int32_t *>(w + l.o_pod);
+                a.why_reason = reinterpret_cast<uint8_t *>(w + l.o_reason);
+                a.why_rows = c->why_rows; a.why_node_rows = c->why_node_rows;
+            }
             break;
     }
     HIPCHK(c, launch_exact(run, npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,

@@ -19,7 +19,10 @@ namespace ksched {
 // rule as a plain exact run.
 // kRunFull (ksched_schedule_full): kRunAll and kRunAffinity in one launch -- the staged words of both and the tables the
 // call switched on; a rejected gang also puts back the affinity words it ORed into, from the undo log in d->aundo.
-enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3, kRunAll = 4, kRunAffinity = 5, kRunFull = 6 };
+// kRunFullWhy (ksched_schedule_full_why): kRunFull, and for every pod that fits nowhere the reason code of each node as
+// the pod saw it at its turn, into the why_* buffers the host zeroed before the launch.
+enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3, kRunAll = 4, kRunAffinity = 5, kRunFull = 6,
+                kRunFullWhy = 7 };
 
 struct ExactArgs {
     NodeRec *nodes;
@@ -67,7 +70,16 @@ struct ExactArgs {
                               // has an anti_zone word) node_anti_zone before the commit -- the winner's owner lane
     uint64_t *af_undo_zone;   // [G][kGangMax][2] per workgroup and member: {zone_member, zone_anti} of the winner's domain
                               // before the commit -- thread 0 of the workgroup
+    // k_exact<kRunFullWhy> (ksched_schedule_full_why): every field above, and what the NO_FIT pods are told.  The r-th
+    // NO_FIT pod of the call (in pod order, never rolled back) owns row r of each buffer while r < why_rows (the bytes:
+    // r < why_node_rows <= why_rows); the host clears all of them before the launch and reads them after the stream sync
+    int32_t *why_pod;         // [why_rows] the pod's index (workgroup 0, thread 0)
+    unsigned long long *why_counts;  // [why_rows][kNumWhyReasons] nodes per reason code: every wave adds its own, atomically
+    uint8_t *why_reason;      // [why_node_rows][n] every node's code, written by the thread that owns the node's slot
+    int64_t why_rows, why_node_rows;
+    int64_t *why_nofit;       // out: the call's NO_FIT pods, recorded or not (workgroup 0, thread 0, at exit)
 };
+constexpr int kNumWhyReasons = 14;      // KSCHED_NUM_REASONS_FULL: ksched_rank_full's codes
 constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
 constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
 constexpr int kSpreadMaxDomains = 1024; // KSCHED_SPREAD_MAX_DOMAINS
@@ -88,7 +100,8 @@ constexpr int kExact1Block = 1024;  // k_exact1: the whole node set in one workg
 // spread table's fields set or sp_S == 0, the extended-resource table's set or n_ext == 0; kRunAffinity: a.af_* set,
 // dynamic LDS of block * npt * 20 bytes (two 8-byte words and the domain of every slot); kRunFull: kRunAll's fields, and
 // kRunAffinity's set or a.af_dom null, with a.af_undo_* set, dynamic LDS of both (the affinity words behind the columns:
-// above 64 KiB, so the launcher raises the kernel's limit first).  (An extension never runs
+// above 64 KiB, so the launcher raises the kernel's limit first); kRunFullWhy: kRunFull's fields and a.why_* set, the
+// same dynamic LDS.  (An extension never runs
 // k_exact1: the one-workgroup kernel knows no gang log and no spread, extended-resource or affinity table.)
 hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
                         bool cooperative, hipStream_t s);

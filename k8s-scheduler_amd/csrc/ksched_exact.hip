@@ -2,9 +2,10 @@
 // extended resources -- each alone, or all three composed -- and inter-pod affinity, alone), the one-workgroup k_exact1,
 // and their launchers.
 // Compiled with -ffp-contract=off: every double op rounds individually, exactly like the Go reference.
-// Three objects, as ksched_pipe.hip's three (-DKSCHED_EXACT_PART): part 0 is every kind but affinity and full, k_exact1
+// Four objects, as ksched_pipe.hip's three (-DKSCHED_EXACT_PART): part 0 is every kind but affinity and full, k_exact1
 // and the launchers; part 1 is the affinity kind's 40 instantiations behind launch_exact_affinity; part 2 the full
-// kind's (gangs, spread, extended resources and affinity composed) behind launch_exact_full.
+// kind's (gangs, spread, extended resources and affinity composed) behind launch_exact_full; part 3 the full kind with
+// the at-its-turn reasons of the pods that fit nowhere (kRunFullWhy) behind launch_exact_full_why.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -14,6 +15,7 @@
 
 #include "ksched_exact.h"
 #include "ksched_kernels.h"  // KSCHED_DISPATCH, kErrExactExchange
+#include "ksched_reason.h"   // PodU, RowX, dry_reason: k_exact<kRunFullWhy>
 
 #ifndef KSCHED_EXACT_PART
 #define KSCHED_EXACT_PART 0
@@ -25,6 +27,8 @@ hipError_t launch_exact_affinity(int npt, int prio, int dom, bool lab, bool f53,
                                  hipStream_t s);  // part 1
 hipError_t launch_exact_full(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
                              hipStream_t s);  // part 2
+hipError_t launch_exact_full_why(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
+                                 hipStream_t s);  // part 3
 
 namespace {
 
@@ -197,10 +201,20 @@ __device__ __forceinline__ uint64_t *aff_table() {
 //   thread, same address: program order, no fence).  The walk's closing barrier gains one more workgroup-uniform reason:
 //   a logged member moved a zone word (its af_word, its words and its winner's domain: uniform loads from arrays nobody
 //   writes).  No exchange, no wait, the tag and parity sequence unchanged.
+// WHY (ksched_schedule_full_why): FULL, and where the decision is NO_FIT -- the same in every
+//   thread of every workgroup, so a pod that finds a node pays one uniform branch -- every thread gives each slot it owns
+//   its reason code at this pod's turn: dry_reason (ksched_reason.h), the function the dry runs explain with, over the
+//   row registers, the columns, domains and words in LDS and the pod's words after the waiver.  The state is the one a
+//   rollback would erase: the tentative commits of the earlier members of the pod's own gang are in it.  The codes go to
+//   why_reason (a byte per node, consecutive lanes consecutive bytes) and, summed per wave in packed fields, to the
+//   pod's row of why_counts with one device-scope integer atomicAdd per wave for the codes that occur (integer sums: any
+//   order).  Every thread counts the NO_FIT pods in a scalar; a rollback never touches it.  Nothing here feeds a
+//   decision: no new LDS, barrier, exchange or wait, the tag and parity sequence unchanged.
 // ------------------------------------------------------------------------------------------------
 template <int NPT, int PRIO, int DOM, bool LAB, bool F53, ExactRun RUN>
 __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
-    constexpr bool FULL = RUN == kRunFull;
+    constexpr bool WHY = RUN == kRunFullWhy;
+    constexpr bool FULL = RUN == kRunFull || WHY;
     constexpr bool ALL = RUN == kRunAll || FULL, AFF = RUN == kRunAffinity || FULL;
     constexpr bool GANG = RUN == kRunGang || ALL, SPREAD = RUN == kRunSpread || ALL, EXT = RUN == kRunExt || ALL;
     const int tid = threadIdx.x;
@@ -304,6 +318,7 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
     if (tid == 0) s_abort = 0;
     [[maybe_unused]] std::conditional_t<GANG, GangState, GangNone> gs;  // (nothing in the plain kernels)
     [[maybe_unused]] int32_t *const s_log = gang_log<GANG>();
+    [[maybe_unused]] int64_t nofit = 0;  // WHY: the NO_FIT pods so far, the same in every thread; never rolled back
 
     for (int64_t i = 0; i < A.pods.p; ++i) {
         const int par = (int)(i & 1);
@@ -471,6 +486,60 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
         double osc = 0.0;
         if (gc == 0) {
             oidx = -1;  // NO_FIT (anchor/schedule.go:74-76)
+            if constexpr (WHY) {
+                // the reasons this pod saw: the rows, columns and words exactly as its scan above read them -- nothing
+                // has been committed since, and the next writer of either table (thread 0, at a later pod's commit or
+                // behind the first barrier of this gang's walk) comes after a barrier that this thread reaches only
+                // once it is through here.  Nothing below feeds a decision.
+                const int64_t row = nofit++;
+                if (__builtin_expect(row < A.why_rows, 0)) {  // (uniform, and rare beside the pods that find a node)
+                    PodU u;
+                    u.rc = rc; u.rm = rm; u.rp = rp; u.sel = sel;
+                    u.mem = pmem; u.anti_h = pah; u.anti_z = paz; u.abit = pabit;  // (pabit: after the waiver)
+#pragma unroll
+                    for (int r = 0; r < kExtMax; ++r) u.er[r] = er[r];
+                    u.srow = enf ? srow : -1; u.slim = slim;
+                    u.flags = aword != 0 ? kDryAff | (azone ? kDryAffZone : 0) : 0;
+                    const bool bytes = row < A.why_node_rows;
+                    uint64_t h0 = 0, h1 = 0;  // this lane's slots per code: code c in byte c & 7 of h[c >> 3]
+#pragma unroll
+                    for (int k = 0; k < NPT; ++k) {
+                        if (id[k] != kNoIdx) {
+                            RowX x;
+                            x.sd = enf ? s_dom[k * kExactBlock] : -1;
+#pragma unroll
+                            for (int r = 0; r < kExtMax; ++r)
+                                x.ext[r] = (eword >> r & 1) ? ext[r * kExtCol + k * kExactBlock] : 0;
+                            x.ad = -1; x.nm = 0; x.na = 0;
+                            if (aword != 0) {
+                                x.nm = af_mem[k * kExactBlock]; x.na = af_anti[k * kExactBlock];
+                                x.ad = af_dom[k * kExactBlock];
+                            }
+                            const int c = dry_reason<LAB>(u, a0[k], a1[k], a2[k], lab[k], x, sp->cnt,
+                                                          reinterpret_cast<const uint64_t *>(zone));
+                            const uint64_t one = 1ull << ((c & 7) * 8);
+                            h0 += c < 8 ? one : 0ull;
+                            h1 += c < 8 ? 0ull : one;
+                            if (bytes) A.why_reason[row * A.n + id[k]] = (uint8_t)c;  // consecutive lanes, consecutive bytes
+                        }
+                        // one slot at a time: eight slots' gathers in flight at once would take their registers from
+                        // the rows, which the scan of every pod wants resident
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    // the wave's sums: even and odd bytes widened apart into four 16-bit fields a word (at most 64 lanes
+                    // x 8 slots in a field), as ksched_dryrun.hip's hist_flush does; lane c then holds code c's count --
+                    // field (c & 7) >> 1 of word (c >> 3) * 2 + (c & 1) -- and adds it to the row where it is not zero
+                    constexpr uint64_t kEven = 0x00ff00ff00ff00ffull;
+                    const uint64_t s0 = (uint64_t)wave_sum_i64((int64_t)(h0 & kEven));
+                    const uint64_t s1 = (uint64_t)wave_sum_i64((int64_t)((h0 >> 8) & kEven));
+                    const uint64_t s2 = (uint64_t)wave_sum_i64((int64_t)(h1 & kEven));
+                    const uint64_t s3 = (uint64_t)wave_sum_i64((int64_t)((h1 >> 8) & kEven));
+                    const uint64_t sw = (lane & 8) ? ((lane & 1) ? s3 : s2) : ((lane & 1) ? s1 : s0);
+                    const unsigned long long mine = (sw >> (16 * ((lane & 7) >> 1))) & 0xffffull;
+                    if (lane < kNumWhyReasons && mine != 0) atomicAdd(A.why_counts + row * kNumWhyReasons + lane, mine);
+                    if (g == 0 && tid == 0) A.why_pod[row] = (int32_t)i;
+                }
+            }
         } else if (gi == kNoIdx) {
             oidx = -2;  // NO_POSITIVE_SCORE (reference: nil node, anchor/priorities.go:55-62)
         } else {
@@ -704,6 +773,9 @@ __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
             for (int c = tid; c < cells; c += kExactBlock) A.sp_counts[c] = sp->cnt[c];
         }
     }
+    if constexpr (WHY) {
+        if (g == 0 && tid == 0) *A.why_nofit = nofit;
+    }
 }
 
 #if KSCHED_EXACT_PART == 0
@@ -857,7 +929,7 @@ __global__ __launch_bounds__(BS) void k_exact1(ExactArgs A) {
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-// kRunFull (part 2): hipFuncAttributeMaxDynamicSharedMemorySize belongs to a kernel on ONE device, and a context chooses
+// kRunFull, kRunFullWhy (parts 2, 3): hipFuncAttributeMaxDynamicSharedMemorySize belongs to a kernel on ONE device, and a context chooses
 // its device: the (device ordinal, kernel) pairs that have it, set at the pair's first launch as launch_stream_kernel
 // does.  Contexts run on threads of their own.
 [[maybe_unused]] hipError_t full_lds_limit(const void *fn, size_t most) {
@@ -875,7 +947,7 @@ namespace {
 
 template <int NPT, int PRIO, int DOM, bool LAB, bool F53, ExactRun RUN>
 hipError_t exact_one(const ExactArgs &a, int block, bool coop, hipStream_t s) {
-    constexpr bool FULL = RUN == kRunFull;
+    constexpr bool FULL = RUN == kRunFull || RUN == kRunFullWhy;
     constexpr bool EXT = RUN == kRunExt || RUN == kRunAll;
     auto fn = k_exact<NPT, PRIO, DOM, LAB, F53, RUN>;
     // EXT: the workgroup's slots of every column (ext_table), at most kExtMax * 256 * 8 * 8 B = 64 KiB (kRunAll without
@@ -926,6 +998,7 @@ hipError_t exact_run(ExactRun run, int npt, const ExactArgs &a, int block, bool 
         case kRunAll: return exact_npt<PRIO, DOM, LAB, F53, kRunAll>(npt, a, block, coop, s);
         case kRunAffinity: break;  // (part 1: launch_exact_affinity)
         case kRunFull: break;      // (part 2: launch_exact_full)
+        case kRunFullWhy: break;   // (part 3: launch_exact_full_why)
     }
     return hipErrorInvalidValue;
 }
@@ -997,6 +1070,7 @@ hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool
                 return hipErrorInvalidValue;
             return launch_exact_affinity(npt, prio, dom, lab, f53, a, block, coop, s);
         case kRunFull:  // kRunAll's and kRunAffinity's checks, "no table" (af_dom null) accepted for affinity too
+        case kRunFullWhy:  // ... and the buffers of the reasons: rows of bytes only where there are rows at all
             if (!a.gang_end || !a.sp_word || !a.ext_word || !a.af_word || !a.af_undo_slot || !a.af_undo_zone)
                 return hipErrorInvalidValue;
             if (a.sp_S != 0 && (!a.sp_dom || !a.sp_counts || !a.sp_skew || a.sp_D < 1 || a.sp_S < 1 ||
@@ -1007,7 +1081,11 @@ hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool
                              a.af_D < 0 || a.af_D > kSpreadMaxDomains))
                 return hipErrorInvalidValue;
             if (!a.af_dom && a.af_D != 0) return hipErrorInvalidValue;
-            return launch_exact_full(npt, prio, dom, lab, f53, a, block, coop, s);
+            if (run == kRunFull) return launch_exact_full(npt, prio, dom, lab, f53, a, block, coop, s);
+            if (!a.why_nofit || a.why_rows < 0 || a.why_node_rows < 0 || a.why_node_rows > a.why_rows ||
+                (a.why_rows > 0 && (!a.why_pod || !a.why_counts)) || (a.why_node_rows > 0 && !a.why_reason))
+                return hipErrorInvalidValue;
+            return launch_exact_full_why(npt, prio, dom, lab, f53, a, block, coop, s);
         default: return hipErrorInvalidValue;
     }
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact_run<P_, D_, L_, F_>(run, npt, a, block, coop, s)));
@@ -1021,10 +1099,15 @@ hipError_t launch_exact_affinity(int npt, int prio, int dom, bool lab, bool f53,
                                  hipStream_t s) {
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, kRunAffinity>(npt, a, block, coop, s)));
 }
-#else
+#elif KSCHED_EXACT_PART == 2
 hipError_t launch_exact_full(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
                              hipStream_t s) {
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, kRunFull>(npt, a, block, coop, s)));
+}
+#else
+hipError_t launch_exact_full_why(int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block, bool coop,
+                                 hipStream_t s) {
+    KSCHED_DISPATCH(prio, dom, lab, f53, (exact_npt<P_, D_, L_, F_, kRunFullWhy>(npt, a, block, coop, s)));
 }
 #endif
 

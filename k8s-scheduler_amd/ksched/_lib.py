@@ -37,6 +37,7 @@ NUM_REASONS = 5
 REASON_EXT0, REASON_SPREAD_NO_KEY, REASON_SPREAD_SKEW = 5, 9, 10
 REASON_AFFINITY, REASON_ANTI_AFFINITY, REASON_EXISTING_ANTI_AFFINITY = 11, 12, 13
 NUM_REASONS_FULL = 14
+WHY_MAX_NODE_BYTES = 1 << 28  # KSCHED_WHY_MAX_NODE_BYTES: node_rows * n of one ksched_schedule_full_why
 RANK_MAX = 64  # KSCHED_RANK_MAX: entries ksched_rank keeps per pod
 GANG_MAX = 1024  # KSCHED_GANG_MAX: members of one gang
 # ksched_load_spread's caps: domains, groups, and groups * domains (the exact kernel's per-workgroup LDS table)
@@ -156,6 +157,9 @@ SIGNATURES = [
                                            F64P, I32P]),
     ("ksched_schedule_full", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, C.c_int64, I64P, I32P, I32P, U8P, I64P,
                                        U64P, U64P, U64P, I32P, U8P, I32P, F64P, I32P, I32P]),
+    ("ksched_schedule_full_why", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, C.c_int64, I64P, I32P, I32P, U8P, I64P,
+                                           U64P, U64P, U64P, I32P, U8P, I32P, F64P, I32P, I32P, C.c_int64, I32P, I64P,
+                                           C.c_int64, U8P, I64P]),
     ("ksched_rank_full", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, I32P, U8P, I64P, U64P, U64P, U64P, I32P, U8P,
                                    C.c_int32, I32P, F64P, U8P, I32P, I32P, I64P]),
     ("ksched_explain_full", C.c_int, [CTX, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, I64P,

@@ -311,7 +311,7 @@ class Engine:
         return self.results()
 
     def _schedule_with(self, name, req_cpu, req_mem, req_pods, selector, extra, tail=()):
-        """What schedule_gangs / schedule_spread / schedule_ext / schedule_constrained / schedule_affinity / schedule_full share: the contiguous request arrays and their length
+        """What schedule_gangs / schedule_spread / schedule_ext / schedule_constrained / schedule_affinity / schedule_full / schedule_full_why share: the contiguous request arrays and their length
         check, the three outputs, the call of ksched_<name> -- extra(p), the extension's arguments (checked against
         the pod count), go between the selectors and the outputs, tail after them -- and self.p.  Returns (idx,
         score, feasible)."""
@@ -490,6 +490,14 @@ class Engine:
         back to their values before the gang's first member.  gang_off, group and req_ext switch their constraint on as
         in schedule_constrained(); affinity is on where any of its five arguments is given (None then: zeros, no
         group).  Returns (idx, score, feasible, gang_placed); gang_placed is empty when gang_off is None."""
+        extra, gp = self._full_args(gang_off, gang_min, group, enforce, req_ext, member, anti_host, anti_zone, aff_group,
+                                    aff_zone)
+        return self._schedule_with("schedule_full", req_cpu, req_mem, req_pods, selector, extra,
+                                   (L.ptr(gp, C.c_int32),)) + (gp,)
+
+    def _full_args(self, gang_off, gang_min, group, enforce, req_ext, member, anti_host, anti_zone, aff_group, aff_zone):
+        """schedule_full's and schedule_full_why's constraint arguments as contiguous arrays: (extra, gang_placed) for
+        _schedule_with, extra(p) checking every length against the pod count."""
         off = None if gang_off is None else _i64(gang_off)
         ng = 0 if off is None else off.shape[0] - 1
         gmin = None if gang_min is None or off is None else np.ascontiguousarray(gang_min, dtype=np.int32)
@@ -509,8 +517,36 @@ class Engine:
             return ((ng, L.ptr(off, C.c_int64), L.ptr(gmin, C.c_int32), L.ptr(gr, C.c_int32), L.ptr(en, C.c_uint8),
                      L.ptr(re_, C.c_int64)) + tuple(L.ptr(m, C.c_uint64) for m in masks) +
                     (L.ptr(ag, C.c_int32), L.ptr(az, C.c_uint8)))
-        return self._schedule_with("schedule_full", req_cpu, req_mem, req_pods, selector, extra,
-                                   (L.ptr(gp, C.c_int32),)) + (gp,)
+        return extra, gp
+
+    def schedule_full_why(self, req_cpu, req_mem, req_pods, selector, gang_off=None, gang_min=None, group=None,
+                          enforce=None, req_ext=None, member=None, anti_host=None, anti_zone=None, aff_group=None,
+                          aff_zone=None, why_rows=None, node_rows=0, trim=True):
+        """schedule_full(), and what every pod that fits nowhere saw AT ITS TURN (ksched_schedule_full_why): the same
+        launch, the same results and state, and for the first why_rows (None: the pod count) NO_FIT pods, in pod order,
+        the nodes per reason code -- against the rows and tables of that moment, the tentative commits of the pod's own
+        gang included, which no later call can see -- and for the first node_rows of them every node's code.  Returns
+        (idx, score, feasible, gang_placed, why) with why = (pods int32[r], counts int64[r, NUM_REASONS_FULL], reasons
+        uint8[min(r, node_rows), n] | None (node_rows 0), nofit): r = min(nofit, why_rows) recorded rows, nofit the
+        call's NO_FIT pods in all.  trim=False returns all why_rows / node_rows rows as the library filled them: -1
+        and zeros past the recorded ones."""
+        extra, gp = self._full_args(gang_off, gang_min, group, enforce, req_ext, member, anti_host, anti_zone, aff_group,
+                                    aff_zone)
+        wr = _i64(req_cpu).shape[0] if why_rows is None else int(why_rows)
+        nr, n = int(node_rows), max(self.n, 0)
+        # (the library refuses shapes these cannot hold before it writes: never a buffer sized from a refused argument)
+        pods = np.empty(max(wr, 0), np.int32)
+        counts = np.empty((max(wr, 0), L.NUM_REASONS_FULL), np.int64)
+        ok = 0 <= nr <= wr and nr * n <= L.WHY_MAX_NODE_BYTES
+        reasons = np.empty((nr, n), np.uint8) if nr > 0 and ok else None
+        nofit = np.zeros(1, np.int64)
+        out = self._schedule_with("schedule_full_why", req_cpu, req_mem, req_pods, selector, extra,
+                                  (L.ptr(gp, C.c_int32), wr, L.ptr(pods if wr > 0 else None, C.c_int32),
+                                   L.ptr(counts if wr > 0 else None, C.c_int64), nr, L.ptr(reasons, C.c_uint8),
+                                   L.ptr(nofit, C.c_int64)))
+        total = int(nofit[0])
+        r = min(total, wr) if trim else wr
+        return out + (gp, (pods[:r], counts[:r], None if nr == 0 else reasons[:min(r, nr)], total))
 
     def rank_full(self, req_cpu, req_mem, req_pods, selector=None, k: int = 16, group=None, enforce=None, req_ext=None,
                   member=None, anti_host=None, anti_zone=None, aff_group=None, aff_zone=None):

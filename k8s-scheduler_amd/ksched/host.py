@@ -644,13 +644,14 @@ class FakeCluster:
 
     def _resolve(self, pods, idx, why=None):
         """One engine call's per-pod results as the (pod, node | Exception) list, in order: NO_FIT posts a
-        FailedScheduling event (with the per-node lines of why[k], where the call has them for pod k) and gives a
-        FitError, NO_POSITIVE_SCORE a NilNodeError, any other index binds the pod to that node."""
+        FailedScheduling event (with the per-node lines of why[k], where the call has them for pod k: its reason codes,
+        or the finished text) and gives a FitError, NO_POSITIVE_SCORE a NilNodeError, any other index binds the pod to
+        that node."""
         out = []
         for k, (pod, i) in enumerate(zip(pods, idx)):
             if i == L.NO_FIT:
-                msg = (self.failed_scheduling_message(pod, why[k]) if why and k in why
-                       else f"pod ({pod.name}) failed to fit in any node")
+                msg = ((why[k] if isinstance(why[k], str) else self.failed_scheduling_message(pod, why[k]))
+                       if why and k in why else f"pod ({pod.name}) failed to fit in any node")
                 self.events.append(dict(reason="FailedScheduling", message=msg, type="Warning",
                                         involved=pod.name))
                 out.append((pod, FitError(f"Unable to schedule pod ({pod.name}) failed to fit in any node")))
@@ -680,7 +681,7 @@ class FakeCluster:
         in order.  An accepted gang's placed members are bound in order; a rejected gang binds nothing and posts one
         FailedScheduling event per member.  Returns (pod, node | Exception) in the gangs' order -- GangRejected for
         a member that found a node in a rejected gang.  (No per-node "fit failure" lines: a rolled-back gang
-        leaves no placements to rebuild a pod's state from.)"""
+        leaves no placements to rebuild a pod's state from; schedule_full_why collects them at the pod's turn.)"""
         pending = self.unscheduled_pods() if pending is None else pending
         pods, off, gmin = group_gangs(pending)
         rc, rm, rp = pack_pods(pods)
@@ -688,8 +689,9 @@ class FakeCluster:
         idx, _, _, placed = self.engine.schedule_gangs(rc, rm, rp, sel, off, gmin)
         return self._resolve_gangs(pods, off, gmin, idx, placed)
 
-    def _resolve_gangs(self, pods, off, gmin, idx, placed):
-        """A gang call's per-pod results, gang by gang, as the (pod, node | Exception) list (see schedule_gangs)."""
+    def _resolve_gangs(self, pods, off, gmin, idx, placed, why=None):
+        """A gang call's per-pod results, gang by gang, as the (pod, node | Exception) list (see schedule_gangs).  why:
+        the FailedScheduling text of the NO_FIT pods the call has one for, by position in pods (schedule_full_why)."""
         out = []
         for g in range(len(gmin)):
             lo, hi = int(off[g]), int(off[g + 1])
@@ -697,7 +699,7 @@ class FakeCluster:
             found = int(np.sum((idx[lo:hi] >= 0) | (idx[lo:hi] == L.GANG_REJECTED)))
             rejected = found < int(gmin[g])
             assert int(placed[g]) == (0 if rejected else found)
-            for pod, i in zip(pods[lo:hi], idx[lo:hi]):
+            for k, (pod, i) in enumerate(zip(pods[lo:hi], idx[lo:hi]), lo):
                 if i == L.GANG_REJECTED:
                     msg = (f"pod ({pod.name}) rejected with its gang ({gname}): {found} of {hi - lo} members placed, "
                            f"{int(gmin[g])} needed")
@@ -707,7 +709,7 @@ class FakeCluster:
                 if i == L.NO_POSITIVE_SCORE and rejected:
                     self.events.append(dict(reason="FailedScheduling", type="Warning", involved=pod.name,
                                             message=f"pod ({pod.name}) found no node with a positive score"))
-                out += self._resolve([pod], [i])
+                out += self._resolve([pod], [i], {0: why[k]} if why and k in why else None)
         return out
 
     def schedule_spread(self, pending: Optional[List[Pod]] = None):
@@ -715,7 +717,8 @@ class FakeCluster:
         ksched_schedule_spread): the spread table is reloaded from self.pods' bound pods on every call, then one
         engine call resolves every pending pod in order and the binds follow.  Returns (pod, node | Exception); a
         pod that fits nowhere its constraint allows gets the usual FailedScheduling event (without per-node lines: the at-its-turn explain
-        calls know no spread reason; explain_pod_full gives them against the current state)."""
+        calls know no spread reason; explain_pod_full gives them against the current state, schedule_full_why at the
+        pod's turn)."""
         pending = self.unscheduled_pods() if pending is None else pending
         node_domain, skew, counts, group, enforce = spread_tables(self.nodes, [p for p in self.pods if p.node_name],
                                                                   pending)
@@ -730,7 +733,8 @@ class FakeCluster:
         ksched_schedule_affinity): the affinity table is reloaded from self.pods' bound pods on every call, then one
         engine call resolves every pending pod in order and the binds follow.  Returns (pod, node | Exception); a pod
         that fits nowhere its terms allow gets the usual FailedScheduling event (without per-node lines: the at-its-turn
-        explain calls know no affinity reason; explain_pod_full gives them against the current state)."""
+        explain calls know no affinity reason; explain_pod_full gives them against the current state, schedule_full_why
+        at the pod's turn)."""
         pending = self.unscheduled_pods() if pending is None else pending
         t = affinity_tables(self.nodes, [p for p in self.pods if p.node_name], pending)
         self.engine.load_affinity(*t[:4])
@@ -744,7 +748,7 @@ class FakeCluster:
         predicate: the table is reloaded from self.pods' bound pods on every call, then one engine call resolves every
         pending pod in order and the binds follow.  Returns (pod, node | Exception); a pod that fits nowhere gets the
         usual FailedScheduling event (without per-node lines: the at-its-turn explain calls know no extended-resource
-        reason; explain_pod_full gives them against the current state)."""
+        reason; explain_pod_full gives them against the current state, schedule_full_why at the pod's turn)."""
         pending = self.unscheduled_pods() if pending is None else pending
         _, node_ext, req_ext = ext_tables(self.nodes, [p for p in self.pods if p.node_name], pending)
         self.engine.load_ext(node_ext)
@@ -792,6 +796,35 @@ class FakeCluster:
         sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
         idx, _, _, placed = self.engine.schedule_full(rc, rm, rp, sel, off, gmin, group, enforce, req_ext, *t[4:])
         return self._resolve_gangs(pods, off, gmin, idx, placed)
+
+    def schedule_full_why(self, pending: Optional[List[Pod]] = None, node_rows: Optional[int] = None):
+        """schedule_full whose FailedScheduling events carry the reference's per-node lines (ksched_schedule_full_why):
+        for every pod that fits nowhere -- a member of a gang included, accepted or rejected -- one "fit failure on node
+        (...): ..." line per node with the reason the pod saw AT ITS TURN, the tentative placements of its own gang
+        included, in kube-scheduler's wordings (REASON_TEXT_FULL, an extended column by its resource's name).
+        node_rows: the number of such pods that get the lines (None: all of them); the others get the plain event.
+        Everything else -- tables, order, binds, GangRejected, return value -- is schedule_full's."""
+        pending = self.unscheduled_pods() if pending is None else pending
+        pods, off, gmin = group_gangs(pending)
+        bound = [p for p in self.pods if p.node_name]
+        node_domain, skew, counts, group, enforce = spread_tables(self.nodes, bound, pods)
+        names, node_ext, req_ext = ext_tables(self.nodes, bound, pods)
+        t = affinity_tables(self.nodes, bound, pods)
+        self.engine.load_spread(node_domain, skew, counts)
+        self.engine.load_ext(node_ext)
+        self.engine.load_affinity(*t[:4])
+        rc, rm, rp = pack_pods(pods)
+        sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
+        rows = len(pods) if node_rows is None else min(int(node_rows), len(pods))
+        idx, _, _, placed, (wpod, _, reasons, _) = self.engine.schedule_full_why(
+            rc, rm, rp, sel, off, gmin, group, enforce, req_ext, *t[4:], why_rows=rows, node_rows=rows)
+        why = {}
+        for r in range(0 if reasons is None else len(reasons)):
+            k = int(wpod[r])
+            lines = [f"fit failure on node ({self.nodes[j].name}): {L.reason_text_full(int(c), names)}"
+                     for j, c in enumerate(reasons[r]) if c != L.REASON_FIT]
+            why[k] = f"pod ({pods[k].name}) failed to fit in any node\n" + "\n".join(lines)
+        return self._resolve_gangs(pods, off, gmin, idx, placed, why)
 
     def schedule_pod(self, pod: Pod, selector: Optional[int] = None):
         """schedulePod (anchor/schedule.go:68-89) for a single pod."""
