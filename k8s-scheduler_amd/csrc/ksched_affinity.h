@@ -49,6 +49,13 @@ inline void aff_derive(int64_t n_local, int32_t n_domains, const int32_t *node_d
 
 constexpr int kAffPodWords = 4;  // ExactArgs::af_pod: member, anti_host, anti_zone, the affinity term's group bit
 
+// Where affinity is optional (the composed schedule calls, the dry runs) it is on when at least one of its five
+// pointers is given.
+inline bool affinity_on(const uint64_t *member, const uint64_t *anti_host, const uint64_t *anti_zone,
+                        const int32_t *aff_group, const uint8_t *aff_zone) {
+    return member || anti_host || anti_zone || aff_group || aff_zone;
+}
+
 // The pods' arguments, and for each pod ExactArgs::af_word -- 0 where the pod has no group and no term, else 1 | (its
 // affinity term is of zone scope) << 1 -- and its kAffPodWords words of ExactArgs::af_pod.  Any array may be null:
 // zeros, or -1 for aff_group.

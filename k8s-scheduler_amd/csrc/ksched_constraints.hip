@@ -1,8 +1,6 @@
-// ksched_constraints.hip -- libksched: the extensions of exact mode above the kernel.  The schedule calls
-// (ksched_schedule_gangs / _spread / _ext, ksched_schedule_constrained for the three in one run,
-// ksched_schedule_affinity, ksched_schedule_full for all four in one run and ksched_schedule_full_why for the same run
-// with the reasons of the pods that fit nowhere) check and pack on the host, stage what
-// they packed and run k_exact with their extension (ExactRun, ksched_exact.h); the table calls load and read
+// ksched_constraints.hip -- libksched: the constraints of exact mode above the kernel.  The constrained schedule calls
+// (ksched_schedule_*) go one way: each names its kind of k_exact (exact_kind, ksched_exact.h), and schedule_kind checks
+// and packs on the host for that kind (ksched_full.h), stages what was packed and runs; the table calls load and read
 // the context's spread, extended-resource and affinity tables; the dry runs (ksched_rank_full, ksched_explain_full) read
 // the rows and those tables through the kernels of ksched_dryrun.hip and write nothing a context holds.
 #include <algorithm>
@@ -24,10 +22,20 @@ using namespace ksched;
 
 namespace {
 
-// One array an extension's call stages for the kernel: the context's buffer, the packed host array (null: an output
-// of the kernel, reserved only) and its bytes.
+// The pods' requests and the results' arrays of a schedule call, as include/ksched.h names them.
+struct PodIO {
+    const int64_t *rc, *rm, *rp;
+    const uint64_t *sel;
+    int32_t *oi;
+    double *os;
+    int32_t *of;
+};
+
+// One array a call stages for the kernel where its kind carries the array's constraint (on): the context's buffer, the
+// packed host array (null: an output of the kernel, reserved only) and its bytes.
 template <class T>
 struct Staged {
+    bool on;
     DevBuf<T> &buf;
     const T *host;
     size_t bytes;
@@ -37,14 +45,13 @@ struct Staged {
 // staged arrays are reserved and copied in the stream of the kernel that reads them -- finished before the host arrays
 // go (ksched_upload_pods) -- then the run over them, the sync on both outcomes, and the results.
 template <class... S>
-int schedule_staged(ksched_ctx *c, ExactRun run, const char *name, int64_t p, const int64_t *rc, const int64_t *rm,
-                    const int64_t *rp, const uint64_t *sel, int32_t *oi, double *os, int32_t *of, const S &...staged) {
-    int r = ksched_upload_pods(c, p, rc, rm, rp, sel);
+int schedule_staged(ksched_ctx *c, ExactRun run, const char *name, int64_t p, const PodIO &io, const S &...staged) {
+    int r = ksched_upload_pods(c, p, io.rc, io.rm, io.rp, io.sel);
     if (r != KSCHED_OK) return r;
     hipError_t e = hipSuccess;
-    auto reserve = [&](const auto &st) { if (e == hipSuccess) e = st.buf.reserve(st.bytes); };
+    auto reserve = [&](const auto &st) { if (st.on && e == hipSuccess) e = st.buf.reserve(st.bytes); };
     auto copy = [&](const auto &st) {
-        if (e == hipSuccess && st.host && st.bytes > 0)
+        if (st.on && e == hipSuccess && st.host && st.bytes > 0)
             e = hipMemcpyAsync(st.buf, st.host, st.bytes, hipMemcpyHostToDevice, c->stream);
     };
     (reserve(staged), ...);  // every array reserved before the first is copied; a step runs only if the last succeeded
@@ -56,7 +63,7 @@ int schedule_staged(ksched_ctx *c, ExactRun run, const char *name, int64_t p, co
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((r = run_impl(c, run)) != KSCHED_OK) { ksched_sync(c); return r; }
     if ((r = ksched_sync(c)) != KSCHED_OK) return r;
-    return ksched_download_results(c, p, oi, os, of);
+    return ksched_download_results(c, p, io.oi, io.os, io.of);
 }
 
 // After a run with gangs: the members bound per gang come down, stats.placed is their sum (a rolled-back member is not
@@ -68,6 +75,58 @@ int gang_results(ksched_ctx *c, size_t ng, int32_t *out) {
     for (int32_t v : gp) c->st.placed += v;
     if (out && ng > 0) std::memcpy(out, gp.data(), ng * 4);
     return KSCHED_OK;
+}
+
+static_assert(KSCHED_GANG_MAX == kGangMax && KSCHED_GANG_REJECTED == kGangRejected, "gang constants");
+static_assert(KSCHED_NUM_REASONS_FULL == kNumWhyReasons, "why constants");
+
+// The first half of every constrained schedule call, nothing of it on the device: the checks every call shares, then
+// the kind's check-and-pack (ksched_full.h).  A refusal leaves the context as it was.
+int constrained_begin(ksched_ctx *c, ExactRun run, const char *name, const FullArgs &args, FullPacked *k) {
+    if (!c) return KSCHED_E_INVALID;
+    const std::string nm(name);
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, nm + " before load_nodes");
+    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, nm + " is single-GPU (the exact kernel)");
+    try {
+        const char *why = nullptr;
+        if (const int code = full_check_pack(exact_kind(run), args, c->spread_S, c->ext_R, c->aff_valid, k, &why))
+            return fail(c, code, nm + ": " + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, nm + ": host staging buffer");
+    }
+    return KSCHED_OK;
+}
+
+// The second half: the run's "on" flags, the arrays of the constraints the kind carries go up, the run over them, the
+// results, the final any words where affinity was on and the gangs' counts where the kind has gangs (to the caller only
+// where it gave gangs).
+int constrained_run(ksched_ctx *c, ExactRun run, const char *name, const FullArgs &args, const FullPacked &k,
+                    const PodIO &io, int32_t *out_gang_placed) {
+    const ExactKind kind = exact_kind(run);
+    const size_t p = (size_t)args.p;
+    c->run_spread = k.spread;
+    c->run_ext = k.ext;
+    c->run_aff = k.aff;
+    const int r = schedule_staged(c, run, name, args.p, io,
+                                  Staged<int32_t>{kind.gang, c->d->gend, k.gend.data(), p * 4},
+                                  Staged<int32_t>{kind.gang, c->d->gplaced, nullptr, k.n_gangs * 4},
+                                  Staged<int32_t>{kind.spread, c->d->sword, k.swords.data(), p * 4},
+                                  Staged<int64_t>{kind.ext, c->d->ereq, k.reqs.data(), k.reqs.size() * 8},
+                                  Staged<int32_t>{kind.ext, c->d->eword, k.ewords.data(), p * 4},
+                                  Staged<int32_t>{kind.aff, c->d->aword, k.awords.data(), p * 4},
+                                  Staged<uint64_t>{kind.aff, c->d->apod, k.apods.data(), k.apods.size() * 8});
+    if (r != KSCHED_OK) return r;
+    // the run's final any words, for the next call's arguments (no pods: no launch, the any words stand)
+    if (k.aff && args.p > 0) HIPCHK(c, hipMemcpy(c->aff_any, c->d->aany, sizeof(c->aff_any), hipMemcpyDeviceToHost));
+    return kind.gang ? gang_results(c, k.n_gangs, args.gang_off ? out_gang_placed : nullptr) : KSCHED_OK;
+}
+
+// A constrained schedule call of one kind, whole.  What the kinds do differently is exact_kind's table.
+int schedule_kind(ksched_ctx *c, ExactRun run, const char *name, const FullArgs &args, const PodIO &io,
+                  int32_t *out_gang_placed) {
+    FullPacked k;
+    const int r = constrained_begin(c, run, name, args, &k);
+    return r != KSCHED_OK ? r : constrained_run(c, run, name, args, k, io, out_gang_placed);
 }
 
 // The tables a dry run is given: those its call switched on, as the context holds them (read only), and the workspace
@@ -94,30 +153,6 @@ int dry_begin(ksched_ctx *c, const char *name, const DryCall &call, DryPacked *k
         return fail(c, KSCHED_E_NOMEM, nm + ": host staging buffer");
     }
     return KSCHED_OK;
-}
-
-// What ksched_schedule_full and ksched_schedule_full_why share behind their checks: the packed words go up, the run
-// (kRunFull or kRunFullWhy) over them, the results, the final any words and the gangs' counts.
-int full_staged(ksched_ctx *c, ExactRun run, const char *name, const FullPacked &k, int64_t p, const int64_t *rc,
-                const int64_t *rm, const int64_t *rp, const uint64_t *sel, int32_t *oi, double *os, int32_t *of,
-                int32_t *out_gang_placed) {
-    const size_t ng = k.n_gangs;
-    const bool aff = k.aff;
-    c->all_spread = k.spread;
-    c->all_ext = k.ext;
-    c->all_aff = k.aff;
-    const int r = schedule_staged(c, run, name, p, rc, rm, rp, sel, oi, os, of,
-                                  Staged<int32_t>{c->d->gend, k.gend.data(), (size_t)p * 4},
-                                  Staged<int32_t>{c->d->gplaced, nullptr, ng * 4},
-                                  Staged<int32_t>{c->d->sword, k.swords.data(), (size_t)p * 4},
-                                  Staged<int64_t>{c->d->ereq, k.reqs.data(), k.reqs.size() * 8},
-                                  Staged<int32_t>{c->d->eword, k.ewords.data(), (size_t)p * 4},
-                                  Staged<int32_t>{c->d->aword, k.awords.data(), (size_t)p * 4},
-                                  Staged<uint64_t>{c->d->apod, k.apods.data(), k.apods.size() * 8});
-    if (r != KSCHED_OK) return r;
-    // the run's final any words, for the next call's arguments (no pods: no launch, the any words stand)
-    if (aff && p > 0) HIPCHK(c, hipMemcpy(c->aff_any, c->d->aany, sizeof(c->aff_any), hipMemcpyDeviceToHost));
-    return gang_results(c, ng, out_gang_placed);
 }
 
 uint64_t uabs64(int64_t v) { return v < 0 ? (uint64_t)0 - (uint64_t)v : (uint64_t)v; }
@@ -198,114 +233,6 @@ int ksched_read_ext(ksched_ctx *c, int64_t *out_ext) {
     return KSCHED_OK;
 }
 
-int ksched_schedule_gangs(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
-                          const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
-                          int32_t *oi, double *os, int32_t *of, int32_t *out_gang_placed) {
-    if (!c) return KSCHED_E_INVALID;
-    static_assert(KSCHED_GANG_MAX == kGangMax && KSCHED_GANG_REJECTED == kGangRejected, "gang constants");
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_gangs before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_gangs is single-GPU (the exact kernel)");
-    // every offset and minimum is checked before anything is written or allocated (ksched_gang.h)
-    if (const char *why = gang_check(p, n_gangs, gang_off, gang_min))
-        return fail(c, KSCHED_E_INVALID, std::string("schedule_gangs: ") + why);
-    // staged per pod, so the kernel reads a gang's end with its last member's request: 0, or size | minimum << 16
-    std::vector<int32_t> gend;
-    try {
-        gang_pack_ends(p, n_gangs, gang_off, gang_min, &gend);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "schedule_gangs: host staging buffer");
-    }
-    const size_t ng = (size_t)n_gangs;
-    const int r = schedule_staged(c, kRunGang, "schedule_gangs", p, rc, rm, rp, sel, oi, os, of,
-                                  Staged<int32_t>{c->d->gend, gend.data(), (size_t)p * 4},
-                                  Staged<int32_t>{c->d->gplaced, nullptr, ng * 4});
-    return r != KSCHED_OK ? r : gang_results(c, ng, out_gang_placed);
-}
-
-int ksched_schedule_spread(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
-                           const uint64_t *sel, const int32_t *spread_group, const uint8_t *spread_enforce, int32_t *oi,
-                           double *os, int32_t *of) {
-    if (!c) return KSCHED_E_INVALID;
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_spread before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_spread is single-GPU (the exact kernel)");
-    if (c->spread_S == 0)
-        return fail(c, KSCHED_E_STATE, "schedule_spread: no spread table (ksched_load_spread after every ksched_load_nodes)");
-    // every group is checked, and the per-pod words are packed, before anything is written or allocated
-    std::vector<int32_t> words;
-    try {
-        if (const char *why = spread_pack_words(p, c->spread_S, spread_group, spread_enforce, &words))
-            return fail(c, KSCHED_E_INVALID, std::string("schedule_spread: ") + why);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "schedule_spread: host staging buffer");
-    }
-    return schedule_staged(c, kRunSpread, "schedule_spread", p, rc, rm, rp, sel, oi, os, of,
-                           Staged<int32_t>{c->d->sword, words.data(), (size_t)p * 4});
-}
-
-int ksched_schedule_ext(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
-                        const uint64_t *sel, const int64_t *req_ext, int32_t *oi, double *os, int32_t *of) {
-    if (!c) return KSCHED_E_INVALID;
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_ext before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_ext is single-GPU (the exact kernel)");
-    if (c->ext_R == 0)
-        return fail(c, KSCHED_E_STATE, "schedule_ext: no extended-resource table (ksched_load_ext after every ksched_load_nodes)");
-    // every request is checked, and the per-pod words are packed, before anything is written or allocated
-    std::vector<int64_t> reqs;
-    std::vector<int32_t> words;
-    try {
-        if (const char *why = ext_pack_pods(p, c->ext_R, req_ext, &reqs, &words))
-            return fail(c, KSCHED_E_INVALID, std::string("schedule_ext: ") + why);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "schedule_ext: host staging buffer");
-    }
-    return schedule_staged(c, kRunExt, "schedule_ext", p, rc, rm, rp, sel, oi, os, of,
-                           Staged<int64_t>{c->d->ereq, reqs.data(), reqs.size() * 8},
-                           Staged<int32_t>{c->d->eword, words.data(), (size_t)p * 4});
-}
-
-// Gangs, spread and extended resources in one run of k_exact<kRunAll>.  A constraint whose argument is NULL is off for
-// the whole call: its per-pod words say so (gangs of one, no group, no request) and the kernel is not given its table.
-int ksched_schedule_constrained(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
-                                const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
-                                const int32_t *spread_group, const uint8_t *spread_enforce, const int64_t *req_ext,
-                                int32_t *oi, double *os, int32_t *of, int32_t *out_gang_placed) {
-    if (!c) return KSCHED_E_INVALID;
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_constrained before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_constrained is single-GPU (the exact kernel)");
-    if (p < 0 || p >= ((int64_t)1 << 30)) return fail(c, KSCHED_E_INVALID, "schedule_constrained: p must be in [0, 2^30)");
-    if (!gang_off && n_gangs != 0)
-        return fail(c, KSCHED_E_INVALID, "schedule_constrained: n_gangs must be 0 without gang_off");
-    if (spread_group && c->spread_S == 0)
-        return fail(c, KSCHED_E_STATE, "schedule_constrained: no spread table (ksched_load_spread after every ksched_load_nodes)");
-    if (req_ext && c->ext_R == 0)
-        return fail(c, KSCHED_E_STATE, "schedule_constrained: no extended-resource table (ksched_load_ext after every ksched_load_nodes)");
-    // every argument is checked, and every per-pod word is packed, before anything is written or allocated
-    std::vector<int32_t> gend, swords, ewords;
-    std::vector<int64_t> reqs;
-    try {
-        const char *why = gang_off ? gang_check(p, n_gangs, gang_off, gang_min) : nullptr;
-        if (!why && spread_group) why = spread_pack_words(p, c->spread_S, spread_group, spread_enforce, &swords);
-        if (!why && req_ext) why = ext_pack_pods(p, c->ext_R, req_ext, &reqs, &ewords);
-        if (why) return fail(c, KSCHED_E_INVALID, std::string("schedule_constrained: ") + why);
-        if (gang_off) gang_pack_ends(p, n_gangs, gang_off, gang_min, &gend);
-        else gang_pack_singles(p, &gend);
-        if (!spread_group) swords.assign((size_t)p, -1);
-        if (!req_ext) ewords.assign((size_t)p, 0);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "schedule_constrained: host staging buffer");
-    }
-    const size_t ng = gang_off ? (size_t)n_gangs : (size_t)p;  // the kernel's gangs: the caller's, or one per pod
-    c->all_spread = spread_group != nullptr;
-    c->all_ext = req_ext != nullptr;
-    const int r = schedule_staged(c, kRunAll, "schedule_constrained", p, rc, rm, rp, sel, oi, os, of,
-                                  Staged<int32_t>{c->d->gend, gend.data(), (size_t)p * 4},
-                                  Staged<int32_t>{c->d->gplaced, nullptr, ng * 4},
-                                  Staged<int32_t>{c->d->sword, swords.data(), (size_t)p * 4},
-                                  Staged<int64_t>{c->d->ereq, reqs.data(), reqs.size() * 8},
-                                  Staged<int32_t>{c->d->eword, ewords.data(), (size_t)p * 4});
-    return r != KSCHED_OK ? r : gang_results(c, ng, gang_off ? out_gang_placed : nullptr);
-}
-
 // The affinity table of ksched_schedule_affinity: checked on the host (ksched_affinity.h), and its zone and `any` words
 // derived there, before anything is allocated or staged; then uploaded in the stream of the kernel that reads it.
 // Touches no node row; the context holds the new table only once the last copy has landed, and the earlier one until the
@@ -364,63 +291,60 @@ int ksched_read_affinity(ksched_ctx *c, uint64_t *out_member, uint64_t *out_anti
     return KSCHED_OK;
 }
 
+// The constrained schedule calls: each names its kind and its arguments (FullArgs: p, the gangs, spread, extended
+// resources, the five affinity arrays; what the call has not stays null) and runs through schedule_kind.  In a composed
+// call (kRunAll, kRunFull, kRunFullWhy) a constraint whose argument is NULL (affinity: all five) is off for the whole
+// call: its per-pod words say so and the kernel is not given its table.
+int ksched_schedule_gangs(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                          const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
+                          int32_t *oi, double *os, int32_t *of, int32_t *out_gang_placed) {
+    const FullArgs args{p, n_gangs, gang_off, gang_min};
+    return schedule_kind(c, kRunGang, "schedule_gangs", args, PodIO{rc, rm, rp, sel, oi, os, of}, out_gang_placed);
+}
+
+int ksched_schedule_spread(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                           const uint64_t *sel, const int32_t *spread_group, const uint8_t *spread_enforce, int32_t *oi,
+                           double *os, int32_t *of) {
+    const FullArgs args{p, 0, nullptr, nullptr, spread_group, spread_enforce};
+    return schedule_kind(c, kRunSpread, "schedule_spread", args, PodIO{rc, rm, rp, sel, oi, os, of}, nullptr);
+}
+
+int ksched_schedule_ext(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                        const uint64_t *sel, const int64_t *req_ext, int32_t *oi, double *os, int32_t *of) {
+    const FullArgs args{p, 0, nullptr, nullptr, nullptr, nullptr, req_ext};
+    return schedule_kind(c, kRunExt, "schedule_ext", args, PodIO{rc, rm, rp, sel, oi, os, of}, nullptr);
+}
+
+int ksched_schedule_constrained(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                                const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
+                                const int32_t *spread_group, const uint8_t *spread_enforce, const int64_t *req_ext,
+                                int32_t *oi, double *os, int32_t *of, int32_t *out_gang_placed) {
+    const FullArgs args{p, n_gangs, gang_off, gang_min, spread_group, spread_enforce, req_ext};
+    return schedule_kind(c, kRunAll, "schedule_constrained", args, PodIO{rc, rm, rp, sel, oi, os, of}, out_gang_placed);
+}
+
 int ksched_schedule_affinity(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
                              const uint64_t *sel, const uint64_t *member, const uint64_t *anti_host,
                              const uint64_t *anti_zone, const int32_t *aff_group, const uint8_t *aff_zone, int32_t *oi,
                              double *os, int32_t *of) {
-    if (!c) return KSCHED_E_INVALID;
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_affinity before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_affinity is single-GPU (the exact kernel)");
-    if (!c->aff_valid)
-        return fail(c, KSCHED_E_STATE, "schedule_affinity: no affinity table (ksched_load_affinity after every ksched_load_nodes)");
-    // every group is checked, and the per-pod words are packed, before anything is written or allocated
-    std::vector<int32_t> words;
-    std::vector<uint64_t> pods;
-    try {
-        if (const char *why = aff_pack_pods(p, member, anti_host, anti_zone, aff_group, aff_zone, &words, &pods))
-            return fail(c, KSCHED_E_INVALID, std::string("schedule_affinity: ") + why);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "schedule_affinity: host staging buffer");
-    }
-    const int r = schedule_staged(c, kRunAffinity, "schedule_affinity", p, rc, rm, rp, sel, oi, os, of,
-                                  Staged<int32_t>{c->d->aword, words.data(), (size_t)p * 4},
-                                  Staged<uint64_t>{c->d->apod, pods.data(), pods.size() * 8});
-    if (r != KSCHED_OK || p == 0) return r;  // (no pods: no launch, the any words stand)
-    // the run's final any words, for the next call's arguments (the sync above is behind the kernel that wrote them)
-    HIPCHK(c, hipMemcpy(c->aff_any, c->d->aany, sizeof(c->aff_any), hipMemcpyDeviceToHost));
-    return KSCHED_OK;
+    const FullArgs args{p, 0, nullptr, nullptr, nullptr, nullptr, nullptr, member, anti_host, anti_zone, aff_group, aff_zone};
+    return schedule_kind(c, kRunAffinity, "schedule_affinity", args, PodIO{rc, rm, rp, sel, oi, os, of}, nullptr);
 }
 
-// ksched_schedule_constrained and ksched_schedule_affinity in one run of k_exact<kRunFull>.  A constraint whose
-// argument is NULL (affinity: all five) is off for the whole call: its per-pod words say so and the kernel is not given
-// its table.  Every check of the four calls runs, through their own checkers and packers (ksched_full.h), before anything
-// is staged.
 int ksched_schedule_full(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
                          const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
                          const int32_t *spread_group, const uint8_t *spread_enforce, const int64_t *req_ext,
                          const uint64_t *member, const uint64_t *anti_host, const uint64_t *anti_zone,
                          const int32_t *aff_group, const uint8_t *aff_zone, int32_t *oi, double *os, int32_t *of,
                          int32_t *out_gang_placed) {
-    if (!c) return KSCHED_E_INVALID;
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_full before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_full is single-GPU (the exact kernel)");
-    // every argument is checked, and every per-pod word is packed, before anything is written or allocated (ksched_full.h)
     const FullArgs args{p, n_gangs, gang_off, gang_min, spread_group, spread_enforce, req_ext, member, anti_host, anti_zone,
                         aff_group, aff_zone};
-    FullPacked k;
-    try {
-        const char *why = nullptr;
-        if (const int code = full_check_pack(args, c->spread_S, c->ext_R, c->aff_valid, &k, &why))
-            return fail(c, code, std::string("schedule_full: ") + why);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "schedule_full: host staging buffer");
-    }
-    return full_staged(c, kRunFull, "schedule_full", k, p, rc, rm, rp, sel, oi, os, of, gang_off ? out_gang_placed : nullptr);
+    return schedule_kind(c, kRunFull, "schedule_full", args, PodIO{rc, rm, rp, sel, oi, os, of}, out_gang_placed);
 }
 
-// ksched_schedule_full, and what every pod that fits nowhere saw at its turn: one run of k_exact<kRunFullWhy>.  The
-// call's own arguments are checked behind ksched_schedule_full's (ksched_why.h), and the rows' buffer is reserved and
-// cleared, before anything is staged: a refused call and a failed allocation leave the context as it was.
+// ksched_schedule_full, and what every pod that fits nowhere saw at its turn.  The call's own arguments are checked
+// behind ksched_schedule_full's (ksched_why.h), and the rows' buffer is reserved and cleared, before anything is staged:
+// a refused call and a failed allocation leave the context as it was.
 int ksched_schedule_full_why(ksched_ctx *c, int64_t p, const int64_t *rc, const int64_t *rm, const int64_t *rp,
                              const uint64_t *sel, int64_t n_gangs, const int64_t *gang_off, const int32_t *gang_min,
                              const int32_t *spread_group, const uint8_t *spread_enforce, const int64_t *req_ext,
@@ -428,20 +352,10 @@ int ksched_schedule_full_why(ksched_ctx *c, int64_t p, const int64_t *rc, const 
                              const int32_t *aff_group, const uint8_t *aff_zone, int32_t *oi, double *os, int32_t *of,
                              int32_t *out_gang_placed, int64_t why_rows, int32_t *out_why_pod, int64_t *out_why_counts,
                              int64_t node_rows, uint8_t *out_why_reason, int64_t *out_nofit) {
-    if (!c) return KSCHED_E_INVALID;
-    static_assert(KSCHED_NUM_REASONS_FULL == kNumWhyReasons, "why constants");
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "schedule_full_why before load_nodes");
-    if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "schedule_full_why is single-GPU (the exact kernel)");
     const FullArgs args{p, n_gangs, gang_off, gang_min, spread_group, spread_enforce, req_ext, member, anti_host, anti_zone,
                         aff_group, aff_zone};
     FullPacked k;
-    try {
-        const char *why = nullptr;
-        if (const int code = full_check_pack(args, c->spread_S, c->ext_R, c->aff_valid, &k, &why))
-            return fail(c, code, std::string("schedule_full_why: ") + why);
-    } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "schedule_full_why: host staging buffer");
-    }
+    if (const int r = constrained_begin(c, kRunFullWhy, "schedule_full_why", args, &k)) return r;
     const int64_t n = c->n_local;
     if (const char *why = why_check(WhyArgs{why_rows, out_why_pod, out_why_counts, node_rows, out_why_reason, n}))
         return fail(c, KSCHED_E_INVALID, std::string("schedule_full_why: ") + why);
@@ -457,10 +371,9 @@ int ksched_schedule_full_why(ksched_ctx *c, int64_t p, const int64_t *rc, const 
     HIPCHK(c, hipMemsetAsync(w, 0, l.total, c->stream));
     if (why_rows > 0) HIPCHK(c, hipMemsetAsync(w + l.o_pod, 0xff, (size_t)why_rows * 4, c->stream));
     c->why_rows = why_rows; c->why_node_rows = node_rows;
-    const int r = full_staged(c, kRunFullWhy, "schedule_full_why", k, p, rc, rm, rp, sel, oi, os, of,
-                              gang_off ? out_gang_placed : nullptr);
+    const int r = constrained_run(c, kRunFullWhy, "schedule_full_why", args, k, PodIO{rc, rm, rp, sel, oi, os, of}, out_gang_placed);
     if (r != KSCHED_OK) return r;
-    // (full_staged's sync is behind the kernel, or -- no pods, no launch -- behind the clears alone)
+    // (the run's sync is behind the kernel, or -- no pods, no launch -- behind the clears alone)
     int64_t total = 0;
     HIPCHK(c, hipMemcpy(&total, w + l.o_nofit, 8, hipMemcpyDeviceToHost));
     if (why_rows > 0) {

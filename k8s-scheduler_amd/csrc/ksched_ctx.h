@@ -216,8 +216,9 @@ struct ksched_ctx {
     bool aff_valid = false;      // ksched_load_affinity's table describes the loaded nodes (every load_nodes clears it)
     int32_t aff_D = 0;           // ... its zone domains (0: no zone key)
     uint64_t aff_any[2] = {};    // ... any_host, any_zone: into every affinity run by value, back from d->aany behind it
-    bool all_spread = false, all_ext = false;  // ksched_schedule_constrained: the tables its kRunAll launch is given
-    bool all_aff = false;        // ksched_schedule_full: its kRunFull launch is given the affinity table (with the two above)
+    // every constrained schedule call, for its run: the tables the launch is given, of those its kind carries (a single
+    // kind's: always)
+    bool run_spread = false, run_ext = false, run_aff = false;
     int64_t why_rows = 0, why_node_rows = 0;  // ksched_schedule_full_why: the rows its kRunFullWhy launch may fill in d->why
     // pods
     int64_t p = 0;

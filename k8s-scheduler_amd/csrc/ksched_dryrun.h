@@ -60,10 +60,6 @@ struct DryPacked {
     std::vector<DryPod> pods;
 };
 
-inline bool dry_affinity_on(const DryCall &a) {
-    return a.member || a.anti_host || a.anti_zone || a.aff_group || a.aff_zone;
-}
-
 // KSCHED_OK with *out packed, or the code and *why.  The order is ksched_schedule_full's: m and the requests' shape
 // (KSCHED_E_INVALID), a constraint that is on without its table (KSCHED_E_STATE), then every array, constraint by
 // constraint (KSCHED_E_INVALID).  No array is read before m is known to be in range.  May throw std::bad_alloc.
@@ -74,7 +70,7 @@ inline int dry_check_pack(const DryCall &a, const DryState &st, DryPacked *out, 
     if (st.use_labels && a.m > 0 && !a.sel) { *why = "use_labels needs selectors"; return KSCHED_E_INVALID; }
     out->spread = a.spread_group != nullptr;
     out->ext = a.req_ext != nullptr;
-    out->aff = dry_affinity_on(a);
+    out->aff = affinity_on(a.member, a.anti_host, a.anti_zone, a.aff_group, a.aff_zone);
     if (out->spread && st.spread_S == 0) { *why = "no spread table (ksched_load_spread after every ksched_load_nodes)"; return KSCHED_E_STATE; }
     if (out->ext && st.ext_R == 0) { *why = "no extended-resource table (ksched_load_ext after every ksched_load_nodes)"; return KSCHED_E_STATE; }
     if (out->aff && !st.aff_valid) { *why = "no affinity table (ksched_load_affinity after every ksched_load_nodes)"; return KSCHED_E_STATE; }

@@ -467,11 +467,45 @@ int enqueue_persistent(ksched_ctx *c) {
     return KSCHED_OK;
 }
 
-// run (ExactRun, ksched_exact.h): a plain exact run, or the run of ksched_schedule_gangs / _spread / _ext /
-// _constrained / _affinity / _full / _full_why over what that call staged -- always k_exact, the multi-slot kernel, under the same geometry and launch
-// rule as a plain run
+// A constraint's fields of ExactArgs from the context: the per-pod words its call staged, and its table where the call
+// has the constraint on (run_spread / run_ext / run_aff; off: the zeroed fields say "no table").
+void args_gang(const ksched_ctx *c, ExactArgs *a) { a->gang_end = c->d->gend; a->gang_placed = c->d->gplaced; }
+void args_spread(const ksched_ctx *c, ExactArgs *a) {
+    a->sp_word = c->d->sword;
+    if (!c->run_spread) return;
+    a->sp_dom = c->d->sdom; a->sp_counts = c->d->scnt; a->sp_skew = c->d->sskew;
+    a->sp_D = c->spread_D; a->sp_S = c->spread_S;
+}
+void args_ext(const ksched_ctx *c, ExactArgs *a) {
+    a->ext_word = c->d->eword;
+    if (c->run_ext) { a->ext = c->d->etab; a->ext_req = c->d->ereq; a->n_ext = c->ext_R; }
+}
+void args_aff(const ksched_ctx *c, ExactArgs *a) {
+    a->af_word = c->d->aword; a->af_pod = c->d->apod;
+    if (!c->run_aff) return;
+    a->af_dom = c->d->adom; a->af_member = c->d->amem; a->af_anti_host = c->d->aanti_h;
+    a->af_anti_zone = c->d->aanti_z; a->af_zone = c->d->azone; a->af_any = c->d->aany;
+    a->af_any_host = c->aff_any[0]; a->af_any_zone = c->aff_any[1]; a->af_D = c->aff_D;
+}
+// the rows of d->why, which ksched_schedule_full_why reserved and cleared (ksched_why.h); false: it did not
+bool args_why(const ksched_ctx *c, ExactArgs *a) {
+    const WhyLayout l = why_layout(c->why_rows, c->why_node_rows, c->n_local);
+    char *w = static_cast<char *>(c->d->why.p);
+    if (!w || c->d->why.bytes < l.total) return false;
+    a->why_counts = reinterpret_cast<unsigned long long *>(w + l.o_counts);
+    a->why_nofit = reinterpret_cast<int64_t *>(w + l.o_nofit);
+    a->why_pod = reinterpret_cast<int32_t *>(w + l.o_pod);
+    a->why_reason = reinterpret_cast<uint8_t *>(w + l.o_reason);
+    a->why_rows = c->why_rows; a->why_node_rows = c->why_node_rows;
+    return true;
+}
+
+// A plain exact run, or the run of a constrained schedule call over what it staged (ksched_constraints.hip) -- always
+// k_exact, the multi-slot kernel, under the same geometry and launch rule as a plain run.  What the kind carries:
+// exact_kind (ksched_exact.h).
 int enqueue_exact(ksched_ctx *c, ExactRun run) {
     if (c->o.nranks > 1) return fail(c, KSCHED_E_INVALID, "exact mode is single-GPU; use batched mode across ranks");
+    const ExactKind kind = exact_kind(run);
     const int64_t n = c->n_local;
     // the whole node set in ONE workgroup's registers (k_exact1): no cross-workgroup exchange per pod
     const bool price = c->o.priority == KSCHED_PRIORITY_BEST_PRICE;
@@ -515,69 +549,23 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
         return fail(c, KSCHED_E_INVALID, "exact mode: too many nodes per workgroup (raise exact_wgs)");
     if (G > c->cus) return fail(c, KSCHED_E_INVALID, "exact mode: more workgroups than CUs");
     HIPCHK(c, c->d->slots.reserve((size_t)2 * G * 4 * sizeof(uint64_t)));
-    // kRunFull: a rejected gang's undo log of the affinity words -- one slot record per member, one zone record per
-    // workgroup and member (written before it is read: not cleared); reserved here, before the timed span begins
+    // a rejected gang's undo log of the affinity words -- one slot record per member, one zone record per workgroup and
+    // member (written before it is read: not cleared); reserved here, before the timed span begins
     const size_t undo_slot_words = (size_t)kGangMax * 3;
-    if (run == kRunFull || run == kRunFullWhy) HIPCHK(c, c->d->aundo.reserve((undo_slot_words + (size_t)G * kGangMax * 2) * sizeof(uint64_t)));
+    if (kind.undo) HIPCHK(c, c->d->aundo.reserve((undo_slot_words + (size_t)G * kGangMax * 2) * sizeof(uint64_t)));
     HIPCHK(c, hipMemsetAsync(c->d->slots, 0, (size_t)2 * G * 4 * sizeof(uint64_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d->err, 0, sizeof(int32_t), c->stream));
     a.G = G; a.per_wg = (int32_t)per_wg; a.slots = c->d->slots;
     a.timeout_ticks = c->diag.exchange_timeout_ms * 100000;  // 100 MHz wall clock
     int e0 = -1;
     HIPCHK(c, ev_begin(c, c->o.timing != 0, &e0, c->stream));
-    switch (run) {  // the extension's fields: what its call staged, and the context's table
-        case kRunPlain: break;
-        case kRunGang:
-            a.gang_end = c->d->gend; a.gang_placed = c->d->gplaced;
-            break;
-        case kRunSpread:
-            a.sp_dom = c->d->sdom; a.sp_counts = c->d->scnt; a.sp_skew = c->d->sskew;
-            a.sp_D = c->spread_D; a.sp_S = c->spread_S; a.sp_word = c->d->sword;
-            break;
-        case kRunExt:
-            a.ext = c->d->etab; a.ext_req = c->d->ereq; a.ext_word = c->d->eword; a.n_ext = c->ext_R;
-            break;
-        case kRunAll:  // every staged word; a table only where ksched_schedule_constrained was given its argument
-            a.gang_end = c->d->gend; a.gang_placed = c->d->gplaced; a.sp_word = c->d->sword; a.ext_word = c->d->eword;
-            if (c->all_spread) {
-                a.sp_dom = c->d->sdom; a.sp_counts = c->d->scnt; a.sp_skew = c->d->sskew;
-                a.sp_D = c->spread_D; a.sp_S = c->spread_S;
-            }
-            if (c->all_ext) { a.ext = c->d->etab; a.ext_req = c->d->ereq; a.n_ext = c->ext_R; }
-            break;
-        case kRunAffinity:
-            a.af_dom = c->d->adom; a.af_member = c->d->amem; a.af_anti_host = c->d->aanti_h;
-            a.af_anti_zone = c->d->aanti_z; a.af_zone = c->d->azone; a.af_any = c->d->aany;
-            a.af_any_host = c->aff_any[0]; a.af_any_zone = c->aff_any[1]; a.af_D = c->aff_D;
-            a.af_word = c->d->aword; a.af_pod = c->d->apod;
-            break;
-        case kRunFull:  // every staged word; a table only where ksched_schedule_full was given its argument; the undo log
-        case kRunFullWhy:  // ... and the rows of d->why, which ksched_schedule_full_why reserved and cleared (ksched_why.h)
-            a.gang_end = c->d->gend; a.gang_placed = c->d->gplaced; a.sp_word = c->d->sword; a.ext_word = c->d->eword;
-            a.af_word = c->d->aword; a.af_pod = c->d->apod;
-            if (c->all_spread) {
-                a.sp_dom = c->d->sdom; a.sp_counts = c->d->scnt; a.sp_skew = c->d->sskew;
-                a.sp_D = c->spread_D; a.sp_S = c->spread_S;
-            }
-            if (c->all_ext) { a.ext = c->d->etab; a.ext_req = c->d->ereq; a.n_ext = c->ext_R; }
-            if (c->all_aff) {
-                a.af_dom = c->d->adom; a.af_member = c->d->amem; a.af_anti_host = c->d->aanti_h;
-                a.af_anti_zone = c->d->aanti_z; a.af_zone = c->d->azone; a.af_any = c->d->aany;
-                a.af_any_host = c->aff_any[0]; a.af_any_zone = c->aff_any[1]; a.af_D = c->aff_D;
-            }
-            a.af_undo_slot = c->d->aundo; a.af_undo_zone = c->d->aundo.p + undo_slot_words;
-            if (run == kRunFullWhy) {
-                const WhyLayout l = why_layout(c->why_rows, c->why_node_rows, n);
-                char *w = static_cast<char *>(c->d->why.p);
-                if (!w || c->d->why.bytes < l.total) return fail(c, KSCHED_E_STATE, "exact mode: the why rows are not reserved");
-                a.why_counts = reinterpret_cast<unsigned long long *>(w + l.o_counts);
-                a.why_nofit = reinterpret_cast<int64_t *>(w + l.o_nofit);
-                a.why_pod = reinterpret_cast<int32_t *>(w + l.o_pod);
-                a.why_reason = reinterpret_cast<uint8_t *>(w + l.o_reason);
-                a.why_rows = c->why_rows; a.why_node_rows = c->why_node_rows;
-            }
-            break;
-    }
+    // the fields of every constraint the kind carries: the words its call staged, and the table where the call has it on
+    if (kind.gang) args_gang(c, &a);
+    if (kind.spread) args_spread(c, &a);
+    if (kind.ext) args_ext(c, &a);
+    if (kind.aff) args_aff(c, &a);
+    if (kind.undo) { a.af_undo_slot = c->d->aundo; a.af_undo_zone = c->d->aundo.p + undo_slot_words; }
+    if (kind.why && !args_why(c, &a)) return fail(c, KSCHED_E_STATE, "exact mode: the why rows are not reserved");
     HIPCHK(c, launch_exact(run, npt, c->o.priority, c->o.domain, c->o.use_labels != 0, c->fast53, a, kExactBlock,
                            G > 1 && !c->diag.plain_launch, c->stream));
     HIPCHK(c, ev_end(c, c->o.timing != 0, 0, e0, c->p * n, c->stream));
@@ -587,8 +575,7 @@ int enqueue_exact(ksched_ctx *c, ExactRun run) {
 
 }  // namespace
 
-// ksched_run, or the run of ksched_schedule_gangs / ksched_schedule_spread / ksched_schedule_ext /
-// ksched_schedule_constrained / ksched_schedule_affinity / ksched_schedule_full: the exact kernel over the staged gangs / spread words / extended requests whatever opts.mode
+// ksched_run (kRunPlain), or the run of a constrained schedule call: the exact kernel over what it staged, whatever opts.mode
 int ksched::run_impl(ksched_ctx *c, ExactRun run) {
     if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "run before load_nodes");
     if (c->o.nranks > 1 && !c->comm && !c->group && !c->xchg_ready)

@@ -1,28 +1,64 @@
-// ksched_exact.h -- exact mode (ksched_exact.hip): the arguments of k_exact / k_exact1, the constants of the four
-// extensions of k_exact (gangs, topology spread, extended resources, inter-pod affinity) and the launchers.  ksched_ctx.h includes it
-// beside ksched_kernels.h, so the host units keep one include and no other device unit depends on it.
+// ksched_exact.h -- exact mode (ksched_exact.hip).  First, in plain C++ (ksched_full.h reads it without a HIP compiler):
+// the kinds of k_exact, what each carries, and the constants of the constraints.  Then, for a HIP compiler only, the
+// arguments of k_exact / k_exact1 and the launchers.  ksched_ctx.h includes it beside ksched_kernels.h, so the host units
+// keep one include and no other device unit depends on it.
 #pragma once
 
-#include "ksched_device.h"
+#include <stdint.h>
 
 namespace ksched {
 
-// Which extension of k_exact a launch runs -- none, one, or (kRunAll) all three together: the value travels from the C
-// entry point (ksched_schedule_gangs / _spread / _ext / _constrained, ksched_constraints.hip) through run_impl and
-// enqueue_exact to the kernel's template parameter.  kRunGang: the staged gangs in d->gend; kRunSpread: the staged words
-// in d->sword and the context's table; kRunExt: the staged requests in d->ereq / d->eword and the context's table;
-// kRunAll (ksched_schedule_constrained): all of these in one launch, a rejected gang undoing its extended-resource and
-// spread commits with its node rows.  No other pairing is instantiated: a kRunAll launch switches a constraint it does
-// not need off by uniform runtime values (sp_S == 0 with every sp_word -1; n_ext == 0 with every ext_word 0; gangs of
-// one).  kRunAffinity (ksched_schedule_affinity): the staged words in d->aword / d->apod and the context's affinity
-// table; it is paired with no other kind.  Every run but kRunPlain is the multi-slot kernel k_exact whatever opts.mode, under the same geometry and launch
-// rule as a plain exact run.
-// kRunFull (ksched_schedule_full): kRunAll and kRunAffinity in one launch -- the staged words of both and the tables the
-// call switched on; a rejected gang also puts back the affinity words it ORed into, from the undo log in d->aundo.
-// kRunFullWhy (ksched_schedule_full_why): kRunFull, and for every pod that fits nowhere the reason code of each node as
-// the pod saw it at its turn, into the why_* buffers the host zeroed before the launch.
+// Which kind of k_exact a launch runs.  The value travels from the C entry point (ksched_constraints.hip) through
+// run_impl and enqueue_exact to the kernel's template parameter; every kind but kRunPlain is the multi-slot kernel
+// whatever opts.mode, under the geometry and launch rule of a plain exact run.  No other pairing is instantiated
+// (a composed kind with a constraint switched off costs 7 to 14 % over the kind without it).
 enum ExactRun { kRunPlain = 0, kRunGang = 1, kRunSpread = 2, kRunExt = 3, kRunAll = 4, kRunAffinity = 5, kRunFull = 6,
                 kRunFullWhy = 7 };
+
+// What a kind carries: the one table that the kernel's constexpr flags, the launcher's checks, enqueue_exact's fields
+// and the host's check-and-pack (ksched_full.h) all read.
+//   gang    the staged gang ends, all-or-nothing rollback
+//   spread  the staged spread words and the context's spread table
+//   ext     the staged requests and words and the context's extended-resource table
+//   aff     the staged affinity words and the context's affinity table
+//   undo    a rejected gang puts back the affinity words it ORed into (the undo log in d->aundo)
+//   why     the reason code of every node for each pod that fits nowhere, at its turn (the why_* buffers)
+//   optional  a composed kind: a call switches a constraint it does not use off by uniform run-time values -- gangs of
+//             one; sp_S == 0 with every sp_word -1; n_ext == 0 with every ext_word 0; af_dom null with every af_word 0 --
+//             and the kernel is not given that table.  A single kind's constraint is always on.
+struct ExactKind {
+    bool gang, spread, ext, aff, undo, why, optional;
+};
+constexpr ExactKind exact_kind(ExactRun run) {
+    switch (run) {  //                   gang   spread ext    aff    undo   why    optional
+        case kRunGang:     return {true,  false, false, false, false, false, false};  // ksched_schedule_gangs
+        case kRunSpread:   return {false, true,  false, false, false, false, false};  // ksched_schedule_spread
+        case kRunExt:      return {false, false, true,  false, false, false, false};  // ksched_schedule_ext
+        case kRunAll:      return {true,  true,  true,  false, false, false, true};   // ksched_schedule_constrained
+        case kRunAffinity: return {false, false, false, true,  false, false, false};  // ksched_schedule_affinity
+        case kRunFull:     return {true,  true,  true,  true,  true,  false, true};   // ksched_schedule_full
+        case kRunFullWhy:  return {true,  true,  true,  true,  true,  true,  true};   // ksched_schedule_full_why
+        default:           return {false, false, false, false, false, false, false};  // kRunPlain (ksched_run)
+    }
+}
+
+constexpr int kNumWhyReasons = 14;      // KSCHED_NUM_REASONS_FULL: ksched_rank_full's codes
+constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
+constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
+constexpr int kSpreadMaxDomains = 1024; // KSCHED_SPREAD_MAX_DOMAINS
+constexpr int kSpreadMaxGroups = 64;    // KSCHED_SPREAD_MAX_GROUPS
+constexpr int kSpreadMaxCells = 4096;   // KSCHED_SPREAD_MAX_CELLS: the LDS table of every workgroup, 16 KiB
+constexpr int kExtMax = 4;              // KSCHED_EXT_MAX: columns of the dynamic LDS table, kExtMax * 256 * 8 slots * 8 B = 64 KiB
+
+constexpr int kAffMaxGroups = 64;       // KSCHED_AFF_MAX_GROUPS: one bit of a 64-bit word per group
+constexpr int kAffWords = 4;            // ExactArgs::af_pod: words per pod
+
+}  // namespace ksched
+
+#ifdef __HIPCC__
+#include "ksched_device.h"
+
+namespace ksched {
 
 struct ExactArgs {
     NodeRec *nodes;
@@ -79,29 +115,15 @@ struct ExactArgs {
     int64_t why_rows, why_node_rows;
     int64_t *why_nofit;       // out: the call's NO_FIT pods, recorded or not (workgroup 0, thread 0, at exit)
 };
-constexpr int kNumWhyReasons = 14;      // KSCHED_NUM_REASONS_FULL: ksched_rank_full's codes
-constexpr int kGangMax = 1024;          // KSCHED_GANG_MAX: the LDS log of one gang's outcomes
-constexpr int32_t kGangRejected = -3;   // KSCHED_GANG_REJECTED
-constexpr int kSpreadMaxDomains = 1024; // KSCHED_SPREAD_MAX_DOMAINS
-constexpr int kSpreadMaxGroups = 64;    // KSCHED_SPREAD_MAX_GROUPS
-constexpr int kSpreadMaxCells = 4096;   // KSCHED_SPREAD_MAX_CELLS: the LDS table of every workgroup, 16 KiB
-constexpr int kExtMax = 4;              // KSCHED_EXT_MAX: columns of the dynamic LDS table, kExtMax * 256 * 8 slots * 8 B = 64 KiB
-
-constexpr int kAffMaxGroups = 64;       // KSCHED_AFF_MAX_GROUPS: one bit of a 64-bit word per group
-constexpr int kAffWords = 4;            // ExactArgs::af_pod: words per pod
-
 constexpr int kExactBlock = 256;
 constexpr int kExact1Block = 1024;  // k_exact1: the whole node set in one workgroup
 
 // host-side launchers (ksched_exact.hip).  fast53: every allocatable and request magnitude stays
 // below 2^52 for the whole call (host-checked), enabling (double)(a-r) == (double)a - (double)r.
-// One launch of k_exact<run>.  kRunGang: a.gang_end set (a.gang_placed may be null); kRunSpread: a.sp_* set; kRunExt:
-// a.ext* set, dynamic LDS of a.n_ext * block * npt * 8 bytes; kRunAll: a.gang_end, a.sp_word and a.ext_word set, the
-// spread table's fields set or sp_S == 0, the extended-resource table's set or n_ext == 0; kRunAffinity: a.af_* set,
-// dynamic LDS of block * npt * 20 bytes (two 8-byte words and the domain of every slot); kRunFull: kRunAll's fields, and
-// kRunAffinity's set or a.af_dom null, with a.af_undo_* set, dynamic LDS of both (the affinity words behind the columns:
-// above 64 KiB, so the launcher raises the kernel's limit first); kRunFullWhy: kRunFull's fields and a.why_* set, the
-// same dynamic LDS.  (An extension never runs
+// One launch of k_exact<run>: the fields of every constraint exact_kind(run) carries must be set, a table's "off" form
+// accepted only where the kind is optional (hipErrorInvalidValue otherwise).  Dynamic LDS: ext, a.n_ext * block * npt *
+// 8 bytes; aff, block * npt * 20 bytes (two 8-byte words and the domain of every slot) where the table is given; the
+// kinds with both may pass 64 KiB, so the launcher raises the kernel's limit first.  (A constrained kind never runs
 // k_exact1: the one-workgroup kernel knows no gang log and no spread, extended-resource or affinity table.)
 hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool fast53, const ExactArgs &a, int block,
                         bool cooperative, hipStream_t s);
@@ -110,3 +132,4 @@ hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool
 hipError_t launch_exact1(int npt, int bs, int prio, int dom, bool lab, bool f53, const ExactArgs &a, hipStream_t s);
 
 }  // namespace ksched
+#endif  // __HIPCC__

@@ -1,11 +1,9 @@
-// ksched_exact.hip -- CDNA4 (gfx950) kernels of exact mode: k_exact with its extensions (gangs, topology spread,
-// extended resources -- each alone, or all three composed -- and inter-pod affinity, alone), the one-workgroup k_exact1,
-// and their launchers.
+// ksched_exact.hip -- CDNA4 (gfx950) kernels of exact mode: k_exact in the kinds of ksched_exact.h's table (exact_kind),
+// the one-workgroup k_exact1, and their launchers.
 // Compiled with -ffp-contract=off: every double op rounds individually, exactly like the Go reference.
-// Four objects, as ksched_pipe.hip's three (-DKSCHED_EXACT_PART): part 0 is every kind but affinity and full, k_exact1
-// and the launchers; part 1 is the affinity kind's 40 instantiations behind launch_exact_affinity; part 2 the full
-// kind's (gangs, spread, extended resources and affinity composed) behind launch_exact_full; part 3 the full kind with
-// the at-its-turn reasons of the pods that fit nowhere (kRunFullWhy) behind launch_exact_full_why.
+// Four objects, as ksched_pipe.hip's three (-DKSCHED_EXACT_PART): part 0 is the kinds kRunPlain to kRunAll, k_exact1
+// and the launchers; parts 1, 2 and 3 are the 40 instantiations each of kRunAffinity, kRunFull and kRunFullWhy, behind
+// launch_exact_affinity, launch_exact_full and launch_exact_full_why.
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -213,10 +211,9 @@ __device__ __forceinline__ uint64_t *aff_table() {
 // ------------------------------------------------------------------------------------------------
 template <int NPT, int PRIO, int DOM, bool LAB, bool F53, ExactRun RUN>
 __global__ __launch_bounds__(kExactBlock) void k_exact(ExactArgs A) {
-    constexpr bool WHY = RUN == kRunFullWhy;
-    constexpr bool FULL = RUN == kRunFull || WHY;
-    constexpr bool ALL = RUN == kRunAll || FULL, AFF = RUN == kRunAffinity || FULL;
-    constexpr bool GANG = RUN == kRunGang || ALL, SPREAD = RUN == kRunSpread || ALL, EXT = RUN == kRunExt || ALL;
+    constexpr ExactKind KIND = exact_kind(RUN);
+    constexpr bool WHY = KIND.why, FULL = KIND.undo, ALL = KIND.optional, AFF = KIND.aff;
+    constexpr bool GANG = KIND.gang, SPREAD = KIND.spread, EXT = KIND.ext;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -947,22 +944,19 @@ namespace {
 
 template <int NPT, int PRIO, int DOM, bool LAB, bool F53, ExactRun RUN>
 hipError_t exact_one(const ExactArgs &a, int block, bool coop, hipStream_t s) {
-    constexpr bool FULL = RUN == kRunFull || RUN == kRunFullWhy;
-    constexpr bool EXT = RUN == kRunExt || RUN == kRunAll;
+    constexpr ExactKind K = exact_kind(RUN);
     auto fn = k_exact<NPT, PRIO, DOM, LAB, F53, RUN>;
-    // EXT: the workgroup's slots of every column (ext_table), at most kExtMax * 256 * 8 * 8 B = 64 KiB (kRunAll without
-    // a table: n_ext == 0, none)
-    // AFF: the workgroup's slots of node_member and node_anti_host and their domains (aff_table), at most 256 * 8 * 20 B
-    // = 40 KiB beside the 16 KiB static zone table
-    // FULL: both, the affinity words behind the columns and only where the call has a table: up to 104 KiB, beyond the
-    // 64 KiB a kernel is admitted to by default -- so the kernel's first launch on a device raises its limit to the
-    // kind's maximum there (full_lds_limit)
-    constexpr bool AFF = RUN == kRunAffinity;
+    // ext: the workgroup's slots of every column (ext_table), at most kExtMax * 256 * 8 * 8 B = 64 KiB (no table:
+    // n_ext == 0, none)
+    // aff: the workgroup's slots of node_member and node_anti_host and their domains (aff_table), at most 256 * 8 * 20 B
+    // = 40 KiB beside the 16 KiB static zone table, and only where the call has a table
+    // both: the affinity words behind the columns, up to 104 KiB, beyond the 64 KiB a kernel is admitted to by default
+    // -- so the kernel's first launch on a device raises its limit to the kind's maximum there (full_lds_limit)
     constexpr size_t aff = (size_t)kExactBlock * NPT * (2 * sizeof(uint64_t) + sizeof(int32_t));
-    const size_t cols = (size_t)a.n_ext * kExactBlock * NPT * sizeof(int64_t);
-    const size_t lds = FULL ? cols + (a.af_dom ? aff : 0) : EXT ? cols : AFF ? aff : 0;
-    if ((EXT || AFF || FULL) && block != kExactBlock) return hipErrorInvalidValue;
-    if constexpr (FULL) {
+    const size_t cols = K.ext ? (size_t)a.n_ext * kExactBlock * NPT * sizeof(int64_t) : 0;
+    const size_t lds = cols + (K.aff && a.af_dom ? aff : 0);
+    if ((K.ext || K.aff) && block != kExactBlock) return hipErrorInvalidValue;
+    if constexpr (K.ext && K.aff) {
         if (a.n_ext < 0 || a.n_ext > kExtMax) return hipErrorInvalidValue;
         const hipError_t e = full_lds_limit((const void *)fn, (size_t)kExtMax * kExactBlock * NPT * sizeof(int64_t) + aff);
         if (e != hipSuccess) return e;
@@ -1044,50 +1038,27 @@ hipError_t exact1_npt(int npt, int bs, const ExactArgs &a, hipStream_t s) {
 #if KSCHED_EXACT_PART == 0
 hipError_t launch_exact(ExactRun run, int npt, int prio, int dom, bool lab, bool f53, const ExactArgs &a, int block,
                         bool coop, hipStream_t s) {
-    switch (run) {  // the extension's fields of ExactArgs
-        case kRunPlain: break;
-        case kRunGang:
-            if (!a.gang_end) return hipErrorInvalidValue;
-            break;
-        case kRunSpread:
-            if (!a.sp_dom || !a.sp_counts || !a.sp_skew || !a.sp_word || a.sp_D < 1 || a.sp_S < 1 ||
-                (int64_t)a.sp_D * a.sp_S > kSpreadMaxCells || a.sp_S > kSpreadMaxGroups)
-                return hipErrorInvalidValue;
-            break;
-        case kRunExt:
-            if (!a.ext || !a.ext_req || !a.ext_word || a.n_ext < 1 || a.n_ext > kExtMax) return hipErrorInvalidValue;
-            break;
-        case kRunAll:  // each kind's fields, with "no table" (sp_S == 0, n_ext == 0) accepted for this kind only
-            if (!a.gang_end || !a.sp_word || !a.ext_word) return hipErrorInvalidValue;
-            if (a.sp_S != 0 && (!a.sp_dom || !a.sp_counts || !a.sp_skew || a.sp_D < 1 || a.sp_S < 1 ||
-                                (int64_t)a.sp_D * a.sp_S > kSpreadMaxCells || a.sp_S > kSpreadMaxGroups))
-                return hipErrorInvalidValue;
-            if (a.n_ext != 0 && (!a.ext || !a.ext_req || a.n_ext < 1 || a.n_ext > kExtMax)) return hipErrorInvalidValue;
-            break;
-        case kRunAffinity:
-            if (!a.af_dom || !a.af_member || !a.af_anti_host || !a.af_anti_zone || !a.af_zone || !a.af_any || !a.af_word ||
-                !a.af_pod || a.af_D < 0 || a.af_D > kSpreadMaxDomains)
-                return hipErrorInvalidValue;
-            return launch_exact_affinity(npt, prio, dom, lab, f53, a, block, coop, s);
-        case kRunFull:  // kRunAll's and kRunAffinity's checks, "no table" (af_dom null) accepted for affinity too
-        case kRunFullWhy:  // ... and the buffers of the reasons: rows of bytes only where there are rows at all
-            if (!a.gang_end || !a.sp_word || !a.ext_word || !a.af_word || !a.af_undo_slot || !a.af_undo_zone)
-                return hipErrorInvalidValue;
-            if (a.sp_S != 0 && (!a.sp_dom || !a.sp_counts || !a.sp_skew || a.sp_D < 1 || a.sp_S < 1 ||
-                                (int64_t)a.sp_D * a.sp_S > kSpreadMaxCells || a.sp_S > kSpreadMaxGroups))
-                return hipErrorInvalidValue;
-            if (a.n_ext != 0 && (!a.ext || !a.ext_req || a.n_ext < 1 || a.n_ext > kExtMax)) return hipErrorInvalidValue;
-            if (a.af_dom && (!a.af_member || !a.af_anti_host || !a.af_anti_zone || !a.af_zone || !a.af_any || !a.af_pod ||
-                             a.af_D < 0 || a.af_D > kSpreadMaxDomains))
-                return hipErrorInvalidValue;
-            if (!a.af_dom && a.af_D != 0) return hipErrorInvalidValue;
-            if (run == kRunFull) return launch_exact_full(npt, prio, dom, lab, f53, a, block, coop, s);
-            if (!a.why_nofit || a.why_rows < 0 || a.why_node_rows < 0 || a.why_node_rows > a.why_rows ||
-                (a.why_rows > 0 && (!a.why_pod || !a.why_counts)) || (a.why_node_rows > 0 && !a.why_reason))
-                return hipErrorInvalidValue;
-            return launch_exact_full_why(npt, prio, dom, lab, f53, a, block, coop, s);
-        default: return hipErrorInvalidValue;
-    }
+    if (run < kRunPlain || run > kRunFullWhy) return hipErrorInvalidValue;
+    // the fields of ExactArgs, constraint by constraint: the per-pod words always, the table's "off" form (sp_S == 0,
+    // n_ext == 0, af_dom null) accepted only where the kind is optional
+    const ExactKind k = exact_kind(run);
+    const bool spread_ok = a.sp_word && ((k.optional && a.sp_S == 0) ||
+                                         (a.sp_dom && a.sp_counts && a.sp_skew && a.sp_D >= 1 && a.sp_S >= 1 &&
+                                          (int64_t)a.sp_D * a.sp_S <= kSpreadMaxCells && a.sp_S <= kSpreadMaxGroups));
+    const bool ext_ok = a.ext_word && ((k.optional && a.n_ext == 0) || (a.ext && a.ext_req && a.n_ext >= 1 && a.n_ext <= kExtMax));
+    const bool aff_ok = a.af_word && (k.optional && !a.af_dom
+                                          ? a.af_D == 0
+                                          : a.af_dom && a.af_member && a.af_anti_host && a.af_anti_zone && a.af_zone &&
+                                                a.af_any && a.af_pod && a.af_D >= 0 && a.af_D <= kSpreadMaxDomains);
+    // (the reasons: rows of bytes only where there are rows at all)
+    const bool why_ok = a.why_nofit && a.why_rows >= 0 && a.why_node_rows >= 0 && a.why_node_rows <= a.why_rows &&
+                        (a.why_rows == 0 || (a.why_pod && a.why_counts)) && (a.why_node_rows == 0 || a.why_reason);
+    if ((k.gang && !a.gang_end) || (k.spread && !spread_ok) || (k.ext && !ext_ok) || (k.aff && !aff_ok) ||
+        (k.undo && (!a.af_undo_slot || !a.af_undo_zone)) || (k.why && !why_ok))
+        return hipErrorInvalidValue;
+    if (run == kRunAffinity) return launch_exact_affinity(npt, prio, dom, lab, f53, a, block, coop, s);
+    if (run == kRunFull) return launch_exact_full(npt, prio, dom, lab, f53, a, block, coop, s);
+    if (run == kRunFullWhy) return launch_exact_full_why(npt, prio, dom, lab, f53, a, block, coop, s);
     KSCHED_DISPATCH(prio, dom, lab, f53, (exact_run<P_, D_, L_, F_>(run, npt, a, block, coop, s)));
 }
 

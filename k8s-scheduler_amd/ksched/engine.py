@@ -25,6 +25,42 @@ def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
 
+class _Constraints:
+    """The constraint arguments of the schedule_* calls and rank_full as the library takes them: contiguous arrays of
+    its types (None stays None: a NULL pointer; gang_min and enforce only with gang_off and group), the gang_placed
+    buffer, and each constraint's arguments as ctypes values in the prototypes' order.  check(p): every length against
+    the pod count."""
+
+    def __init__(self, engine, gang_off=None, gang_min=None, group=None, enforce=None, req_ext=None, member=None,
+                 anti_host=None, anti_zone=None, aff_group=None, aff_zone=None):
+        def arr(a, dtype, given=True):
+            return None if a is None or not given else np.ascontiguousarray(a, dtype=dtype)
+
+        def flags(a, given=True):
+            return None if a is None or not given else np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8)
+        off = arr(gang_off, np.int64)
+        ng = 0 if off is None else off.shape[0] - 1
+        gmin = arr(gang_min, np.int32, off is not None)
+        assert ng >= 0 and (gmin is None or gmin.shape[0] == ng)
+        gr = arr(group, np.int32)
+        self.per_pod = [gr, flags(enforce, gr is not None)] + [arr(m, np.uint64) for m in (member, anti_host, anti_zone)] + [
+            arr(aff_group, np.int32), flags(aff_zone)]
+        self.req_ext = arr(req_ext, np.int64)
+        self.ext_rows = getattr(engine, "_ext_shape", (None,))[0]  # the load_ext() table's, where one was loaded
+        self.gp = np.empty(ng, np.int32)
+        self.placed = L.ptr(self.gp, C.c_int32)
+        self.gang_arrays = (off, gmin)  # (held while the pointers are in use)
+        self.gangs = (ng, L.ptr(off, C.c_int64), L.ptr(gmin, C.c_int32))
+        types = (C.c_int32, C.c_uint8, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint8)
+        ptrs = tuple(L.ptr(a, t) for a, t in zip(self.per_pod, types))
+        self.spread, self.ext, self.affinity = ptrs[:2], (L.ptr(self.req_ext, C.c_int64),), ptrs[2:]
+
+    def check(self, p):
+        assert all(a is None or a.shape == (p,) for a in self.per_pod)
+        re_ = self.req_ext
+        assert re_ is None or (re_.ndim == 2 and re_.shape == (re_.shape[0] if self.ext_rows is None else self.ext_rows, p))
+
+
 class Group:
     """In-process rank group (ksched_group): R contexts of this process on one device exchange their
     per-batch candidate lists through a shared device ring instead of RCCL.  Each rank's Engine calls
@@ -310,19 +346,19 @@ class Engine:
         self.sync()
         return self.results()
 
-    def _schedule_with(self, name, req_cpu, req_mem, req_pods, selector, extra, tail=()):
-        """What schedule_gangs / schedule_spread / schedule_ext / schedule_constrained / schedule_affinity / schedule_full / schedule_full_why share: the contiguous request arrays and their length
-        check, the three outputs, the call of ksched_<name> -- extra(p), the extension's arguments (checked against
-        the pod count), go between the selectors and the outputs, tail after them -- and self.p.  Returns (idx,
-        score, feasible)."""
+    def _schedule_with(self, name, req_cpu, req_mem, req_pods, selector, k, extra, tail=()):
+        """What the constrained schedule calls share: the contiguous request arrays and their length check, the three
+        outputs, the call of ksched_<name> -- extra, the call's constraint arguments out of k (_Constraints, checked
+        here against the pod count), go between the selectors and the outputs, tail after them -- and self.p.  Returns
+        (idx, score, feasible)."""
         rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
         p = rc.shape[0]
         assert rm.shape[0] == p and rp.shape[0] == p
         sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
-        ext_args = extra(p)
+        k.check(p)
         oi = np.empty(p, np.int32); os_ = np.empty(p, np.float64); of = np.empty(p, np.int32)
         self._chk(getattr(L.lib(), "ksched_" + name)(self._ctx, p, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64),
-                                                     L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64), *ext_args,
+                                                     L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64), *extra,
                                                      L.ptr(oi, C.c_int32), L.ptr(os_, C.c_double), L.ptr(of, C.c_int32),
                                                      *tail), name)
         self.p = p
@@ -334,14 +370,9 @@ class Engine:
         rejected gang's commits are undone before the next gang is evaluated.  One launch of the exact kernel,
         whatever the engine's mode.  Returns (idx, score, feasible, gang_placed): idx is GANG_REJECTED for a member
         that found a node in a rejected gang; gang_placed[g] = members bound (0 for a rejected gang)."""
-        off = _i64(gang_off)
-        ng = off.shape[0] - 1
-        gmin = None if gang_min is None else np.ascontiguousarray(gang_min, dtype=np.int32)
-        assert ng >= 0 and (gmin is None or gmin.shape[0] == ng)
-        gp = np.empty(ng, np.int32)
-        return self._schedule_with("schedule_gangs", req_cpu, req_mem, req_pods, selector,
-                                   lambda p: (ng, L.ptr(off, C.c_int64), L.ptr(gmin, C.c_int32)),
-                                   (L.ptr(gp, C.c_int32),)) + (gp,)
+        k = _Constraints(self, gang_off=_i64(gang_off), gang_min=gang_min)
+        return self._schedule_with("schedule_gangs", req_cpu, req_mem, req_pods, selector, k, k.gangs,
+                                   (k.placed,)) + (k.gp,)
 
     def load_spread(self, node_domain, max_skew, counts=None, n_domains=None):
         """The spread table of schedule_spread() (ksched_load_spread): node j lies in topology domain node_domain[j]
@@ -376,13 +407,8 @@ class Engine:
         group[i] of the load_spread() table (-1: none) and, where enforce[i] (None: every pod), may only land in a
         domain whose count stays within the group's max_skew of the emptiest domain; every placed pod of a group is
         counted.  One launch of the exact kernel, whatever the engine's mode.  Returns (idx, score, feasible)."""
-        gr = np.ascontiguousarray(group, dtype=np.int32)
-        en = None if enforce is None else np.ascontiguousarray(np.asarray(enforce) != 0, dtype=np.uint8)
-
-        def extra(p):
-            assert gr.shape[0] == p and (en is None or en.shape[0] == p)
-            return L.ptr(gr, C.c_int32), L.ptr(en, C.c_uint8)
-        return self._schedule_with("schedule_spread", req_cpu, req_mem, req_pods, selector, extra)
+        k = _Constraints(self, group=np.ascontiguousarray(group, dtype=np.int32), enforce=enforce)
+        return self._schedule_with("schedule_spread", req_cpu, req_mem, req_pods, selector, k, k.spread)
 
     def load_ext(self, node_ext):
         """The extended-resource table of schedule_ext() (ksched_load_ext): node_ext[r, j], int64 [R, n] with R in
@@ -406,12 +432,8 @@ class Engine:
         int64 [R, p] (None: zeros), is pod i's request for resource r; a zero request is not checked, any other must
         not exceed the node's column, and the placed pod's requests are subtracted from its node's columns.  One
         launch of the exact kernel, whatever the engine's mode.  Returns (idx, score, feasible)."""
-        re_ = None if req_ext is None else np.ascontiguousarray(req_ext, dtype=np.int64)
-
-        def extra(p):
-            assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], p))
-            return (L.ptr(re_, C.c_int64),)
-        return self._schedule_with("schedule_ext", req_cpu, req_mem, req_pods, selector, extra)
+        k = _Constraints(self, req_ext=req_ext)
+        return self._schedule_with("schedule_ext", req_cpu, req_mem, req_pods, selector, k, k.ext)
 
     def schedule_constrained(self, req_cpu, req_mem, req_pods, selector, gang_off=None, gang_min=None, group=None,
                              enforce=None, req_ext=None):
@@ -421,22 +443,9 @@ class Engine:
         gang undoes all three.  Each constraint is off where its argument is None: gang_off (every pod a gang of one),
         group (no pod in a spread group; no table needed, a loaded one stays), req_ext (the same for the ext table).
         Returns (idx, score, feasible, gang_placed); gang_placed is empty when gang_off is None."""
-        off = None if gang_off is None else _i64(gang_off)
-        ng = 0 if off is None else off.shape[0] - 1
-        gmin = None if gang_min is None or off is None else np.ascontiguousarray(gang_min, dtype=np.int32)
-        assert ng >= 0 and (gmin is None or gmin.shape[0] == ng)
-        gr = None if group is None else np.ascontiguousarray(group, dtype=np.int32)
-        en = None if enforce is None or gr is None else np.ascontiguousarray(np.asarray(enforce) != 0, dtype=np.uint8)
-        re_ = None if req_ext is None else np.ascontiguousarray(req_ext, dtype=np.int64)
-        gp = np.empty(ng, np.int32)
-
-        def extra(p):
-            assert (gr is None or gr.shape[0] == p) and (en is None or en.shape[0] == p)
-            assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], p))
-            return (ng, L.ptr(off, C.c_int64), L.ptr(gmin, C.c_int32), L.ptr(gr, C.c_int32), L.ptr(en, C.c_uint8),
-                    L.ptr(re_, C.c_int64))
-        return self._schedule_with("schedule_constrained", req_cpu, req_mem, req_pods, selector, extra,
-                                   (L.ptr(gp, C.c_int32),)) + (gp,)
+        k = _Constraints(self, gang_off, gang_min, group, enforce, req_ext)
+        return self._schedule_with("schedule_constrained", req_cpu, req_mem, req_pods, selector, k,
+                                   k.gangs + k.spread + k.ext, (k.placed,)) + (k.gp,)
 
     def load_affinity(self, node_domain=None, node_member=None, node_anti_host=None, node_anti_zone=None, n_domains=None):
         """The affinity table of schedule_affinity() (ksched_load_affinity): node j lies in zone node_domain[j] (-1: it
@@ -472,14 +481,8 @@ class Engine:
         of that group on its node (aff_zone[i] == 0) or in its zone, unless it is the first of its own group.  uint64[p]
         masks, int32[p] group, uint8[p] scope; None: zeros (no group).  One launch of the exact kernel, whatever the
         engine's mode.  Returns (idx, score, feasible)."""
-        masks = [None if m is None else np.ascontiguousarray(m, dtype=np.uint64) for m in (member, anti_host, anti_zone)]
-        ag = None if aff_group is None else np.ascontiguousarray(aff_group, dtype=np.int32)
-        az = None if aff_zone is None else np.ascontiguousarray(np.asarray(aff_zone) != 0, dtype=np.uint8)
-
-        def extra(p):
-            assert all(m is None or m.shape == (p,) for m in masks + [ag, az])
-            return tuple(L.ptr(m, C.c_uint64) for m in masks) + (L.ptr(ag, C.c_int32), L.ptr(az, C.c_uint8))
-        return self._schedule_with("schedule_affinity", req_cpu, req_mem, req_pods, selector, extra)
+        k = _Constraints(self, member=member, anti_host=anti_host, anti_zone=anti_zone, aff_group=aff_group, aff_zone=aff_zone)
+        return self._schedule_with("schedule_affinity", req_cpu, req_mem, req_pods, selector, k, k.affinity)
 
     def schedule_full(self, req_cpu, req_mem, req_pods, selector, gang_off=None, gang_min=None, group=None, enforce=None,
                       req_ext=None, member=None, anti_host=None, anti_zone=None, aff_group=None, aff_zone=None):
@@ -490,34 +493,9 @@ class Engine:
         back to their values before the gang's first member.  gang_off, group and req_ext switch their constraint on as
         in schedule_constrained(); affinity is on where any of its five arguments is given (None then: zeros, no
         group).  Returns (idx, score, feasible, gang_placed); gang_placed is empty when gang_off is None."""
-        extra, gp = self._full_args(gang_off, gang_min, group, enforce, req_ext, member, anti_host, anti_zone, aff_group,
-                                    aff_zone)
-        return self._schedule_with("schedule_full", req_cpu, req_mem, req_pods, selector, extra,
-                                   (L.ptr(gp, C.c_int32),)) + (gp,)
-
-    def _full_args(self, gang_off, gang_min, group, enforce, req_ext, member, anti_host, anti_zone, aff_group, aff_zone):
-        """schedule_full's and schedule_full_why's constraint arguments as contiguous arrays: (extra, gang_placed) for
-        _schedule_with, extra(p) checking every length against the pod count."""
-        off = None if gang_off is None else _i64(gang_off)
-        ng = 0 if off is None else off.shape[0] - 1
-        gmin = None if gang_min is None or off is None else np.ascontiguousarray(gang_min, dtype=np.int32)
-        assert ng >= 0 and (gmin is None or gmin.shape[0] == ng)
-        gr = None if group is None else np.ascontiguousarray(group, dtype=np.int32)
-        en = None if enforce is None or gr is None else np.ascontiguousarray(np.asarray(enforce) != 0, dtype=np.uint8)
-        re_ = None if req_ext is None else np.ascontiguousarray(req_ext, dtype=np.int64)
-        masks = [None if m is None else np.ascontiguousarray(m, dtype=np.uint64) for m in (member, anti_host, anti_zone)]
-        ag = None if aff_group is None else np.ascontiguousarray(aff_group, dtype=np.int32)
-        az = None if aff_zone is None else np.ascontiguousarray(np.asarray(aff_zone) != 0, dtype=np.uint8)
-        gp = np.empty(ng, np.int32)
-
-        def extra(p):
-            assert (gr is None or gr.shape[0] == p) and (en is None or en.shape[0] == p)
-            assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], p))
-            assert all(m is None or m.shape == (p,) for m in masks + [ag, az])
-            return ((ng, L.ptr(off, C.c_int64), L.ptr(gmin, C.c_int32), L.ptr(gr, C.c_int32), L.ptr(en, C.c_uint8),
-                     L.ptr(re_, C.c_int64)) + tuple(L.ptr(m, C.c_uint64) for m in masks) +
-                    (L.ptr(ag, C.c_int32), L.ptr(az, C.c_uint8)))
-        return extra, gp
+        k = _Constraints(self, gang_off, gang_min, group, enforce, req_ext, member, anti_host, anti_zone, aff_group, aff_zone)
+        return self._schedule_with("schedule_full", req_cpu, req_mem, req_pods, selector, k,
+                                   k.gangs + k.spread + k.ext + k.affinity, (k.placed,)) + (k.gp,)
 
     def schedule_full_why(self, req_cpu, req_mem, req_pods, selector, gang_off=None, gang_min=None, group=None,
                           enforce=None, req_ext=None, member=None, anti_host=None, anti_zone=None, aff_group=None,
@@ -530,9 +508,8 @@ class Engine:
         uint8[min(r, node_rows), n] | None (node_rows 0), nofit): r = min(nofit, why_rows) recorded rows, nofit the
         call's NO_FIT pods in all.  trim=False returns all why_rows / node_rows rows as the library filled them: -1
         and zeros past the recorded ones."""
-        extra, gp = self._full_args(gang_off, gang_min, group, enforce, req_ext, member, anti_host, anti_zone, aff_group,
-                                    aff_zone)
-        wr = _i64(req_cpu).shape[0] if why_rows is None else int(why_rows)
+        k = _Constraints(self, gang_off, gang_min, group, enforce, req_ext, member, anti_host, anti_zone, aff_group, aff_zone)
+        wr =_i64(req_cpu).shape[0] if why_rows is None else int(why_rows)
         nr, n = int(node_rows), max(self.n, 0)
         # (the library refuses shapes these cannot hold before it writes: never a buffer sized from a refused argument)
         pods = np.empty(max(wr, 0), np.int32)
@@ -540,13 +517,14 @@ class Engine:
         ok = 0 <= nr <= wr and nr * n <= L.WHY_MAX_NODE_BYTES
         reasons = np.empty((nr, n), np.uint8) if nr > 0 and ok else None
         nofit = np.zeros(1, np.int64)
-        out = self._schedule_with("schedule_full_why", req_cpu, req_mem, req_pods, selector, extra,
-                                  (L.ptr(gp, C.c_int32), wr, L.ptr(pods if wr > 0 else None, C.c_int32),
+        out = self._schedule_with("schedule_full_why", req_cpu, req_mem, req_pods, selector, k,
+                                  k.gangs + k.spread + k.ext + k.affinity,
+                                  (k.placed, wr, L.ptr(pods if wr > 0 else None, C.c_int32),
                                    L.ptr(counts if wr > 0 else None, C.c_int64), nr, L.ptr(reasons, C.c_uint8),
                                    L.ptr(nofit, C.c_int64)))
         total = int(nofit[0])
         r = min(total, wr) if trim else wr
-        return out + (gp, (pods[:r], counts[:r], None if nr == 0 else reasons[:min(r, nr)], total))
+        return out + (k.gp, (pods[:r], counts[:r], None if nr == 0 else reasons[:min(r, nr)], total))
 
     def rank_full(self, req_cpu, req_mem, req_pods, selector=None, k: int = 16, group=None, enforce=None, req_ext=None,
                   member=None, anti_host=None, anti_zone=None, aff_group=None, aff_zone=None):
@@ -560,21 +538,14 @@ class Engine:
         m = rc.shape[0]
         assert rm.shape[0] == m and rp.shape[0] == m
         sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
-        gr = None if group is None else np.ascontiguousarray(group, dtype=np.int32)
-        en = None if enforce is None or gr is None else np.ascontiguousarray(np.asarray(enforce) != 0, dtype=np.uint8)
-        re_ = None if req_ext is None else np.ascontiguousarray(req_ext, dtype=np.int64)
-        masks = [None if x is None else np.ascontiguousarray(x, dtype=np.uint64) for x in (member, anti_host, anti_zone)]
-        ag = None if aff_group is None else np.ascontiguousarray(aff_group, dtype=np.int32)
-        az = None if aff_zone is None else np.ascontiguousarray(np.asarray(aff_zone) != 0, dtype=np.uint8)
-        assert all(x is None or x.shape == (m,) for x in [gr, en, ag, az] + masks)
-        assert re_ is None or (re_.ndim == 2 and re_.shape == (getattr(self, "_ext_shape", re_.shape)[0], m))
+        cs = _Constraints(self, None, None, group, enforce, req_ext, member, anti_host, anti_zone, aff_group, aff_zone)
+        cs.check(m)
         kk = max(int(k), 0)
         idx = np.empty((m, kk), np.int32); score = np.empty((m, kk), np.float64); reason = np.empty((m, kk), np.uint8)
         count = np.empty(m, np.int32); feas = np.empty(m, np.int32); hist = np.empty((m, L.NUM_REASONS_FULL), np.int64)
         self._chk(L.lib().ksched_rank_full(
             self._ctx, m, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64), L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64),
-            L.ptr(gr, C.c_int32), L.ptr(en, C.c_uint8), L.ptr(re_, C.c_int64), *(L.ptr(x, C.c_uint64) for x in masks),
-            L.ptr(ag, C.c_int32), L.ptr(az, C.c_uint8), int(k), L.ptr(idx, C.c_int32), L.ptr(score, C.c_double),
+            *cs.spread, *cs.ext, *cs.affinity, int(k), L.ptr(idx, C.c_int32), L.ptr(score, C.c_double),
             L.ptr(reason, C.c_uint8), L.ptr(count, C.c_int32), L.ptr(feas, C.c_int32), L.ptr(hist, C.c_int64)),
             "rank_full")
         return idx, score, reason, count, feas, hist

@@ -676,18 +676,62 @@ class FakeCluster:
         idx, score, feas = self.engine.schedule(rc, rm, rp, sel)
         return self._resolve(pending, idx, self._explain_failures(idx) if self.explain_failures else {})
 
+    # the engine call of each set of constraints (gangs, spread, ext, affinity)
+    _CONSTRAINED_CALLS = {(True, False, False, False): "schedule_gangs", (False, True, False, False): "schedule_spread",
+                          (False, False, True, False): "schedule_ext", (False, False, False, True): "schedule_affinity",
+                          (True, True, True, False): "schedule_constrained", (True, True, True, True): "schedule_full"}
+
+    def _schedule_under(self, pending, gangs=False, spread=False, ext=False, affinity=False, why=False, node_rows=None):
+        """What the constrained schedule_* methods share.  With gangs the pending pods are grouped first (group_gangs
+        reorders them); the tables wanted are built for that list from self.pods' bound pods (spread_tables,
+        ext_tables, affinity_tables), all of them before the first is loaded; then the one engine call those constraints
+        have, with the per-pod arguments in its order, resolved through _resolve_gangs (gangs) or _resolve.  why: the
+        call's _why form, with the per-node lines of the first node_rows pods that fit nowhere (None: all)."""
+        pods = self.unscheduled_pods() if pending is None else pending
+        off = gmin = names = None
+        if gangs:
+            pods, off, gmin = group_gangs(pods)
+        bound = [p for p in self.pods if p.node_name]
+        args, loads = ([off, gmin] if gangs else []), []
+        if spread:
+            node_domain, skew, counts, group, enforce = spread_tables(self.nodes, bound, pods)
+            loads.append(lambda: self.engine.load_spread(node_domain, skew, counts))
+            args += [group, enforce]
+        if ext:
+            names, node_ext, req_ext = ext_tables(self.nodes, bound, pods)
+            loads.append(lambda: self.engine.load_ext(node_ext))
+            args.append(req_ext)
+        if affinity:
+            t = affinity_tables(self.nodes, bound, pods)
+            loads.append(lambda: self.engine.load_affinity(*t[:4]))
+            args += t[4:]
+        for load in loads:
+            load()
+        rc, rm, rp = pack_pods(pods)
+        sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
+        call = getattr(self.engine, self._CONSTRAINED_CALLS[gangs, spread, ext, affinity] + ("_why" if why else ""))
+        texts = None
+        if why:
+            rows = len(pods) if node_rows is None else min(int(node_rows), len(pods))
+            idx, _, _, placed, (wpod, _, reasons, _) = call(rc, rm, rp, sel, *args, why_rows=rows, node_rows=rows)
+            texts = {}
+            for r in range(0 if reasons is None else len(reasons)):
+                k = int(wpod[r])
+                lines = [f"fit failure on node ({self.nodes[j].name}): {L.reason_text_full(int(c), names)}"
+                         for j, c in enumerate(reasons[r]) if c != L.REASON_FIT]
+                texts[k] = f"pod ({pods[k].name}) failed to fit in any node\n" + "\n".join(lines)
+        else:
+            idx, _, _, *placed = call(rc, rm, rp, sel, *args)
+            placed = placed[0] if gangs else None
+        return self._resolve_gangs(pods, off, gmin, idx, placed, texts) if gangs else self._resolve(pods, idx)
+
     def schedule_gangs(self, pending: Optional[List[Pod]] = None):
         """schedule_pods with pod groups (group_gangs; ksched_schedule_gangs): one engine call resolves every gang
         in order.  An accepted gang's placed members are bound in order; a rejected gang binds nothing and posts one
         FailedScheduling event per member.  Returns (pod, node | Exception) in the gangs' order -- GangRejected for
         a member that found a node in a rejected gang.  (No per-node "fit failure" lines: a rolled-back gang
         leaves no placements to rebuild a pod's state from; schedule_full_why collects them at the pod's turn.)"""
-        pending = self.unscheduled_pods() if pending is None else pending
-        pods, off, gmin = group_gangs(pending)
-        rc, rm, rp = pack_pods(pods)
-        sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
-        idx, _, _, placed = self.engine.schedule_gangs(rc, rm, rp, sel, off, gmin)
-        return self._resolve_gangs(pods, off, gmin, idx, placed)
+        return self._schedule_under(pending, gangs=True)
 
     def _resolve_gangs(self, pods, off, gmin, idx, placed, why=None):
         """A gang call's per-pod results, gang by gang, as the (pod, node | Exception) list (see schedule_gangs).  why:
@@ -719,14 +763,7 @@ class FakeCluster:
         pod that fits nowhere its constraint allows gets the usual FailedScheduling event (without per-node lines: the at-its-turn explain
         calls know no spread reason; explain_pod_full gives them against the current state, schedule_full_why at the
         pod's turn)."""
-        pending = self.unscheduled_pods() if pending is None else pending
-        node_domain, skew, counts, group, enforce = spread_tables(self.nodes, [p for p in self.pods if p.node_name],
-                                                                  pending)
-        self.engine.load_spread(node_domain, skew, counts)
-        rc, rm, rp = pack_pods(pending)
-        sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
-        idx, _, _ = self.engine.schedule_spread(rc, rm, rp, sel, group, enforce)
-        return self._resolve(pending, idx)
+        return self._schedule_under(pending, spread=True)
 
     def schedule_affinity(self, pending: Optional[List[Pod]] = None):
         """schedule_pods under the pods' required inter-pod affinity and anti-affinity terms (affinity_tables;
@@ -735,13 +772,7 @@ class FakeCluster:
         that fits nowhere its terms allow gets the usual FailedScheduling event (without per-node lines: the at-its-turn
         explain calls know no affinity reason; explain_pod_full gives them against the current state, schedule_full_why
         at the pod's turn)."""
-        pending = self.unscheduled_pods() if pending is None else pending
-        t = affinity_tables(self.nodes, [p for p in self.pods if p.node_name], pending)
-        self.engine.load_affinity(*t[:4])
-        rc, rm, rp = pack_pods(pending)
-        sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
-        idx, _, _ = self.engine.schedule_affinity(rc, rm, rp, sel, *t[4:])
-        return self._resolve(pending, idx)
+        return self._schedule_under(pending, affinity=True)
 
     def schedule_ext(self, pending: Optional[List[Pod]] = None):
         """schedule_pods with the pending pods' extended resources (ext_tables; ksched_schedule_ext) in the fit
@@ -749,13 +780,7 @@ class FakeCluster:
         pending pod in order and the binds follow.  Returns (pod, node | Exception); a pod that fits nowhere gets the
         usual FailedScheduling event (without per-node lines: the at-its-turn explain calls know no extended-resource
         reason; explain_pod_full gives them against the current state, schedule_full_why at the pod's turn)."""
-        pending = self.unscheduled_pods() if pending is None else pending
-        _, node_ext, req_ext = ext_tables(self.nodes, [p for p in self.pods if p.node_name], pending)
-        self.engine.load_ext(node_ext)
-        rc, rm, rp = pack_pods(pending)
-        sel = np.asarray([self.selector_of(p) for p in pending], dtype=np.uint64) if self.use_labels else None
-        idx, _, _ = self.engine.schedule_ext(rc, rm, rp, sel, req_ext)
-        return self._resolve(pending, idx)
+        return self._schedule_under(pending, ext=True)
 
     def schedule_constrained(self, pending: Optional[List[Pod]] = None):
         """schedule_gangs, schedule_spread and schedule_ext in one engine call (ksched_schedule_constrained): the
@@ -764,17 +789,7 @@ class FakeCluster:
         and one launch resolves every gang in order -- a rejected gang gives back the extended resources it took and
         the spread counts it raised.  Resolved gang by gang exactly as schedule_gangs does: binds, GangRejected and
         events."""
-        pending = self.unscheduled_pods() if pending is None else pending
-        pods, off, gmin = group_gangs(pending)
-        bound = [p for p in self.pods if p.node_name]
-        node_domain, skew, counts, group, enforce = spread_tables(self.nodes, bound, pods)
-        _, node_ext, req_ext = ext_tables(self.nodes, bound, pods)
-        self.engine.load_spread(node_domain, skew, counts)
-        self.engine.load_ext(node_ext)
-        rc, rm, rp = pack_pods(pods)
-        sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
-        idx, _, _, placed = self.engine.schedule_constrained(rc, rm, rp, sel, off, gmin, group, enforce, req_ext)
-        return self._resolve_gangs(pods, off, gmin, idx, placed)
+        return self._schedule_under(pending, gangs=True, spread=True, ext=True)
 
     def schedule_full(self, pending: Optional[List[Pod]] = None):
         """schedule_constrained and schedule_affinity in one engine call (ksched_schedule_full): the pending pods are
@@ -783,19 +798,7 @@ class FakeCluster:
         pods, and one launch resolves every gang in order -- a rejected gang gives back the extended resources it took,
         the spread counts it raised and the affinity words it set.  Resolved gang by gang exactly as schedule_gangs
         does: binds, GangRejected and events."""
-        pending = self.unscheduled_pods() if pending is None else pending
-        pods, off, gmin = group_gangs(pending)
-        bound = [p for p in self.pods if p.node_name]
-        node_domain, skew, counts, group, enforce = spread_tables(self.nodes, bound, pods)
-        _, node_ext, req_ext = ext_tables(self.nodes, bound, pods)
-        t = affinity_tables(self.nodes, bound, pods)
-        self.engine.load_spread(node_domain, skew, counts)
-        self.engine.load_ext(node_ext)
-        self.engine.load_affinity(*t[:4])
-        rc, rm, rp = pack_pods(pods)
-        sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
-        idx, _, _, placed = self.engine.schedule_full(rc, rm, rp, sel, off, gmin, group, enforce, req_ext, *t[4:])
-        return self._resolve_gangs(pods, off, gmin, idx, placed)
+        return self._schedule_under(pending, gangs=True, spread=True, ext=True, affinity=True)
 
     def schedule_full_why(self, pending: Optional[List[Pod]] = None, node_rows: Optional[int] = None):
         """schedule_full whose FailedScheduling events carry the reference's per-node lines (ksched_schedule_full_why):
@@ -804,27 +807,8 @@ class FakeCluster:
         included, in kube-scheduler's wordings (REASON_TEXT_FULL, an extended column by its resource's name).
         node_rows: the number of such pods that get the lines (None: all of them); the others get the plain event.
         Everything else -- tables, order, binds, GangRejected, return value -- is schedule_full's."""
-        pending = self.unscheduled_pods() if pending is None else pending
-        pods, off, gmin = group_gangs(pending)
-        bound = [p for p in self.pods if p.node_name]
-        node_domain, skew, counts, group, enforce = spread_tables(self.nodes, bound, pods)
-        names, node_ext, req_ext = ext_tables(self.nodes, bound, pods)
-        t = affinity_tables(self.nodes, bound, pods)
-        self.engine.load_spread(node_domain, skew, counts)
-        self.engine.load_ext(node_ext)
-        self.engine.load_affinity(*t[:4])
-        rc, rm, rp = pack_pods(pods)
-        sel = np.asarray([self.selector_of(p) for p in pods], dtype=np.uint64) if self.use_labels else None
-        rows = len(pods) if node_rows is None else min(int(node_rows), len(pods))
-        idx, _, _, placed, (wpod, _, reasons, _) = self.engine.schedule_full_why(
-            rc, rm, rp, sel, off, gmin, group, enforce, req_ext, *t[4:], why_rows=rows, node_rows=rows)
-        why = {}
-        for r in range(0 if reasons is None else len(reasons)):
-            k = int(wpod[r])
-            lines = [f"fit failure on node ({self.nodes[j].name}): {L.reason_text_full(int(c), names)}"
-                     for j, c in enumerate(reasons[r]) if c != L.REASON_FIT]
-            why[k] = f"pod ({pods[k].name}) failed to fit in any node\n" + "\n".join(lines)
-        return self._resolve_gangs(pods, off, gmin, idx, placed, why)
+        return self._schedule_under(pending, gangs=True, spread=True, ext=True, affinity=True, why=True,
+                                    node_rows=node_rows)
 
     def schedule_pod(self, pod: Pod, selector: Optional[int] = None):
         """schedulePod (anchor/schedule.go:68-89) for a single pod."""

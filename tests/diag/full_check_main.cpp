@@ -56,7 +56,7 @@ static int run(const Call &c) {
     Exact<uint64_t> m(c.member), ah(c.anti_host), anz(c.anti_zone);
     const FullArgs a{c.p, c.n_gangs, off.p, gmin.p, group.p, enf.p, req.p, m.p, ah.p, anz.p, ag.p, az.p};
     packed = FullPacked{};
-    return full_check_pack(a, c.S, c.R, c.aff_table, &packed, &why);
+    return full_check_pack(exact_kind(kRunFull), a, c.S, c.R, c.aff_table, &packed, &why);
 }
 
 // three pods, every constraint on: gangs {p0, p1}, {p2}; two groups, two columns

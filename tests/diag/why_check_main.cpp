@@ -61,7 +61,7 @@ static int run(const Call &c) {
     const FullArgs a{c.p, c.n_gangs, off.p, gmin.p, group.p, enf.p, req.p, mem.p, nullptr, nullptr, ag.p, nullptr};
     FullPacked k;
     why = nullptr;
-    if (const int code = full_check_pack(a, c.S, c.R, c.aff_valid, &k, &why)) return code;
+    if (const int code = full_check_pack(exact_kind(kRunFullWhy), a, c.S, c.R, c.aff_valid, &k, &why)) return code;
     const bool rows = c.why_rows > 0 && c.why_rows < 4096, nodes = c.node_rows > 0 && c.node_rows < 4096;
     Exact<int32_t> wp(std::vector<int32_t>(rows && !c.no_pod ? (size_t)c.why_rows : 0));
     Exact<int64_t> wc(std::vector<int64_t>(rows && !c.no_counts ? (size_t)c.why_rows * KSCHED_NUM_REASONS_FULL : 0));
