@@ -859,11 +859,21 @@ int ksched_set_timeout(ksched_ctx *ctx, int32_t persist_ms);
 int ksched_sync(ksched_ctx *ctx);                /* waits for the run; fills stats */
 int ksched_download_results(ksched_ctx *ctx, int64_t p, int32_t *out_idx, double *out_score, int32_t *out_feasible);
 int ksched_get_stats(const ksched_ctx *ctx, ksched_stats *out);
-/* Diagnostics (added within ABI 6: probe with dlsym(lib, "ksched_get_commit_stamps")): the first n <= 32 words of the
+/* Diagnostics (added within ABI 6: probe with dlsym(lib, "ksched_get_commit_stamps")): the first n <= 48 words of the
  * persistent commit's KSCHED_COMMIT_STAMPS sums of the last synced run -- zeros unless the context was created with
- * that variable set.  [12] rounds, [13] failed guesses, [14] batches, [15] batches whose early read of the merge count
- * sufficed, [29] batches whose inherited keys were loaded before the merges' wait, [30] batches that tried (those with an
- * older export to inherit, voided ones included); the others are cycle sums (ksched_diag.hip prints them). */
+ * that variable set (n <= 32 up to the library that added the fold masks: a larger n is KSCHED_E_INVALID there, and
+ * words 0-31 keep their meaning).  [12] rounds, [13] failed guesses, [14] batches, [15] batches whose early read of
+ * the merge count sufficed, [29] batches whose inherited keys were loaded before the merges' wait, [30] batches that
+ * tried (those with an older export to inherit, voided ones included); the others of 0-31 are cycle sums and the
+ * touched-node screen's column counts (ksched_diag.hip's print_persist_trace prints them, the fold masks' line too,
+ * with the KSCHED_PERSIST_TRACE summary; print_commit_stamps is the stream pipeline's).  The two commit workgroups add
+ * to the same words: the resource-priority (screened) kernels add the counts [5], [8], [12]-[14], [31] and [32]-[37]
+ * atomically, so they are exact; the best-price kernels keep plain adds for [5], [8], [12]-[14] and [31], which can
+ * lose a few per call (the cycle sums are plain adds in every kernel).  The screened commit's fold masks
+ * (KSCHED_NO_FOLD_MASK=1 turns them off): [32] rounds whose check read no wave's partial bests, [33] partial rows read
+ * over all checks (masks off: waves x rounds), [34] batches whose wave-0 state read none, [35] columns the confirm
+ * folds visited, [36] columns they skipped, [37] batches with a check that read none after an earlier one that read
+ * some; [38]-[47] are reserved (zero). */
 int ksched_get_commit_stamps(const ksched_ctx *ctx, int32_t n, int64_t *out);
 /* Diagnostics (added within ABI 6: probe with dlsym): the seeded score scan's counters of the last synced persistent
  * run, summed over the score workgroups, into out[5]: [0] (workgroup, batch) scans whose bound was seeded from the

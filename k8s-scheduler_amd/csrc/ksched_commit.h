@@ -48,6 +48,12 @@ constexpr int spc_slots() { return LAG3 ? 192 : 128; }
 static_assert(spc_slots<true>() + 1 <= kRescueMaxT, "RescueReq::ti must hold the persistent commit's touched slots");
 constexpr int kSpcInvalid = kSpcHash - 1;  // table position reserved for "no entry" (always taken)
 constexpr int kGS = 14;                     // words per guessed entry in SpcSmem::GS
+// The screened commit's fold masks (SpcSmem::fm).  A wave's partial best (pbk / pbx) is -inf in every lane unless one of
+// its columns was keyed exactly (touch_column returned true), and a guessed column that no pod needs holds kSkipKey in
+// every lane and, where no later pod's predicate changed, zeros in D: wave 0 folds only the waves and columns whose bit
+// is set (on c4 0.17 % of the guessed columns are keyed).  A wave without a keyed column writes no partials: its rows
+// keep what own[] left there.  KSCHED_NO_FOLD_MASK=1 (CommitArgs::fold_all) folds everything, as before the masks.
+constexpr int kFoldMaskBytes = 16;
 
 // The touched-node screen (persistent commit, resource priority).  A pod's key for a touched
 // node matters only where it can beat an untouched entry of the pod's list -- each of which keys at or above the
@@ -135,7 +141,13 @@ struct SpcSmem {
     int32_t *gs;      // per pod: slot of the guess
     double *pbk;      // [waves][64 pods] partial best key over the wave's guessed columns
     int64_t *pbx;     // [waves][64 pods] (slot << 32) | node of that best
-    int32_t *ctl;     // [0] round start c, [1] window end, [2] stop
+    int32_t *ctl;     // [0] round start c, [1] window end, [2] stop; [3] the persistent prologue's slot count nin (P2 ->
+                      // every thread, read before the barrier behind key_inherited), then, under KSCHED_COMMIT_STAMPS in
+                      // the screened kernels only, wave 0's state of counter word 37 for the batch (0 no check read
+                      // partials yet, 1 one did, 2 counted); a plain run never writes it after the prologue
+    uint32_t *fm;     // the screened commit's fold masks (kFoldMaskBytes; below): words 0-1 the round's guessed columns
+                      // that some pod needs (one 64-bit word, bit = guessing pod), [2] the waves that keyed a guessed
+                      // column this round, [3] the waves that keyed an entry of export(b - 1) (bit = wave)
     int32_t *own;     // [kSpcHash] lowest pod proposing each position in a guess iteration (64 = none);
                       // step 1 only (aliases pbk/pbx, which steps 2-3 use)
     uint64_t *GS;     // [64 pods][kGS] each pod's guessed entry: state a[3], labels, price, and the state after
@@ -536,6 +548,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
     // function cost a plain run through register allocation alone
     const bool sdbg = KSCHED_COMMIT_SPLIT && dbg;
     uint64_t t_fold = 0, t_probe = 0, t_pod = 0, t_load = 0;
+    uint64_t t_tstar = 0, t_resc = 0;  // trace columns 38-39: the t* fold over the waves' partials, the rescue leg
     SpcSmem m;
     {
         // every array but S below 64 KB: an LDS instruction's immediate offset (16 bits) then reaches it from one
@@ -559,6 +572,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
         m.gq = reinterpret_cast<int32_t *>(p); p += 64 * sizeof(int32_t);
         m.gs = reinterpret_cast<int32_t *>(p); p += 64 * sizeof(int32_t);
         m.ctl = reinterpret_cast<int32_t *>(p); p += 4 * sizeof(int32_t);
+        m.fm = reinterpret_cast<uint32_t *>(p); p += SCR ? kFoldMaskBytes : 0;  // (the unscreened kernels: no such words)
         m.thr = reinterpret_cast<float *>(p); p += 64 * sizeof(float);
         m.x2s = reinterpret_cast<int16_t *>(p); p += 64 * sizeof(int16_t);
         m.S = reinterpret_cast<double *>(p);
@@ -653,8 +667,18 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             const bool up = k != -__builtin_inf() && better(k, x.idx, pk, pi);
             pk = up ? k : pk; pi = up ? x.idx : pi; ps = up ? t : ps;
         }
-        m.pbk[wave * 64 + lane] = pk;
-        m.pbx[wave * 64 + lane] = ((int64_t)ps << 32) | (uint32_t)pi;
+        if constexpr (SCR) {
+            // (nex is wave-uniform.)  A wave that keyed no entry leaves its partials unwritten and its bit clear: the
+            // wave-0 state, behind the next barrier, folds the set waves only
+            if (nex > 0 || A.fold_all) {
+                m.pbk[wave * 64 + lane] = pk;
+                m.pbx[wave * 64 + lane] = ((int64_t)ps << 32) | (uint32_t)pi;
+                if (lane == 0) atomicOr(&m.fm[3], 1u << wave);
+            }
+        } else {
+            m.pbk[wave * 64 + lane] = pk;
+            m.pbx[wave * 64 + lane] = ((int64_t)ps << 32) | (uint32_t)pi;
+        }
         if (dfl != 0) atomicAdd(&m.dfacc[lane], dfl);
         if (SCR && A.dbg && lane == 0 && wave < ne) {  // diagnostics: entries keyed, exactly
             atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[16]), (unsigned long long)((ne - 1 - wave) / kSpcWaves + 1));
@@ -715,6 +739,9 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
         if (wave == 1 && lane < n2) xi = load_xrec<COH>(A.xin2->e, lane);
         for (int w = tid; w < kSpcHash; w += kSpcThreads) m.hk[w] = -1;
         if (tid < 64) { m.dfacc[tid] = 0; m.fcg[tid] = 0; m.tkc[tid] = tid == (kSpcInvalid >> 5) ? (1u << (kSpcInvalid & 31)) : 0u; }
+        if constexpr (SCR) {
+            if (tid == 0) m.fm[3] = 0;  // no wave has keyed an entry of export(b - 1) yet (key_inherited sets the bits)
+        }
         __syncthreads();
         // slots [0, n2) = export(b - 2) in entry order (a node export(b - 1) also holds is superseded in P2); own[]
         // (free until the guess step) maps their table positions to their slots
@@ -901,6 +928,14 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
     }
     int64_t placed = 0, nrounds = 0, nfail = 0, niters = 0, nseq = 0;
     int nfull = 0;  // wave 0: guess iterations that scanned all K entries
+    // the fold masks (SCR; kFoldMaskBytes above): one bit per wave
+    static_assert(kSpcWaves <= 32, "SpcSmem::fm: a wave mask is one 32-bit word");
+    constexpr uint32_t kAllWaves = 0xffffffffu >> (32 - kSpcWaves);
+    // diagnostics (KSCHED_COMMIT_STAMPS words 32-37, wave 0 lane 0): added where they arise, so a plain run keeps no
+    // count in registers through the rounds; the two commit workgroups add to the same words
+    auto fm_count = [&](int w, int64_t v) {
+        if (v) atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[w]), (unsigned long long)v);
+    };
     if (wave == 0) {
         int64_t ds2 = 0;
         double xk = -__builtin_inf();
@@ -915,11 +950,28 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
         cut = cut0;
 #pragma unroll
         for (int q = 0; q < K; ++q) cv += m.LI[q * 64 + lane] != kNoIdx;  // valid entries form a prefix
-        for (int w = 0; w < kSpcWaves; ++w) {
-            const double k = m.pbk[w * 64 + lane];
-            const int64_t x = m.pbx[w * 64 + lane];
-            const int32_t xi = (int32_t)(uint32_t)x;
-            if (k != -__builtin_inf() && better(k, xi, rbk, rbi)) { rbk = k; rbi = xi; rbs = (int32_t)(x >> 32); }
+        if constexpr (SCR) {
+            // the waves that keyed an entry of export(b - 1), lowest first: the fold order over the waves that take part
+            // is the one over all of them (a wave without a keyed entry would have contributed -inf in every lane)
+            uint32_t wm = (uint32_t)__builtin_amdgcn_readfirstlane((int)m.fm[3]) | (A.fold_all & kAllWaves);
+            if (dbg && lane == 0) {
+                fm_count(34, wm == 0);  // batches whose wave-0 state read no partials
+                m.ctl[3] = 0;           // (free since the prologue read nin: 1 once a check of this batch read some)
+            }
+            for (; wm != 0; wm &= wm - 1u) {
+                const int w = __builtin_ctz(wm);
+                const double k = m.pbk[w * 64 + lane];
+                const int64_t x = m.pbx[w * 64 + lane];
+                const int32_t xi = (int32_t)(uint32_t)x;
+                if (k != -__builtin_inf() && better(k, xi, rbk, rbi)) { rbk = k; rbi = xi; rbs = (int32_t)(x >> 32); }
+            }
+        } else {
+            for (int w = 0; w < kSpcWaves; ++w) {
+                const double k = m.pbk[w * 64 + lane];
+                const int64_t x = m.pbx[w * 64 + lane];
+                const int32_t xi = (int32_t)(uint32_t)x;
+                if (k != -__builtin_inf() && better(k, xi, rbk, rbi)) { rbk = k; rbi = xi; rbs = (int32_t)(x >> 32); }
+            }
         }
         if (LAG3 && xix != kNoIdx) {
             if (m.x2s[xe] >= 0) {  // the best entry has a slot of its own
@@ -1104,6 +1156,9 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             m.gq[lane] = my_q;
             m.gs[lane] = my_s;
             m.fcg[lane] = 0;
+            if constexpr (SCR) {
+                if (lane < 3) m.fm[lane] = 0;  // this round's column and wave masks (step 2 sets the bits)
+            }
             if (lane == 0) { m.ctl[0] = c; m.ctl[1] = cend; }
         }
         __syncthreads();
@@ -1156,6 +1211,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             const float thrf = SCR ? m.thr[lane] : 0.0f;
             const float qc = screen_req(rc), qm = screen_req(rm), qp = screen_req(rp);
             int64_t nev = 0, nex = 0;
+            uint64_t cmask = 0;  // SCR, wave-uniform: the wave's columns the confirm fold has to visit (bit = guessing pod)
             // SCR: the slots of all the wave's columns in one read (lane u: its u-th column; -1 where gn < 0), no LDS
             // trip per column for them; the guessed node comes with the slot's record
             int32_t sv = -1;
@@ -1182,6 +1238,11 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                     Srow[s] = kv;
                     m.D[k * 64 + lane] = (int8_t)d;
                     if (lane > k && d != 0) atomicAdd(&m.fcg[lane], d);
+                    // The confirm fold needs this column only where its key can count (any) or it changed the predicate
+                    // of a later pod.  Lanes <= k are not asked: the fold runs over the columns k < f, so those pods are
+                    // confirmed by then, and the fcc / rbk of a confirmed pod are never read again (the guess step, the
+                    // check and the one-by-one step read them for lanes >= c, the next round's start, only)
+                    if (any || __ballot(lane > k && d != 0) != 0) cmask |= 1ull << k;
                     if (!any) continue;  // kSkipKey never passes better()
                     ++nex;
                     if (lane > k) {
@@ -1228,8 +1289,21 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                     }
                 }
             }
-            m.pbk[wave * 64 + lane] = pk;
-            m.pbx[wave * 64 + lane] = ((int64_t)ps << 32) | (uint32_t)pi;
+            if constexpr (SCR) {
+                // (nex and cmask are wave-uniform.)  A wave that keyed no column writes no partials -- its rows keep what
+                // own[] left there -- and sets no bit: the check folds the set waves only
+                if (nex > 0 || A.fold_all) {
+                    m.pbk[wave * 64 + lane] = pk;
+                    m.pbx[wave * 64 + lane] = ((int64_t)ps << 32) | (uint32_t)pi;
+                }
+                if (lane == 0) {
+                    if (nex > 0) atomicOr(&m.fm[2], 1u << wave);
+                    if (cmask != 0) atomicOr(reinterpret_cast<unsigned long long *>(m.fm), (unsigned long long)cmask);
+                }
+            } else {
+                m.pbk[wave * 64 + lane] = pk;
+                m.pbx[wave * 64 + lane] = ((int64_t)ps << 32) | (uint32_t)pi;
+            }
             if (SCR && A.dbg && lane == 0 && nev) {  // diagnostics: guessed columns keyed, exactly
                 atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[18]), (unsigned long long)nev);
                 atomicAdd(reinterpret_cast<unsigned long long *>(&A.dbg[19]), (unsigned long long)nex);
@@ -1245,13 +1319,36 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             // t* = best of the confirmed slots and of the guessed commits before this pod
             double tk = rbk;
             int32_t ti = rbi, ts = rbs;
-            for (int w = 0; w < kSpcWaves; ++w) {
-                const double k = m.pbk[w * 64 + lane];
-                const int64_t x = m.pbx[w * 64 + lane];
-                const int32_t xi = (int32_t)(uint32_t)x;
-                const bool up = k != -__builtin_inf() && better(k, xi, tk, ti);
-                tk = up ? k : tk; ti = up ? xi : ti; ts = up ? (int32_t)(x >> 32) : ts;
+            const uint64_t tt0 = sdbg ? __builtin_amdgcn_s_memtime() : 0;
+            if constexpr (SCR) {
+                // the waves that keyed a guessed column this round, lowest first (the fold order of before, over the
+                // waves that take part): in most rounds none did, and nothing is read
+                uint32_t wm = (uint32_t)__builtin_amdgcn_readfirstlane((int)m.fm[2]) | (A.fold_all & kAllWaves);
+                if (dbg && lane == 0) {
+                    fm_count(32, wm == 0);                  // checks that read no wave's partials
+                    fm_count(33, __builtin_popcount(wm));   // partial rows read
+                    // batches with a check that read none after an earlier one that read some (1 -> 2: counted once)
+                    if (wm != 0 && m.ctl[3] == 0) m.ctl[3] = 1;
+                    if (wm == 0 && m.ctl[3] == 1) { m.ctl[3] = 2; fm_count(37, 1); }
+                }
+                for (; wm != 0; wm &= wm - 1u) {
+                    const int w = __builtin_ctz(wm);
+                    const double k = m.pbk[w * 64 + lane];
+                    const int64_t x = m.pbx[w * 64 + lane];
+                    const int32_t xi = (int32_t)(uint32_t)x;
+                    const bool up = k != -__builtin_inf() && better(k, xi, tk, ti);
+                    tk = up ? k : tk; ti = up ? xi : ti; ts = up ? (int32_t)(x >> 32) : ts;
+                }
+            } else {
+                for (int w = 0; w < kSpcWaves; ++w) {
+                    const double k = m.pbk[w * 64 + lane];
+                    const int64_t x = m.pbx[w * 64 + lane];
+                    const int32_t xi = (int32_t)(uint32_t)x;
+                    const bool up = k != -__builtin_inf() && better(k, xi, tk, ti);
+                    tk = up ? k : tk; ti = up ? xi : ti; ts = up ? (int32_t)(x >> 32) : ts;
+                }
             }
+            if (sdbg) t_tstar += __builtin_amdgcn_s_memtime() - tt0;
             const bool has_t = ti != kNoIdx;
             const int32_t fcj = fcc + m.fcg[lane];
             // kind: 0 no placement, 1 the guess (first touch), 2 t*, 3 overflow, 4 guess unknown (re-probe)
@@ -1294,18 +1391,49 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                 // bring the confirmed state of the pods still to come up to date with [c, f)
                 const uint64_t tf0 = sdbg ? __builtin_amdgcn_s_memtime() : 0;
                 float b2 = trk ? m.rb2[lane] : 0.0f;
-                for (int k = c; k < f; ++k) {
-                    const int32_t g = __builtin_amdgcn_readlane(my_g, k);
-                    if (g < 0) continue;
-                    const int s = __builtin_amdgcn_readlane(my_s, k);
-                    const double v = Srow[s];
-                    fcc += m.D[k * 64 + lane];
-                    const bool up = v != -__builtin_inf() && better(v, g, rbk, rbi);
-                    if (trk) {
-                        const double o = up ? rbk : v;  // the key that is not (or no longer) the best
-                        b2 = o > (double)b2 ? __double2float_ru(o) : b2;  // (a skipped slot's NaN leaves the bound as it is)
+                if constexpr (SCR) {
+                    // Only the columns of [c, f) that step 2 marked, in ascending order: an unmarked column holds kSkipKey
+                    // in every lane, which never passes better() and leaves rb2 as it is, and changed the predicate of
+                    // no pod after its own -- nothing of rbk / rbi / rbs / rb2, and of fcc only lanes <= k, which no one
+                    // reads again.  (A column with gn < 0 is never marked; with every column visited -- fold_all -- it
+                    // is passed over as before.)  The statements of a column are those of the unscreened loop below,
+                    // which stays as it was written: a change of its form alone moves those kernels' register allocation.
+                    const uint64_t in = (f < 64 ? (1ull << f) - 1ull : ~0ull) & ~((1ull << c) - 1ull);  // c < 64
+                    uint64_t cm = *reinterpret_cast<const uint64_t *>(m.fm);
+                    cm = ((uint64_t)rl64((int64_t)cm, 0) | (A.fold_all ? ~0ull : 0ull)) & in;
+                    if (dbg && lane == 0) {  // columns visited (a marked column has a guess) / skipped, of the ncg confirmed
+                        const int nv = A.fold_all ? ncg : (int)__popcll(cm);
+                        fm_count(35, nv);
+                        fm_count(36, ncg - nv);
                     }
-                    rbk = up ? v : rbk; rbi = up ? g : rbi; rbs = up ? s : rbs;
+                    for (; cm != 0; cm &= cm - 1ull) {
+                        const int k = (int)__builtin_ctzll(cm);
+                        const int32_t g = __builtin_amdgcn_readlane(my_g, k);
+                        if (g < 0) continue;
+                        const int s = __builtin_amdgcn_readlane(my_s, k);
+                        const double v = Srow[s];
+                        fcc += m.D[k * 64 + lane];
+                        const bool up = v != -__builtin_inf() && better(v, g, rbk, rbi);
+                        if (trk) {
+                            const double o = up ? rbk : v;  // the key that is not (or no longer) the best
+                            b2 = o > (double)b2 ? __double2float_ru(o) : b2;  // (a skipped slot's NaN leaves the bound as it is)
+                        }
+                        rbk = up ? v : rbk; rbi = up ? g : rbi; rbs = up ? s : rbs;
+                    }
+                } else {
+                    for (int k = c; k < f; ++k) {
+                        const int32_t g = __builtin_amdgcn_readlane(my_g, k);
+                        if (g < 0) continue;
+                        const int s = __builtin_amdgcn_readlane(my_s, k);
+                        const double v = Srow[s];
+                        fcc += m.D[k * 64 + lane];
+                        const bool up = v != -__builtin_inf() && better(v, g, rbk, rbi);
+                        if (trk) {
+                            const double o = up ? rbk : v;  // the key that is not (or no longer) the best
+                            b2 = o > (double)b2 ? __double2float_ru(o) : b2;  // (a skipped slot's NaN leaves the bound as it is)
+                        }
+                        rbk = up ? v : rbk; rbi = up ? g : rbi; rbs = up ? s : rbs;
+                    }
                 }
                 if (trk) m.rb2[lane] = b2;
                 if (sdbg) t_fold += __builtin_amdgcn_s_memtime() - tf0;
@@ -1361,6 +1489,8 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                 RescueOut ro{};
                 if constexpr (COH) {
                     // the persistent commit (one rank) rescues an exhausted list instead of truncating the batch
+                    const bool exh = kf == 3;
+                    const uint64_t tq0 = (sdbg && exh) ? __builtin_amdgcn_s_memtime() : 0;  // the rescue leg: look, rescue, re-key
                     bool afford = kf == 3 && A.rescue && nresc < rmax && 4 * (nresc + 1) <= rcredit;
                     if (afford && A.rescue_look) {
                         // look ahead: the later pods of the batch whose cut list is exhausted already (every entry a
@@ -1404,6 +1534,7 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
                             kf = ht ? 2 : 0;
                         }
                     }
+                    if (sdbg && exh) t_resc += __builtin_amdgcn_s_memtime() - tq0;
                 }
                 if (kf == 3) {
                     done = f;  // overflow: the batch stops before pod f
@@ -1630,12 +1761,20 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
             A.trace_row[16] = (uint64_t)nrounds | (uint64_t)nresc << 16 | (uint64_t)done << 24 | (uint64_t)nfail << 32 |
                               (uint64_t)nseq << 48;
         if (A.dbg) {
-            A.dbg[12] += nrounds; A.dbg[13] += nfail; A.dbg[14] += 1; A.dbg[5] += niters;
-            A.dbg[8] += nfull; A.dbg[31] += nseq;
+            if constexpr (SCR) {
+                // the counts, exactly: the two commit workgroups add to the same words, and a plain read-modify-write of
+                // one can fall between the other's (the fold-mask counts are compared with the rounds)
+                fm_count(12, nrounds); fm_count(13, nfail); fm_count(14, 1); fm_count(5, niters); fm_count(8, nfull);
+                fm_count(31, nseq);
+            } else {
+                A.dbg[12] += nrounds; A.dbg[13] += nfail; A.dbg[14] += 1; A.dbg[5] += niters;
+                A.dbg[8] += nfull; A.dbg[31] += nseq;
+            }
             A.dbg[0] += t_pro; A.dbg[1] += t_s1; A.dbg[2] += t_s2; A.dbg[3] += t_s3;
             if (A.trace_row) { A.trace_row[18] = t_pro; A.trace_row[19] = t_s1; A.trace_row[20] = t_s2; A.trace_row[21] = t_s3; }
             if (KSCHED_COMMIT_SPLIT && A.trace_row) {  // the check step's split: fold, probe, commit of the pod, of it the state load
                 A.trace_row[33] = t_fold; A.trace_row[34] = t_probe; A.trace_row[35] = t_pod; A.trace_row[36] = t_load;
+                A.trace_row[38] = t_tstar; A.trace_row[39] = t_resc;
             }
             A.dbg[4] += __builtin_amdgcn_s_memtime() - t_start;
             A.dbg[6] += t_pre;
@@ -1666,13 +1805,14 @@ __device__ __forceinline__ int commit_spc_batch(const CommitArgs &A, char *smem,
 template <int K, int NT = kSpcThreads, bool LAG3 = false>
 constexpr size_t spc_small_bytes() {
     return (size_t)(NT / 64) * 64 * 16 + (size_t)K * 64 * 8 + 64 * kGS * 8 + 64 * 64 + spc_slots<LAG3>() * sizeof(SpcSlot) +
-           (size_t)K * 64 * 8 + (size_t)kSpcHash * 4 + 64 * 4 + spc_slots<LAG3>() * 4 + 5 * 64 * 4 + 16 + 64 * 4 + 64 * 2;
+           (size_t)K * 64 * 8 + (size_t)kSpcHash * 4 + 64 * 4 + spc_slots<LAG3>() * 4 + 5 * 64 * 4 + 16 + 64 * 4 + 64 * 2 +
+           (LAG3 ? kFoldMaskBytes : 0);  // (the persistent commit's best-price kernels leave them unused, behind S)
 }
 template <int K, int NT = kSpcThreads, bool LAG3 = false>
 constexpr size_t spc_lds_bytes() {
     return (size_t)64 * (spc_slots<LAG3>() + 1) * 8 + (size_t)(NT / 64) * 64 * 16 + (size_t)K * 64 * 12 +
            spc_slots<LAG3>() * sizeof(SpcSlot) + (size_t)kSpcHash * 4 + (size_t)K * 64 * 4 + 64 * 4 +
-           spc_slots<LAG3>() * 4 + 5 * 64 * 4 + 16 + 64 * kGS * 8 + 64 * 4 + 64 * 2 + 64 * 64;
+           spc_slots<LAG3>() * 4 + 5 * 64 * 4 + 16 + 64 * kGS * 8 + 64 * 4 + 64 * 2 + 64 * 64 + (LAG3 ? kFoldMaskBytes : 0);
 }
 static_assert(spc_lds_bytes<16>() <= 160 * 1024, "k_commit_spc LDS");
 static_assert(spc_lds_bytes<16, kPipeThreads, true>() == spc_small_bytes<16, kPipeThreads, true>() + 64 * 193 * 8,

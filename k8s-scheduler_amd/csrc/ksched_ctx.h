@@ -145,6 +145,7 @@ struct ksched_bufs {
 //   KSCHED_NO_PAIRS              0        the screened scan's exact phase by rows (A/B of the pair lists)
 //   KSCHED_NO_SEED               0        the seeded scan's bound from all rows in every batch (A/B of the seed masks)
 //   KSCHED_NO_TOUCH_SCREEN       0        the commit keys every touched node exactly
+//   KSCHED_NO_FOLD_MASK          0        the screened commit folds every wave's partial bests and every guessed column
 //   KSCHED_NO_EARLY_INH          0        the commit loads the mergers' inherited keys only after its merges' wait
 //   KSCHED_POISON                0        workspace and LDS filled with 0xff before every persistent run
 //   KSCHED_LDS_FILL=<u32>        unset    (without POISON) LDS only, filled with this pattern before every persistent run
@@ -170,6 +171,7 @@ struct ksched_diag {
     bool no_pairs = false;        // KSCHED_NO_PAIRS
     bool no_seed = false;         // KSCHED_NO_SEED
     bool touch_screen = true;     // off with KSCHED_NO_TOUCH_SCREEN
+    bool no_fold_mask = false;    // KSCHED_NO_FOLD_MASK
     bool early_inh = true;        // off with KSCHED_NO_EARLY_INH
     bool poison = false;          // KSCHED_POISON
     std::optional<uint32_t> lds_fill;  // KSCHED_LDS_FILL (unset: no fill)
@@ -247,7 +249,7 @@ struct ksched_ctx {
     int prog_G = 0, prog_B = 0, prog_rows = 0;
     int64_t xdbg_calls = 0;       // KSCHED_XCHG_DUMP: dumps written so far
     bool persist_stats = false;  // stats come from the Ctl copy queued behind the run
-    int64_t commit_dbg[32] = {};  // KSCHED_COMMIT_STAMPS: the last persistent run's words (ksched_get_commit_stamps)
+    int64_t commit_dbg[ksched::kCommitDbgWords] = {};  // KSCHED_COMMIT_STAMPS: the last persistent run's words (ksched_get_commit_stamps)
     int64_t persist_B = 0;
     bool seed_counted = false;    // the last persistent launch ran a kernel that writes the seeded scan's counters
     int64_t seed_stats[5] = {};   // the last persistent run's seeded-scan counters (ksched_get_seed_stats)

@@ -29,6 +29,7 @@ void read_env(ksched_diag *d) {
     d->no_pairs = env_int("KSCHED_NO_PAIRS", 0) != 0;
     d->no_seed = env_int("KSCHED_NO_SEED", 0) != 0;
     d->touch_screen = env_int("KSCHED_NO_TOUCH_SCREEN", 0) == 0;
+    d->no_fold_mask = env_int("KSCHED_NO_FOLD_MASK", 0) != 0;
     d->early_inh = env_int("KSCHED_NO_EARLY_INH", 0) == 0;
     d->poison = env_int("KSCHED_POISON", 0) != 0;
     if (const std::string f = env_str("KSCHED_LDS_FILL"); !f.empty()) d->lds_fill = (uint32_t)std::strtoul(f.c_str(), nullptr, 0);
@@ -107,7 +108,7 @@ void print_persist_trace(ksched_ctx *c) {
         }
     }
     if (c->d->dbg) {
-        int64_t hd[32];
+        int64_t hd[kCommitDbgWords];
         if (hipMemcpy(hd, c->d->dbg, sizeof(hd), hipMemcpyDeviceToHost) == hipSuccess && hd[14] && hd[16])
             fprintf(stderr, "persist commit screen: export(b-1) entries %lld keyed exactly %.4f | guessed columns %lld, "
                     "exactly %.4f | sequential columns %lld, exactly %.4f | rescue re-keys %lld\n", (long long)hd[16],
@@ -127,6 +128,12 @@ void print_persist_trace(ksched_ctx *c) {
                     "%lld, %.0f cycles each | with the second-best key %lld, %.0f cycles each\n", (long long)hd[23],
                     (long long)hd[24], (long long)hd[25], (double)hd[26] / std::max<int64_t>(1, hd[25]), (long long)hd[27],
                     (double)hd[28] / std::max<int64_t>(1, hd[27]));
+        if (hd[14] && hd[16])  // the screened commit's fold masks (KSCHED_NO_FOLD_MASK=1: every wave, every column)
+            fprintf(stderr, "persist commit fold masks: checks that read no partials %lld of %lld, partial rows read %lld | "
+                    "wave-0 states that read none %lld of %lld | confirm-fold columns visited %lld skipped %lld | batches "
+                    "with a check that read none after one that read some %lld\n", (long long)hd[32], (long long)hd[12],
+                    (long long)hd[33], (long long)hd[34], (long long)hd[14], (long long)hd[35], (long long)hd[36],
+                    (long long)hd[37]);
     }
     if (c->d->mdbg) {
         int64_t hm[8];

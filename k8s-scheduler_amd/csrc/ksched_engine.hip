@@ -130,8 +130,8 @@ int enqueue_batched(ksched_ctx *c) {
     Ctl *ctl = reinterpret_cast<Ctl *>(c->d->cursor.p);
     HIPCHK(c, launch_ctl_init(ctl, pl.B, c->p, 2, sS));
     for (int r = 0; r <= kRing; ++r) HIPCHK(c, hipMemsetAsync(xbuf(r == kRing ? -1 : r), 0, 8, sS));
-    if (c->diag.commit_stamps) HIPCHK(c, c->d->dbg.reserve(32 * sizeof(int64_t)));
-    if (c->d->dbg) HIPCHK(c, hipMemsetAsync(c->d->dbg, 0, 32 * sizeof(int64_t), sS));
+    if (c->diag.commit_stamps) HIPCHK(c, c->d->dbg.reserve(kCommitDbgWords * sizeof(int64_t)));
+    if (c->d->dbg) HIPCHK(c, hipMemsetAsync(c->d->dbg, 0, kCommitDbgWords * sizeof(int64_t), sS));
     if (c->diag.merge_stamps) HIPCHK(c, c->d->mdbg.reserve(8 * sizeof(int64_t)));
     if (c->d->mdbg) HIPCHK(c, hipMemsetAsync(c->d->mdbg, 0, 8 * sizeof(int64_t), sS));
     HIPCHK(c, hipEventRecord(c->ev_pipe[0], sS));  // stream C starts after the initialisation above
@@ -340,6 +340,7 @@ int enqueue_persistent(ksched_ctx *c) {
     a.rescue_low = c->diag.rescue_low;
     a.touch_screen = c->diag.touch_screen ? 1 : 0;
     a.early_inh = c->diag.early_inh ? 1 : 0;
+    a.no_fold_mask = c->diag.no_fold_mask ? 1 : 0;
     if (c->diag.jitter) a.jitter = c->diag.jitter * 2654435761u + (uint32_t)(++c->jitter_calls) * 40503u + 1u;
     a.inh = reinterpret_cast<char *>(a.prog) + prog_b + resc_b;
     c->d_prog = a.prog;
@@ -377,9 +378,9 @@ int enqueue_persistent(ksched_ctx *c) {
         a.xdbg = c->d->xdbg;
         a.xdbg_cap = cap;
     }
-    if (c->diag.commit_stamps) HIPCHK(c, c->d->dbg.reserve(32 * sizeof(int64_t)));
+    if (c->diag.commit_stamps) HIPCHK(c, c->d->dbg.reserve(kCommitDbgWords * sizeof(int64_t)));
     if (c->d->dbg) {
-        HIPCHK(c, hipMemsetAsync(c->d->dbg, 0, 32 * sizeof(int64_t), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d->dbg, 0, kCommitDbgWords * sizeof(int64_t), c->stream));
         a.cdbg = c->d->dbg;
     }
     if (c->diag.merge_stamps) HIPCHK(c, c->d->mdbg.reserve(8 * sizeof(int64_t)));
@@ -808,7 +809,7 @@ int ksched_get_stats(const ksched_ctx *c, ksched_stats *out) {
 }
 
 int ksched_get_commit_stamps(const ksched_ctx *c, int32_t n, int64_t *out) {
-    if (!c || !out || n < 0 || n > 32) return KSCHED_E_INVALID;
+    if (!c || !out || n < 0 || n > kCommitDbgWords) return KSCHED_E_INVALID;
     for (int i = 0; i < n; ++i) out[i] = c->commit_dbg[i];
     return KSCHED_OK;
 }

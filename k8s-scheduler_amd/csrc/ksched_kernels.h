@@ -145,6 +145,8 @@ struct CommitArgs {
     int32_t rescue_rate;    // persistent: the bucket's refill per batch of this workgroup, in quarter rescues (a batch
                             // spends at most min(rescue_max, credit) rescues; rate >= 4 * rescue_max: a fixed budget)
     int32_t touch_screen;   // persistent commit: the touched-node screen on (KSCHED_NO_TOUCH_SCREEN=1 turns it off)
+    uint32_t fold_all;      // screened commit: ~0u folds every wave's partials and every guessed column (KSCHED_NO_FOLD_MASK=1),
+                            // 0 only those its fold masks name (ksched_commit.h kFoldMaskBytes)
     const char *inh;        // persistent commit: the mergers' keys of the older export (inherit_x2_keys), else null
     int64_t timeout_ticks;  // bound of the rescue wait
     int32_t *err;           // device error word (kErrWaitRescue)
@@ -152,6 +154,8 @@ struct CommitArgs {
     const PersistArgs *xp;  // persistent pipeline: its arguments (R > 1: the rescue's rank fold through the rings)
     int64_t dbg_act;        // diagnostics (KSCHED_XCHG_DUMP): this batch's active-batch index
 };
+// CommitArgs::dbg, in 8-byte words (ksched_get_commit_stamps; include/ksched.h names the words)
+constexpr int kCommitDbgWords = 48;
 // k_commit_spc's workgroup (wave 0 guesses and checks, 8 waves evaluate); commit_spc_batch's default size in k_pipe too
 constexpr int kSpcThreads = 512;
 

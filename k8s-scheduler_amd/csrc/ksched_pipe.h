@@ -177,6 +177,7 @@ struct PersistArgs {
     int32_t early_inh;      // the commit loads those keys before its merges' wait when Ctl::inh_done shows them
                             // (KSCHED_NO_EARLY_INH=1: always after the wait)
     int32_t no_seed;        // diagnostics (KSCHED_NO_SEED): the seeded scan's bound from all rows in every batch
+    int32_t no_fold_mask;   // diagnostics (KSCHED_NO_FOLD_MASK): the screened commit folds every wave and column
 };
 constexpr size_t inh_bytes(int B) { return (size_t)4 * B * 32 + (size_t)4 * B * 64 * 8; }
 // progress phases (PersistArgs::prog); kProgWords 8-byte words per workgroup
@@ -283,7 +284,8 @@ hipError_t launch_xchg_min(const PersistArgs &a, int32_t mine, int32_t *out, hip
 // 27 P1 done, 29 the check step's rescans, 30 the lists hashed; 33-36 the check step's split in cycles (the fold of
 // the confirmed columns, the probe of a pod resolved exactly, the commit of that pod, of it the wait for a listed
 // record's state; builds with -DKSCHED_COMMIT_SPLIT=1 only).  An earlier check split had columns 26-28 and 30; P1's
-// stamps took 26, 27 and 30 since, so the split moved to 33-36.  Free (no writer): 28, 31-32, 38-48.
+// stamps took 26, 27 and 30 since, so the split moved to 33-36; 38-39 (the same builds) the check's t* fold over the
+// waves' partial bests and its rescue leg (look-ahead, rescue, re-key).  Free (no writer): 28, 31-32, 40-48.
 constexpr int kTraceCols = 54;  // + 37: score WG 0 behind the bound's barrier (every wave's pass 1 / seed pass done);
                                 // 49-53: the commit's rounds
 // KSCHED_JITTER (race hunting): at one in four (workgroup, batch, site) triples, sleep the wave for up to ~50 us,

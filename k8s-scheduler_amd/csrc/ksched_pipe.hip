@@ -1735,6 +1735,7 @@ __device__ __forceinline__ void commit_role(const PersistArgs &P, char *smem, co
         ca.rescue_cap = P.rescue_cap;
         ca.rescue_low = P.rescue_low;
         ca.touch_screen = P.touch_screen;
+        ca.fold_all = P.no_fold_mask ? ~0u : 0u;
         ca.inh = P.inh;
         ca.timeout_ticks = P.timeout_ticks;
         ca.err = P.err;

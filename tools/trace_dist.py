@@ -131,7 +131,8 @@ def main():
             print(f"  {r} rescues: {s.sum()} batches, commit mean {cm[s].mean():.1f} p50 {np.median(cm[s]):.1f} max {cm[s].max():.1f} us,"
                   f" rounds mean {rounds[s].mean():.2f}, resolved {done[s].mean():.1f}")
     # The check step's split (columns 33-36: fold of the confirmed columns, probe, commit of the resolved pod, of it
-    # the wait for a listed record's state) is written only by a library built with -DKSCHED_COMMIT_SPLIT=1
+    # the wait for a listed record's state; 38-39: the t* fold over the waves' partial bests, the rescue leg -- look-ahead,
+    # rescue and re-key) is written only by a library built with -DKSCHED_COMMIT_SPLIT=1
     # (tools/build_split.sh); the rescans (29) by every build.  Columns 31-32 (the guess step's set-up / fixpoint) have
     # no writer in this tree (they printed as zeros) and are no longer printed.
     split = bool((t[b][:, 33:37] != 0).any())
@@ -139,15 +140,16 @@ def main():
     for lo, hi in ((0, 1), (1, 2), (2, 3), (3, 5), (5, 10), (10, 1 << 16)):
         s = (rounds >= lo) & (rounds < hi)
         if s.any():
-            kc = [t[b[s], c].mean() / 1e3 for c in (18, 19, 20, 21, 29, 33, 34, 35, 36)]
-            tail = (f"fold {kc[5]:.1f} probe {kc[6]:.1f} pod {kc[7]:.1f} [state load {kc[8]:.1f}] " if split else "")
+            kc = [t[b[s], c].mean() / 1e3 for c in (18, 19, 20, 21, 29, 33, 34, 35, 36, 38, 39)]
+            tail = (f"fold {kc[5]:.1f} probe {kc[6]:.1f} pod {kc[7]:.1f} [state load {kc[8]:.1f}] t* {kc[9]:.1f} rescue {kc[10]:.1f} " if split else "")
             print(f"  rounds [{lo},{hi}): {s.sum()} batches, commit mean {cm[s].mean():.1f} max {cm[s].max():.1f} us, total"
                   f" {cm[s].sum() / 1e3:.2f} ms | {kc[0]:.1f} / {kc[1]:.1f} / {kc[2]:.1f} / {kc[3]:.1f}"
                   f" (check: {tail}rescan {kc[4]:.1f})")
-    ck = [float(t[b, c].sum()) / 1e6 for c in (21, 33, 34, 35, 36, 29)]
+    ck = [float(t[b, c].sum()) / 1e6 for c in (21, 33, 34, 35, 36, 29, 38, 39)]
     if split:
         print(f"check step, Mcycles over the call: {ck[0]:.1f} = fold {ck[1]:.1f} + probe {ck[2]:.1f} + pod {ck[3]:.1f}"
-              f" [state load {ck[4]:.1f}] + rescan {ck[5]:.1f} + rest {ck[0] - ck[1] - ck[2] - ck[3] - ck[5]:.1f}")
+              f" [state load {ck[4]:.1f}] + rescan {ck[5]:.1f} + t* fold {ck[6]:.1f} + rescue leg {ck[7]:.1f}"
+              f" + rest {ck[0] - ck[1] - ck[2] - ck[3] - ck[5] - ck[6] - ck[7]:.1f}")
     else:
         print(f"check step, Mcycles over the call: {ck[0]:.1f}, of it rescans {ck[5]:.1f} (no split: the library was not"
               f" built with KSCHED_COMMIT_SPLIT)")
