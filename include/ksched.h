@@ -370,7 +370,8 @@ int ksched_schedule_gangs(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, co
  * it is loaded again); ksched_apply_delta and ksched_save_state / ksched_restore_state leave the counts alone --
  * keeping them in step is the caller's business, as with ksched_load_bound (FakeCluster.schedule_spread reloads the
  * table on every call).  ksched_schedule, ksched_schedule_gangs, ksched_rank, ksched_explain, ksched_explain_batch /
- * _pod and ksched_preempt neither read nor move the table; ksched_rank_full and ksched_explain_full read it.  After ksched_schedule_spread, ksched_explain_batch / ksched_explain_pod return
+ * _pod and ksched_preempt neither read nor move the table; ksched_rank_full, ksched_explain_full and
+ * ksched_preempt_constrained read it.  After ksched_schedule_spread, ksched_explain_batch / ksched_explain_pod return
  * KSCHED_E_STATE: they know no spread reason (KSCHED_NUM_REASONS did not change); ksched_schedule_full_why below gives
  * the reasons at a pod's turn.
  *
@@ -429,7 +430,7 @@ int ksched_schedule_spread(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, c
  * again); ksched_apply_delta and ksched_save_state / ksched_restore_state leave it alone -- keeping it in step is the
  * caller's business (FakeCluster.schedule_ext reloads the table on every call).  ksched_schedule,
  * ksched_schedule_gangs, ksched_schedule_spread, ksched_rank, ksched_explain, ksched_explain_batch / _pod and
- * ksched_preempt neither read nor move it; ksched_rank_full and ksched_explain_full read it.  After ksched_schedule_ext, ksched_explain_batch / ksched_explain_pod return KSCHED_E_STATE: they know no
+ * ksched_preempt neither read nor move it; ksched_rank_full, ksched_explain_full and ksched_preempt_constrained read it.  After ksched_schedule_ext, ksched_explain_batch / ksched_explain_pod return KSCHED_E_STATE: they know no
  * extended-resource reason (KSCHED_NUM_REASONS did not change); ksched_schedule_full_why below gives the reasons at a
  * pod's turn.
  *
@@ -437,7 +438,7 @@ int ksched_schedule_spread(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, c
  * node_ext, a negative request, p outside [0, 2^30), opts.nranks > 1.
  *
  * Out of scope: extended columns in ksched_rank, ksched_preempt and ksched_explain* (dry runs that see them:
- * ksched_rank_full and ksched_explain_full below; with gangs and spread: ksched_schedule_constrained below); the batched pipeline and multi-rank; the one-workgroup exact kernel (an ext run always takes the multi-slot one); an apply_delta for the table; init
+ * ksched_rank_full, ksched_explain_full and ksched_preempt_constrained below; with gangs and spread: ksched_schedule_constrained below); the batched pipeline and multi-rank; the one-workgroup exact kernel (an ext run always takes the multi-slot one); an apply_delta for the table; init
  * containers and pod overhead; quantity suffixes (amounts are whole numbers, pre-scaled by the caller); scoring on
  * extended resources.
  *
@@ -588,7 +589,7 @@ int ksched_schedule_constrained(ksched_ctx *ctx, int64_t p,
  * zone key; namespaceSelector, matchLabelKeys; pod removal without a reload; affinity reasons from this call itself (at
  * a pod's turn: ksched_schedule_full_why below) and ksched_rank under affinity (against the current state:
  * ksched_explain_full and ksched_rank_full below); ksched_preempt
- * under affinity; the batched pipelines and multi-rank; the one-workgroup exact kernel.
+ * under affinity (under ext and spread: ksched_preempt_constrained below); the batched pipelines and multi-rank; the one-workgroup exact kernel.
  *
  * Worked example (best-price, feasible domain, ample room): nodes n0 (zone A, price 0.1), n1 (B, 0.2), n2 (A, 0.3), n3
  * (no key, 0.4); groups web = bit 0, cache = bit 1, db = bit 2; the table starts empty.  Pods: p0, p1: member web,
@@ -747,8 +748,8 @@ int ksched_schedule_full(ksched_ctx *ctx, int64_t p,
  * NULL selector under opts.use_labels, a NULL out_counts, opts.nranks > 1 (the tables are single-GPU; there is no shard
  * merge).  KSCHED_E_STATE before ksched_load_nodes.  n_local == 0 answers as ksched_rank does: empty lists, zero counts.
  *
- * Out of scope: dry runs of a gang (members see each other's tentative commits); ksched_preempt under constraints;
- * multi-rank; ScheduleAnyway and preferred terms.  The reasons a pod of a finished constrained run saw at its turn are
+ * Out of scope: dry runs of a gang (members see each other's tentative commits); ksched_preempt under affinity
+ * (under ext and spread: ksched_preempt_constrained below); multi-rank; ScheduleAnyway and preferred terms.  The reasons a pod of a finished constrained run saw at its turn are
  * not a dry run's to give -- a rolled-back gang leaves no placements to rebuild from, and ksched_explain_batch /
  * ksched_explain_pod still return KSCHED_E_STATE after a constrained call: ksched_schedule_full_why below collects them
  * inside the run.
@@ -847,6 +848,104 @@ int ksched_schedule_full_why(ksched_ctx *ctx, int64_t p,
         int64_t *out_why_counts /* why_rows * KSCHED_NUM_REASONS_FULL */,
         int64_t node_rows, uint8_t *out_why_reason /* node_rows * n_local, or NULL with node_rows 0 */,
         int64_t *out_nofit /* or NULL */);
+
+/* ---- preemption under the extended columns and the spread table (added within ABI 6: probe with dlsym(lib, "ksched_preempt_constrained"); the version number did not move) ----
+ * ksched_preempt knows cpu, memory and pod slots.  A pod that came back KSCHED_NO_FIT from ksched_schedule_full with
+ * "Insufficient amd.com/gpu" on every node gets from it a node where cpu can be freed but no gpu can, or a victim set
+ * that reprieves the one pod holding the gpu.  kube-scheduler's default preemption removes the lower-priority pods from
+ * every filter plugin's view of the node (RemovePod), re-runs the filters, and reprieves under the same filters.  Two of
+ * the constraints here are counted, so a removal is an exact subtraction: the extended columns, as amounts, and the
+ * spread table, as counts per (group, domain).  These two calls are preemption under those two --
+ * ksched_schedule_constrained's node-level constraints.
+ *
+ * ksched_load_bound_constrained loads the one bound-pod table ksched_load_bound loads, under its rules (after
+ * ksched_load_nodes; it replaces the table held; ksched_load_nodes invalidates it; a refused load leaves the earlier
+ * table in place; KSCHED_BOUND_MAX_PER_NODE), with two more columns per pod:
+ *   bound_ext[r * nb + t] >= 0   what table pod t holds of extended resource r: what its commit subtracted from
+ *                                ext[r][node].  NULL if and only if n_ext == 0
+ *   bound_spread[t]              bit s set: pod t is counted in counts[s][.] of the spread table -- it matches group s's
+ *                                selector.  A mask, not an index: a bound pod can match several groups' selectors.  NULL:
+ *                                zeros
+ * KSCHED_E_INVALID: ksched_load_bound's cases; n_ext outside [0, KSCHED_EXT_MAX]; a NULL bound_ext with n_ext > 0 or a
+ * non-NULL one with n_ext == 0; a negative amount.  A table loaded by ksched_load_bound is the table with n_ext == 0 and
+ * every mask zero.  ksched_preempt ignores the extra columns: its outputs after this call are byte-equal to those after
+ * ksched_load_bound with the first four arrays.
+ *
+ * ksched_preempt_constrained is ksched_preempt word for word -- a dry run, each pod on its own, nothing committed; the
+ * outputs, the key, the choice, vcap, the chunks, the wait for the stream, selector under opts.use_labels -- except for
+ * the eligibility of a node.  Each constraint is on or off for the whole call by ksched_schedule_full's NULL rule
+ * (spread_group, req_ext).  Per pod i and node j, with d = the spread table's node_domain[j]; s = spread_group[i] where it
+ * is >= 0 and the pod enforces, none otherwise; C = counts[s][d] as loaded; mo = the minimum of counts[s][d'] over
+ * d' != d (absent with one domain: the minimum below is then c alone):
+ *   1. potential victims: the table's pods on j with prio < prio[i]; ksched_preempt's importance order.
+ *   2. with all of them gone: free = alloc[j] + sum of (cpu, mem, 1); fext[r] = ext[r][j] + sum of bound_ext[r][v]
+ *      (wrapping int64); rem = the potential victims with bit s in their mask.
+ *        elig(free, fext, rem) = fits(req[i], free)
+ *                                && for every r: req_ext[r][i] == 0 || req_ext[r][i] <= fext[r]
+ *                                && (s none || (d >= 0 && c + 1 - min(mo, c) <= max_skew[s])),  c = C - rem in int64
+ *      !elig: j is no candidate.
+ *   3. reprieve, most important first: elig(free - v, fext - v's amounts, rem - [v has bit s]) holds: those become the
+ *      state and v is reprieved; otherwise v is a victim.
+ *   4. the node's key, the choice (smallest key, then lowest global index) and every output column: ksched_preempt's.
+ * The preemptor's own + 1 is in the formula only: no count moves.  A pod that only counts (spread_enforce == 0) or has
+ * group -1 reads no count.  A zero extended request checks nothing, so a zero or negative column does not bar the node.
+ * elig is monotone -- more free resource and fewer counted pods never make it false -- so with its victims gone the pod
+ * is eligible on the chosen node, and with the last victim left in place it is not.  Keeping the counts and the masks
+ * consistent is the caller's business, as with every table here (FakeCluster.preempt_pod_constrained derives both from
+ * the same pods).
+ *
+ * Errors, in this order.  KSCHED_E_INVALID (nothing changed): ksched_preempt's argument rules; m outside [0, 2^30);
+ * opts.nranks > 1 (the tables are single-GPU: there is no shard merge for this call); ksched_schedule_spread's and
+ * ksched_schedule_ext's rules for the pod arrays (a group outside [-1, S), a negative request; against a table that is
+ * loaded -- without one there is no S and no array length, and the call ends in the next code).  KSCHED_E_STATE: before
+ * ksched_load_nodes; no bound-pod table; a constraint on without its table; req_ext given and the bound table's n_ext
+ * not the ext table's; spread on and a mask bit at or above the spread table's S.
+ *
+ * The call leaves byte-identical: the node rows, what ksched_read_spread and ksched_read_ext return, the staged pods, the
+ * last call's results, and the validity and content of ksched_explain_batch.  With both constraints off its outputs are
+ * byte-equal to ksched_preempt's on the same table (from kernels of its own).  With every prio[i] at or below the
+ * table's lowest priority nobody may go: out_candidates[i] is then ksched_explain_full's out_counts[0] for that pod
+ * (affinity off, the same spread and ext arguments), and out_node[i] the lowest node whose code there is 0, or
+ * KSCHED_NO_FIT.
+ *
+ * Out of scope: affinity under preemption (the affinity table keeps ORs of group bits per node and zone, and a removal
+ * cannot be taken out of an OR: it needs per-(node, group) counts first); gangs of preemptors; PDBs and start times;
+ * multi-rank; the batched pipelines; reasons for the nodes that are no candidates.
+ *
+ * Worked example.  ksched_preempt's hand cluster (tests/test_preempt_host.py; 1 MiB and 10 slots free everywhere) with
+ * one gpu column and one spread group of max_skew 1, loaded counts A 3, B 2 (one counted pod in A is not in the table):
+ *   node  alloc cpu  zone  free gpu      table pod  node  cpu  prio  gpu  in group
+ *   n0    400        A     0             0          n2    500  100   1    yes
+ *   n1    0          B     0             1          n0    600  200   1    no
+ *   n2    400        A     1             2          n1    500  200   0    yes
+ *                                        3          n0    500  100   1    yes
+ *                                        4          n1    500  50    1    yes
+ *                                        5          n2    600  200   0    no
+ * Pods: A cpu 1000, prio 1000, gpu 2, no group; B as A with prio 150 and gpu 0; C cpu 400, prio 1000, gpu 0, group 0,
+ * enforcing; D as C, counting only.
+ *   A on n0: free cpu 1500, gpu 2.  Pod 1: 900 < 1000, a victim.  Pod 3: cpu fits, but gpu 2 - 1 < 2, a victim.  Key
+ *     (200, 300 + 2^32, 2), victims [1, 3].  n1: gpu 1 < 2, no candidate.  n2: n0's key, victims [5, 0], loses the tie
+ *     on the index.  Answer: n0, 2 victims, 2 candidates (ksched_preempt: n0, victims [1], 3 candidates -- a gpu short).
+ *   B: no candidate.
+ *   C on n0: rem 1, c = 2, skew 1: a candidate.  Pod 1: reprieved.  Pod 3: c = 3, 3 + 1 - 2 = 2 > 1, a victim by the
+ *     spread rule alone.  Key (100, ...).  n1: rem 2, c = 0.  Pod 2: reprieved (cpu 500 >= 400, c = 1).  Pod 4: cpu 0 <
+ *     400, a victim.  Key (50, 50 + 2^31, 1).  n2: as n0, victim [0].  Answer: n1, victims [4], 3 candidates
+ *     (ksched_preempt: n0, no victim).
+ *   D: n0, no victim, 3 candidates.
+ * At vcap 2: out_node {0, -1, 1, 0}, out_nvictims {2, 0, 1, 0}, out_max_prio {200, INT32_MIN, 50, INT32_MIN},
+ * out_sum_prio {4294967596, 0, 2147483698, 0}, out_candidates {2, 0, 3, 3}, out_victims {[1, 3], [-1, -1], [4, -1],
+ * [-1, -1]}. */
+int ksched_load_bound_constrained(ksched_ctx *ctx, int64_t nb, const int32_t *node_idx, const int64_t *cpu,
+        const int64_t *mem, const int32_t *prio,
+        int32_t n_ext, const int64_t *bound_ext /* n_ext * nb, bound_ext[r * nb + t]; NULL iff n_ext == 0 */,
+        const uint64_t *bound_spread /* nb, or NULL = zeros */);
+int ksched_preempt_constrained(ksched_ctx *ctx, int64_t m,
+        const int64_t *req_cpu, const int64_t *req_mem, const int64_t *req_pods, const uint64_t *selector,
+        const int32_t *prio,
+        const int32_t *spread_group /* m, or NULL */, const uint8_t *spread_enforce /* m, or NULL = all 1 */,
+        const int64_t *req_ext /* n_ext * m, req_ext[r * m + i], or NULL */,
+        int32_t vcap, int32_t *out_node, int32_t *out_nvictims, int32_t *out_max_prio, int64_t *out_sum_prio,
+        int32_t *out_candidates, int32_t *out_victims);
 
 /* Same, in two halves, with the pods staged in HBM: upload once, run many times (bench). */
 int ksched_upload_pods(ksched_ctx *ctx, int64_t p, const int64_t *req_cpu, const int64_t *req_mem,

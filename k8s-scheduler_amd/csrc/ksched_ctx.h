@@ -125,6 +125,9 @@ struct ksched_bufs {
     DevBuf<int64_t> bcpu, bmem, boff;     // ksched_load_bound: the bound-pod table (BoundTable, ksched_preempt.h)
     DevBuf<int32_t> bprio, btidx, bdepth, bseg;
     DevBuf<void> vws;                     // ksched_preempt: one chunk's pods, span parts and outputs
+    DevBuf<int64_t> bext;                 // ksched_load_bound_constrained: the table's extended amounts, [bound_R][entries]
+    DevBuf<uint64_t> bmask;               // ... and group masks, [entries] (zeros behind ksched_load_bound, filled on first use)
+    DevBuf<void> cws;                     // ksched_preempt_constrained: the groups' minima, one chunk's pods, span parts and outputs
     DevBuf<void> pws;                     // persistent pipeline: part lists, list / export rings, progress words, ...
     DevBuf<uint64_t> trace;               // KSCHED_PERSIST_TRACE: per-batch wall-clock stamps [rows][kTraceCols]
     DevBuf<uint64_t> trace_wg;            // KSCHED_TRACE_WG: per batch and score workgroup {start, arrival}
@@ -213,6 +216,10 @@ struct ksched_ctx {
     uint64_t snap_max_abs_alloc = 0;  // max_abs_alloc of the save_state snapshot
     int64_t perm_n = -1;         // the node count d->perm was built for (-1: none; k_exact1 needs perm_n == n_local)
     bool bound_valid = false;    // ksched_load_bound's table describes the loaded nodes (every load_nodes clears it)
+    int32_t bound_R = 0;         // ... its extended columns (ksched_load_bound_constrained's n_ext; ksched_load_bound: 0)
+    uint64_t bound_mask_or = 0;  // ... every group mask of it ORed (ksched_load_bound: 0)
+    int64_t bound_entries = 0;   // ... its entries (64 * the sum of the blocks' depths)
+    bool bound_mask_dev = false; // ... d->bmask holds its masks
     int32_t spread_D = 0, spread_S = 0;  // ksched_load_spread's table; 0: none (every load_nodes clears it)
     int32_t ext_R = 0;           // ksched_load_ext's table: its resource columns; 0: none (every load_nodes clears it)
     bool aff_valid = false;      // ksched_load_affinity's table describes the loaded nodes (every load_nodes clears it)

@@ -7,6 +7,7 @@
 
 #include "ksched_ctx.h"
 #include "ksched_preempt.h"
+#include "ksched_preemptc.h"
 #include "ksched_rank.h"
 
 using namespace ksched;
@@ -643,22 +644,50 @@ int ksched_rank_merge(int32_t priority, int32_t nranks, int64_t m, int32_t k, co
     return KSCHED_OK;
 }
 
-// The bound-pod table of ksched_preempt: built on the host (build_bound_table), uploaded in the stream of the
-// kernels that read it.  Touches no node row; the context holds no table until the last copy has landed.
-int ksched_load_bound(ksched_ctx *c, int64_t nb, const int32_t *node_idx, const int64_t *cpu, const int64_t *mem,
-                      const int32_t *prio) {
-    if (!c) return KSCHED_E_INVALID;
-    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_bound before load_nodes");
-    static_assert(KSCHED_BOUND_MAX_PER_NODE == kBoundMaxPerNode, "segment bound");
-    if (nb < 0 || nb >= 0x7fffffff || (nb > 0 && (!node_idx || !cpu || !mem || !prio)))
-        return fail(c, KSCHED_E_INVALID, "load_bound: bad arguments");
+}  // extern "C"
+
+// The six output columns of ksched_preempt and ksched_preempt_constrained (any pointer may be null).
+namespace {
+struct PreemptOut {
+    int32_t *node, *nvictims, *max_prio;
+    int64_t *sum_prio;
+    int32_t *candidates, *victims;
+    // m pods without a candidate
+    void no_candidate(int64_t m, int32_t vcap) const {
+        if (node) std::fill(node, node + m, KSCHED_NO_FIT);
+        if (nvictims) std::fill(nvictims, nvictims + m, 0);
+        if (max_prio) std::fill(max_prio, max_prio + m, KSCHED_PREEMPT_NO_VICTIM_PRIO);
+        if (sum_prio) std::fill(sum_prio, sum_prio + m, (int64_t)0);
+        if (candidates) std::fill(candidates, candidates + m, 0);
+        if (victims) std::fill(victims, victims + (size_t)m * vcap, -1);
+    }
+    // a chunk's mc pods from pod `at` on, out of its staged copy: ho holds the node column, the others at these offsets
+    void chunk(int64_t at, int64_t mc, int32_t vcap, const char *ho, size_t nv, size_t mx, size_t sum, size_t cand, size_t vic) const {
+        if (node) std::memcpy(node + at, ho, (size_t)mc * 4);
+        if (nvictims) std::memcpy(nvictims + at, ho + nv, (size_t)mc * 4);
+        if (max_prio) std::memcpy(max_prio + at, ho + mx, (size_t)mc * 4);
+        if (sum_prio) std::memcpy(sum_prio + at, ho + sum, (size_t)mc * 8);
+        if (candidates) std::memcpy(candidates + at, ho + cand, (size_t)mc * 4);
+        if (victims) std::memcpy(victims + (size_t)at * vcap, ho + vic, (size_t)mc * vcap * 4);
+    }
+};
+}  // namespace
+
+// The bound-pod table of ksched_preempt and ksched_preempt_constrained: built on the host (build_bound_table; x's extra
+// columns beside it, pc_pack_columns), uploaded in the stream of the kernels that read it.  Touches no node row; the
+// context holds no table until the last copy has landed.  The arguments have passed the caller's checks.
+static int load_bound_table(ksched_ctx *c, const std::string &nm, const PcBound &x) {
     BoundTableHost h;
+    std::vector<int64_t> hext;
+    std::vector<uint64_t> hmask;
+    uint64_t mask_or = 0;
     const char *why = "";
     try {
-        if (!build_bound_table(c->n_local, nb, node_idx, cpu, mem, prio, &h, &why))
-            return fail(c, KSCHED_E_INVALID, std::string("load_bound: ") + why);
+        if (!build_bound_table(c->n_local, x.nb, x.node_idx, x.cpu, x.mem, x.prio, &h, &why))
+            return fail(c, KSCHED_E_INVALID, nm + ": " + why);
+        if (x.n_ext > 0 || x.bound_spread) pc_pack_columns(h.tidx, x, &hext, &hmask, &mask_or);
     } catch (const std::bad_alloc &) {
-        return fail(c, KSCHED_E_NOMEM, "load_bound: host allocation of the table failed");
+        return fail(c, KSCHED_E_NOMEM, nm + ": host allocation of the table failed");
     }
     HIPCHK(c, hipSetDevice(c->dev));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -672,10 +701,12 @@ int ksched_load_bound(ksched_ctx *c, int64_t nb, const int32_t *node_idx, const 
     if (r == hipSuccess) r = d.boff.reserve(nblk * 8);
     if (r == hipSuccess) r = d.bdepth.reserve(nblk * 4);
     if (r == hipSuccess) r = d.bseg.reserve(n * 4);
+    if (r == hipSuccess && x.n_ext > 0) r = d.bext.reserve(hext.size() * 8);
+    if (r == hipSuccess && x.bound_spread) r = d.bmask.reserve(e * 8);
     if (r != hipSuccess) {
         (void)hipGetLastError();
-        if (r == hipErrorOutOfMemory) return fail(c, KSCHED_E_NOMEM, "load_bound: device allocation of the table failed");
-        return fail(c, KSCHED_E_DEVICE, std::string("load_bound: ") + hipGetErrorString(r));
+        if (r == hipErrorOutOfMemory) return fail(c, KSCHED_E_NOMEM, nm + ": device allocation of the table failed");
+        return fail(c, KSCHED_E_DEVICE, nm + ": " + hipGetErrorString(r));
     }
     auto up = [&](void *dst, const void *src, size_t bytes) {
         return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
@@ -684,9 +715,38 @@ int ksched_load_bound(ksched_ctx *c, int64_t nb, const int32_t *node_idx, const 
     HIPCHK(c, up(d.bprio, h.prio.data(), e * 4)); HIPCHK(c, up(d.btidx, h.tidx.data(), e * 4));
     HIPCHK(c, up(d.boff, h.off.data(), nblk * 8)); HIPCHK(c, up(d.bdepth, h.depth.data(), nblk * 4));
     HIPCHK(c, up(d.bseg, h.seg.data(), n * 4));
+    if (x.n_ext > 0) HIPCHK(c, up(d.bext, hext.data(), hext.size() * 8));
+    if (x.bound_spread) HIPCHK(c, up(d.bmask, hmask.data(), e * 8));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors go away with this call
+    c->bound_R = x.n_ext; c->bound_mask_or = mask_or; c->bound_entries = (int64_t)e; c->bound_mask_dev = x.bound_spread != nullptr;
     c->bound_valid = true;
     return KSCHED_OK;
+}
+
+extern "C" {
+
+int ksched_load_bound(ksched_ctx *c, int64_t nb, const int32_t *node_idx, const int64_t *cpu, const int64_t *mem,
+                      const int32_t *prio) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_bound before load_nodes");
+    static_assert(KSCHED_BOUND_MAX_PER_NODE == kBoundMaxPerNode, "segment bound");
+    if (nb < 0 || nb >= 0x7fffffff || (nb > 0 && (!node_idx || !cpu || !mem || !prio)))
+        return fail(c, KSCHED_E_INVALID, "load_bound: bad arguments");
+    return load_bound_table(c, "load_bound", PcBound{nb, node_idx, cpu, mem, prio, 0, nullptr, nullptr});
+}
+
+// ksched_load_bound with the table's two extra columns (ksched_preemptc.h has the checks and the packing).
+int ksched_load_bound_constrained(ksched_ctx *c, int64_t nb, const int32_t *node_idx, const int64_t *cpu, const int64_t *mem,
+                                  const int32_t *prio, int32_t n_ext, const int64_t *bound_ext, const uint64_t *bound_spread) {
+    if (!c) return KSCHED_E_INVALID;
+    if (c->n_local < 0) return fail(c, KSCHED_E_STATE, "load_bound_constrained before load_nodes");
+    const PcBound x{nb, node_idx, cpu, mem, prio, n_ext, bound_ext, bound_spread};
+    try {
+        if (const char *why = pc_check_bound(x, c->n_local)) return fail(c, KSCHED_E_INVALID, std::string("load_bound_constrained: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "load_bound_constrained: host allocation failed");
+    }
+    return load_bound_table(c, "load_bound_constrained", x);
 }
 
 // Preemption dry run (ksched_preempt.hip).  As ksched_rank: its pods, span parts and outputs live in a workspace of its
@@ -706,12 +766,8 @@ int ksched_preempt(ksched_ctx *c, int64_t m, const int64_t *rc, const int64_t *r
     if (m == 0) return KSCHED_OK;
     const int64_t n = c->n_local;
     if (n == 0) {  // an empty shard has no candidate
-        if (out_node) std::fill(out_node, out_node + m, KSCHED_NO_FIT);
-        if (out_nvictims) std::fill(out_nvictims, out_nvictims + m, 0);
-        if (out_max_prio) std::fill(out_max_prio, out_max_prio + m, KSCHED_PREEMPT_NO_VICTIM_PRIO);
-        if (out_sum_prio) std::fill(out_sum_prio, out_sum_prio + m, (int64_t)0);
-        if (out_candidates) std::fill(out_candidates, out_candidates + m, 0);
-        if (out_victims) std::fill(out_victims, out_victims + (size_t)m * vcap, -1);
+        const PreemptOut out{out_node, out_nvictims, out_max_prio, out_sum_prio, out_candidates, out_victims};
+        out.no_candidate(m, vcap);
         return KSCHED_OK;
     }
     // the workspace of one chunk: pods | span parts | counts | outputs, each 256-byte aligned
@@ -764,13 +820,110 @@ int ksched_preempt(ksched_ctx *c, int64_t m, const int64_t *rc, const int64_t *r
         const size_t cp = out_victims ? (o_vic - o_node) + (size_t)mc * vcap * 4 : out_bytes;
         HIPCHK(c, hipMemcpyAsync(stage.data(), w + o_node, cp, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the next chunk reuses the workspace and the staging buffer
-        const char *ho = stage.data();  // the outputs, at their workspace offsets less o_node
-        if (out_node) std::memcpy(out_node + at, ho, (size_t)mc * 4);
-        if (out_nvictims) std::memcpy(out_nvictims + at, ho + (o_nv - o_node), (size_t)mc * 4);
-        if (out_max_prio) std::memcpy(out_max_prio + at, ho + (o_mx - o_node), (size_t)mc * 4);
-        if (out_sum_prio) std::memcpy(out_sum_prio + at, ho + (o_sum - o_node), (size_t)mc * 8);
-        if (out_candidates) std::memcpy(out_candidates + at, ho + (o_cand - o_node), (size_t)mc * 4);
-        if (out_victims) std::memcpy(out_victims + (size_t)at * vcap, ho + (o_vic - o_node), (size_t)mc * vcap * 4);
+        const PreemptOut out{out_node, out_nvictims, out_max_prio, out_sum_prio, out_candidates, out_victims};
+        out.chunk(at, mc, vcap, stage.data(), o_nv - o_node, o_mx - o_node, o_sum - o_node, o_cand - o_node, o_vic - o_node);
+    }
+    return KSCHED_OK;
+}
+
+// Preemption dry run under the extended columns and the spread table (ksched_preemptc.hip).  ksched_preempt's shape:
+// the groups' minima, one chunk's pods, span parts and outputs live in a workspace of its own (d->cws); every check
+// (ksched_preemptc.h) runs before anything is allocated or staged; nothing a schedule call left behind is touched.
+int ksched_preempt_constrained(ksched_ctx *c, int64_t m, const int64_t *rc, const int64_t *rm, const int64_t *rp,
+                               const uint64_t *sel, const int32_t *prio, const int32_t *spread_group,
+                               const uint8_t *spread_enforce, const int64_t *req_ext, int32_t vcap, int32_t *out_node,
+                               int32_t *out_nvictims, int32_t *out_max_prio, int64_t *out_sum_prio, int32_t *out_candidates,
+                               int32_t *out_victims) {
+    if (!c) return KSCHED_E_INVALID;
+    PcPacked k;
+    try {
+        const PcCall call{m, rc, rm, rp, sel, prio, spread_group, spread_enforce, req_ext, vcap};
+        const PcState st{c->n_local >= 0, c->o.use_labels != 0, c->o.nranks, c->bound_valid, c->bound_R, c->bound_mask_or,
+                         c->spread_S, c->ext_R};
+        const char *why = nullptr;
+        if (const int code = pc_check_pack(call, st, &k, &why)) return fail(c, code, std::string("preempt_constrained: ") + why);
+    } catch (const std::bad_alloc &) {
+        return fail(c, KSCHED_E_NOMEM, "preempt_constrained: host staging buffer");
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (m == 0) return KSCHED_OK;
+    const int64_t n = c->n_local;
+    const PreemptOut out{out_node, out_nvictims, out_max_prio, out_sum_prio, out_candidates, out_victims};
+    if (n == 0) {  // no node, no candidate
+        out.no_candidate(m, vcap);
+        return KSCHED_OK;
+    }
+    ksched_bufs &d = *c->d;
+    if (k.spread && !c->bound_mask_dev) {  // a table without masks: the column of zeros it stands for
+        HIPCHK(c, d.bmask.reserve((size_t)c->bound_entries * 8));
+        if (c->bound_entries > 0) HIPCHK(c, hipMemsetAsync(d.bmask, 0, (size_t)c->bound_entries * 8, c->stream));
+        c->bound_mask_dev = true;
+    }
+    // the workspace: minima | one chunk's pods | span parts | counts | outputs, each 256-byte aligned
+    const int64_t mc_max = std::min<int64_t>(m, kPreemptChunk);
+    size_t np = 0;  // span parts of the largest chunk: at most kPreemptGridWGs * kPreemptCTile (preemptc_geometry)
+    for (int64_t q : {mc_max, m % kPreemptChunk}) {  // the full chunk and the tail (fewer pods, more spans)
+        if (q <= 0) continue;
+        int32_t s; int64_t rows;
+        preemptc_geometry(n, q, &s, &rows);
+        np = std::max(np, (size_t)q * (size_t)s);
+    }
+    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t q = (size_t)mc_max;
+    constexpr size_t kPod = 36 + KSCHED_EXT_MAX * 8 + 4;  // rc | rm | rp | sel | er[4] | prio | sg per pod
+    const size_t o_min = 0, o_pods = al(o_min + (size_t)KSCHED_SPREAD_MAX_GROUPS * kPreemptCMinWords * 4),
+                 o_part = al(o_pods + q * kPod), o_nc = al(o_part + np * sizeof(PreemptPart)),
+                 o_node = al(o_nc + np * 4), o_nv = al(o_node + q * 4), o_mx = al(o_nv + q * 4), o_sum = al(o_mx + q * 4),
+                 o_cand = al(o_sum + q * 8), o_vic = al(o_cand + q * 4), total = al(o_vic + q * (size_t)vcap * 4);
+    HIPCHK(c, d.cws.reserve(total));
+    char *w = static_cast<char *>(d.cws.p);
+    PreemptCArgs A{};
+    A.bext = d.bext; A.entries = c->bound_entries; A.bmask = d.bmask;
+    if (k.ext) { A.ext = d.etab; A.n_ext = c->ext_R; }
+    if (k.spread) { A.sp_dom = d.sdom; A.sp_cnt = d.scnt; A.sp_skew = d.sskew; A.sp_D = c->spread_D; A.sp_S = c->spread_S; }
+    A.sp_min = reinterpret_cast<int32_t *>(w + o_min);
+    HIPCHK(c, launch_preemptc_min(A, c->stream));
+    // the victims leave only when asked for: up to 4 MiB of the chunk's copy out
+    const size_t out_bytes = (out_victims ? total : o_vic) - o_node;
+    std::vector<char> stage(std::max(q * kPod, out_bytes));  // host side of the chunk's two copies
+    for (int64_t at = 0; at < m; at += kPreemptChunk) {
+        const int64_t mc = std::min<int64_t>(kPreemptChunk, m - at);
+        PreemptArgs &a = A.a;
+        a = PreemptArgs{};
+        a.nodes = d.nodes; a.n_local = n; a.node_offset = c->o.node_offset;
+        a.tb.cpu = d.bcpu; a.tb.mem = d.bmem; a.tb.prio = d.bprio; a.tb.tidx = d.btidx;
+        a.tb.off = d.boff; a.tb.depth = d.bdepth; a.tb.seg = d.bseg;
+        int64_t *dp = reinterpret_cast<int64_t *>(w + o_pods);
+        a.rc = dp; a.rm = dp + mc; a.rp = dp + 2 * mc; a.sel = reinterpret_cast<uint64_t *>(dp + 3 * mc);
+        A.er = dp + 4 * mc;
+        a.prio = reinterpret_cast<int32_t *>(dp + (4 + KSCHED_EXT_MAX) * mc);
+        A.sg = a.prio + mc;
+        a.m = (int32_t)mc; a.vcap = vcap;
+        preemptc_geometry(n, mc, &a.spans, &a.span_rows);
+        if ((size_t)mc * a.spans > np) return fail(c, KSCHED_E_NOMEM, "preempt_constrained: workspace bound");  // (preemptc_geometry's bound)
+        a.part = reinterpret_cast<PreemptPart *>(w + o_part); a.part_nc = reinterpret_cast<int32_t *>(w + o_nc);
+        a.out_node = reinterpret_cast<int32_t *>(w + o_node); a.out_nvictims = reinterpret_cast<int32_t *>(w + o_nv);
+        a.out_max_prio = reinterpret_cast<int32_t *>(w + o_mx); a.out_sum_prio = reinterpret_cast<int64_t *>(w + o_sum);
+        a.out_candidates = reinterpret_cast<int32_t *>(w + o_cand); a.out_victims = reinterpret_cast<int32_t *>(w + o_vic);
+        // one copy in and one copy out per chunk, in the stream of the kernels
+        int64_t *hp = reinterpret_cast<int64_t *>(stage.data());
+        std::memcpy(hp, rc + at, (size_t)mc * 8);
+        std::memcpy(hp + mc, rm + at, (size_t)mc * 8);
+        std::memcpy(hp + 2 * mc, rp + at, (size_t)mc * 8);
+        if (sel) std::memcpy(hp + 3 * mc, sel + at, (size_t)mc * 8);
+        else std::memset(hp + 3 * mc, 0, (size_t)mc * 8);
+        std::memcpy(hp + 4 * mc, k.er.data() + (size_t)at * KSCHED_EXT_MAX, (size_t)mc * KSCHED_EXT_MAX * 8);
+        int32_t *hq = reinterpret_cast<int32_t *>(hp + (4 + KSCHED_EXT_MAX) * mc);
+        std::memcpy(hq, prio + at, (size_t)mc * 4);
+        std::memcpy(hq + mc, k.sg.data() + at, (size_t)mc * 4);
+        HIPCHK(c, hipMemcpyAsync(dp, hp, (size_t)mc * kPod, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_preemptc(c->o.use_labels != 0, A, c->stream));
+        // (a short chunk's victims are [mc][vcap] from o_vic: the copy covers them)
+        const size_t cp = out_victims ? (o_vic - o_node) + (size_t)mc * vcap * 4 : out_bytes;
+        HIPCHK(c, hipMemcpyAsync(stage.data(), w + o_node, cp, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // the next chunk reuses the workspace and the staging buffer
+        out.chunk(at, mc, vcap, stage.data(), o_nv - o_node, o_mx - o_node, o_sum - o_node, o_cand - o_node, o_vic - o_node);
     }
     return KSCHED_OK;
 }

@@ -76,9 +76,10 @@ struct PreemptArgs {
 };
 
 // The spans of a chunk of m pods over n rows (rank_geometry's rule): as many as keep the scan grid near
-// kPreemptGridWGs workgroups, none shorter than kPreemptSpanMin rows; spans * m <= kPreemptGridWGs * kPreemptTile.
-inline void preempt_geometry(int64_t n, int64_t m, int32_t *spans, int64_t *span_rows) {
-    const int64_t tiles = (m + kPreemptTile - 1) / kPreemptTile;
+// kPreemptGridWGs workgroups, none shorter than kPreemptSpanMin rows; spans * m <= kPreemptGridWGs * tile (tile: the
+// scan's pods per wave).
+inline void preempt_geometry(int64_t n, int64_t m, int32_t *spans, int64_t *span_rows, int tile = kPreemptTile) {
+    const int64_t tiles = (m + tile - 1) / tile;
     int64_t s = kPreemptGridWGs / (tiles < 1 ? 1 : tiles);
     const int64_t smax = (n + kPreemptSpanMin - 1) / kPreemptSpanMin;
     if (s > smax) s = smax;

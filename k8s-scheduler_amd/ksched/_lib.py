@@ -164,6 +164,9 @@ SIGNATURES = [
                                    C.c_int32, I32P, F64P, U8P, I32P, I32P, I64P]),
     ("ksched_explain_full", C.c_int, [CTX, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, I64P,
                                       C.c_uint64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32, I64P, U8P]),
+    ("ksched_load_bound_constrained", C.c_int, [CTX, C.c_int64, I32P, I64P, I64P, I32P, C.c_int32, I64P, U64P]),
+    ("ksched_preempt_constrained", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P, I32P, I32P, U8P, I64P, C.c_int32,
+                                             I32P, I32P, I32P, I64P, I32P, I32P]),
     ("ksched_upload_pods", C.c_int, [CTX, C.c_int64, I64P, I64P, I64P, U64P]),
     ("ksched_run", C.c_int, [CTX]),
     ("ksched_sync", C.c_int, [CTX]),

@@ -275,6 +275,47 @@ class Engine:
                                          L.ptr(cand, C.c_int32), L.ptr(vic, C.c_int32)), "preempt")
         return node, nv, mx, sm, cand, vic
 
+    def load_bound_constrained(self, node_idx, cpu, mem, prio, bound_ext=None, bound_spread=None):
+        """load_bound() with the table's two extra columns (ksched_load_bound_constrained): bound_ext[r, t] >= 0, int64
+        [R, nb] (None: no columns), is what table pod t holds of extended resource r; bound_spread[t], uint64[nb]
+        (None: zeros), has bit s where the pod is counted in group s of the load_spread() table.  preempt() ignores
+        both."""
+        ix = np.ascontiguousarray(node_idx, dtype=np.int32)
+        bc, bm = _i64(cpu), _i64(mem)
+        bp = np.ascontiguousarray(prio, dtype=np.int32)
+        nb = ix.shape[0]
+        assert bc.shape[0] == nb and bm.shape[0] == nb and bp.shape[0] == nb
+        be = None if bound_ext is None else np.ascontiguousarray(bound_ext, dtype=np.int64)
+        bs = None if bound_spread is None else np.ascontiguousarray(bound_spread, dtype=np.uint64)
+        assert (be is None or (be.ndim == 2 and be.shape[1] == nb)) and (bs is None or bs.shape == (nb,))
+        self._chk(L.lib().ksched_load_bound_constrained(
+            self._ctx, nb, L.ptr(ix, C.c_int32), L.ptr(bc, C.c_int64), L.ptr(bm, C.c_int64), L.ptr(bp, C.c_int32),
+            0 if be is None else be.shape[0], L.ptr(be, C.c_int64), L.ptr(bs, C.c_uint64)), "load_bound_constrained")
+
+    def preempt_constrained(self, req_cpu, req_mem, req_pods, selector, prio, group=None, enforce=None, req_ext=None,
+                            vcap: int = 16):
+        """preempt() under the load_ext() columns and the load_spread() table (ksched_preempt_constrained): a node is
+        a candidate, and a bound pod is reprieved, only where the pod also holds its extended requests and satisfies
+        its spread constraint with the victims' amounts returned and their counts taken off; against the
+        load_bound_constrained() table.  group and req_ext switch their constraint on as in schedule_constrained().
+        Nothing is committed and no table moves.  Returns preempt()'s six columns."""
+        rc, rm, rp = _i64(req_cpu), _i64(req_mem), _i64(req_pods)
+        m = rc.shape[0]
+        pr = np.ascontiguousarray(prio, dtype=np.int32)
+        assert rm.shape[0] == m and rp.shape[0] == m and pr.shape[0] == m
+        sel = None if selector is None else np.ascontiguousarray(selector, dtype=np.uint64)
+        cs = _Constraints(self, None, None, group, enforce, req_ext)
+        cs.check(m)
+        node = np.empty(m, np.int32); nv = np.empty(m, np.int32); mx = np.empty(m, np.int32)
+        sm = np.empty(m, np.int64); cand = np.empty(m, np.int32)
+        vic = np.empty((m, max(int(vcap), 0)), np.int32)
+        self._chk(L.lib().ksched_preempt_constrained(
+            self._ctx, m, L.ptr(rc, C.c_int64), L.ptr(rm, C.c_int64), L.ptr(rp, C.c_int64), L.ptr(sel, C.c_uint64),
+            L.ptr(pr, C.c_int32), *cs.spread, *cs.ext, int(vcap), L.ptr(node, C.c_int32), L.ptr(nv, C.c_int32),
+            L.ptr(mx, C.c_int32), L.ptr(sm, C.c_int64), L.ptr(cand, C.c_int32), L.ptr(vic, C.c_int32)),
+            "preempt_constrained")
+        return node, nv, mx, sm, cand, vic
+
     def read_nodes(self):
         ac = np.empty(self.n, np.int64); am = np.empty(self.n, np.int64); ap = np.empty(self.n, np.int64)
         self._chk(L.lib().ksched_read_nodes(self._ctx, self.n, L.ptr(ac, C.c_int64), L.ptr(am, C.c_int64),

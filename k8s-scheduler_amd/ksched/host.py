@@ -433,6 +433,29 @@ def ext_tables(nodes: List[Node], bound: List[Pod], pending: List[Pod], names: O
     return names, node_ext, req_ext
 
 
+def bound_constraint_columns(bound: List[Pod], pending: List[Pod], names: List[str]):
+    """The two extra columns of ksched_load_bound_constrained's table from Kubernetes objects, for the bound pods in
+    their order: what each holds of the extended resources `names` (ext_tables' names; its one empty column where
+    there is none), and the mask of the spread groups that count it -- spread_tables' groups for the same pending
+    pods, one per distinct (selector, maxSkew) in their order, bit s where the pod's labels match group s's selector.
+    Returns (bound_ext int64[R, nb], bound_spread uint64[nb])."""
+    bound_ext = np.zeros((max(len(names), 1), len(bound)), np.int64)
+    for r, name in enumerate(names):
+        for t, pod in enumerate(bound):
+            bound_ext[r, t] = sum(_whole(c.requests[name], f"pod {pod.name}, {name}")
+                                  for c in pod.containers if name in c.requests)
+    groups: Dict[tuple, int] = {}
+    for pod in pending:
+        if pod.spread is not None:
+            groups.setdefault((pod.spread.match_labels, pod.spread.max_skew), len(groups))
+    bound_spread = np.zeros(len(bound), np.uint64)
+    for (match_labels, _), s in groups.items():
+        for t, pod in enumerate(bound):
+            if all(pod.labels.get(k) == v for k, v in match_labels):
+                bound_spread[t] |= np.uint64(1) << np.uint64(s)
+    return bound_ext, bound_spread
+
+
 def parse_price(s: str) -> float:
     out = C.c_float(0)
     r = L.lib().ksched_parse_price(s.encode(), C.byref(out))
@@ -626,6 +649,34 @@ class FakeCluster:
             selector = self.selector_of(pod)
         sel = np.asarray([selector], dtype=np.uint64) if self.use_labels else None
         node, nv, _, _, _, vic = self.engine.preempt(rc, rm, rp, sel, [pod.priority], vcap=L.BOUND_MAX_PER_NODE)
+        return self._preempt_answer(pod, bound, node, nv, vic, evict)
+
+    def preempt_pod_constrained(self, pod: Pod, evict: bool = False, selector: Optional[int] = None):
+        """preempt_pod under the pod's extended-resource requests and spread constraint (ksched_preempt_constrained):
+        a node counts, and a bound pod stays, only where the pod would also hold its extended requests and satisfy its
+        spread constraint with the victims gone.  The spread and extended-resource tables and the bound-pod table --
+        with each bound pod's extended amounts and group mask (bound_constraint_columns) -- are reloaded from self.pods
+        (spread_tables, ext_tables) on every call.  Everything else is preempt_pod's: the answer, FitError, evict=True
+        through the DELETED path with one Preempted event per victim, and the pod itself never bound."""
+        bound = [p for p in self.pods if p.node_name]
+        node_domain, skew, counts, group, enforce = spread_tables(self.nodes, bound, [pod])
+        names, node_ext, req_ext = ext_tables(self.nodes, bound, [pod])
+        bound_ext, bound_spread = bound_constraint_columns(bound, [pod], names)
+        self.engine.load_spread(node_domain, skew, counts)
+        self.engine.load_ext(node_ext)
+        bc, bm, _ = pack_pods(bound)
+        self.engine.load_bound_constrained([self._node_index(p.node_name) for p in bound], bc, bm,
+                                           [p.priority for p in bound], bound_ext, bound_spread)
+        rc, rm, rp = pack_pods([pod])
+        if selector is None:
+            selector = self.selector_of(pod)
+        sel = np.asarray([selector], dtype=np.uint64) if self.use_labels else None
+        node, nv, _, _, _, vic = self.engine.preempt_constrained(rc, rm, rp, sel, [pod.priority], group, enforce, req_ext,
+                                                                 vcap=L.BOUND_MAX_PER_NODE)
+        return self._preempt_answer(pod, bound, node, nv, vic, evict)
+
+    def _preempt_answer(self, pod: Pod, bound: List[Pod], node, nv, vic, evict: bool):
+        """A one-pod preemption answer as (Node, [victim Pods]), the victims evicted where asked (preempt_pod)."""
         if node[0] == L.NO_FIT:
             raise FitError(f"Unable to schedule pod ({pod.name}): no node fits it even without its lower-priority pods")
         target = self.nodes[int(node[0])]
